@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- IQ Msamples/s through FFT + FIR + BPSK demod on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload pipeline|fft|bpsk] [--streams S] [--samples L]
+    python bench.py --gpus N --steps K --warmup W [--workload pipeline|fft|bpsk] [--streams S] [--samples L] [--dump-outputs DIR]
 
 One STEP = one pass of the hot path over one HBM-resident batch of synthetic input:
     S streams x L int16 IQ samples (96 kHz FUNcube-style DBPSK carrying valid FEC frames, generated on
@@ -105,6 +105,9 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-validate", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a fixed, seeded sample of larger outputs, with the sampled rows in <name>_rows.npy)")
     ap.add_argument("--demod-mode", default="am", choices=["am", "nfm", "wfm", "raw"],
                     help="--workload demod: the demod.java chain (8f next-3) with filter, down-conversion and AGC on")
     ap.add_argument("--waterfall-width", type=int, default=0,
@@ -274,6 +277,74 @@ def validate_fir(J, d_iq, d_fir, S, L, taps, decim, scale):
         if got.tobytes() != want.tobytes():
             return False, {"streams_checked": len(idx), "first_bad_stream": st}
     return True, {"streams_checked": len(idx), "outputs_per_stream": no}
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: the most it writes in all
+
+
+def sample_rows(nrows, row_bytes, budget):
+    """which rows of an output to write: all of them when they fit in `budget` bytes, else a fixed, seeded sample (sorted)"""
+    if row_bytes > budget:
+        raise SystemExit(f"--dump-outputs: one row of an output ({row_bytes} B) is larger than its share of {DUMP_BYTES} B")
+    k = min(nrows, budget // row_bytes)
+    if k == nrows:
+        return np.arange(nrows)
+    return np.sort(np.random.default_rng(SEED).choice(nrows, k, replace=False))
+
+
+def dump_device_rows(out_dir, name, buf, nrows, row_elems, dtype, out_dtype, budget):
+    """rows of `row_elems` elements of `dtype` from a device buffer -> out_dir/<name>.npy as out_dtype; a sample of the rows is
+    written with their indices beside it (<name>_rows.npy)"""
+    dtype, out_dtype = np.dtype(dtype), np.dtype(out_dtype)
+    row_bytes = row_elems * dtype.itemsize
+    assert nrows * row_bytes <= buf.nbytes, (name, nrows, row_bytes, buf.nbytes)
+    rows = sample_rows(nrows, row_elems * out_dtype.itemsize + 8, budget)  # (+ its index, if sampled)
+    out = np.empty((len(rows), row_elems), out_dtype)
+    for j, r in enumerate(rows):
+        out[j] = buf.to_host(dtype, row_elems, offset_bytes=int(r) * row_bytes)
+    np.save(os.path.join(out_dir, name + ".npy"), out)
+    if len(rows) < nrows:
+        np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+
+
+def dump_bpsk(J, out_dir, dem, S, budget):
+    """what the demodulator's caller receives after the last call, from the packed result slots (include/jsdr_hip.h):
+    bpsk_header [S, 13] every stream's nbits, nfec, nine counters, overflow and uncertified flags (sampled as dump_device_rows
+    does past half the budget); for a seeded sample of streams (bpsk_streams) the bits of the last call (bpsk_bits), its FEC
+    results (bpsk_fec [k, nfec_max, 2 + 256]: rc, bit index, bytes) and the state doubles (bpsk_state [k, 18]).  Every value
+    is finite: bpsk_sample_info [k, 3] holds how many bits and FEC results of a row are real (the rest is 0) and whether its
+    state was delivered (0: the fast variant's uncertified stream, whose getters fail; its state row is 0)"""
+    info = dem.slot_info()
+    sb, bo, fo, nbits_max, nfec_max = (info[k] for k in ("slot_bytes", "bits_offset", "fec_offset", "slot_bits", "nfec_max"))
+    d_slots = J.DeviceBuffer(S * sb)
+    dem.pack_slots(d_slots)
+    J.binding.stream_sync(None)
+    blob = d_slots.to_host(np.uint8).reshape(S, sb)
+    hdr = np.frombuffer(blob[:, :64].tobytes(), np.int32).reshape(S, 16)
+    rows = sample_rows(S, 14 * 8, budget // 2)
+    np.save(os.path.join(out_dir, "bpsk_header.npy"), hdr[rows, :13].astype(np.float64))
+    if len(rows) < S:
+        np.save(os.path.join(out_dir, "bpsk_header_rows.npy"), rows.astype(np.float64))
+    streams = sample_rows(S, 8 + 24 + 4 * nbits_max + 4 * nfec_max * 258 + 8 * 18, budget - 14 * 8 * len(rows))
+    bits = np.zeros((len(streams), nbits_max), np.float32)
+    fec = np.zeros((len(streams), nfec_max, 258), np.float32)
+    state = np.zeros((len(streams), 18), np.float64)
+    sample_info = np.zeros((len(streams), 3), np.float64)
+    for j, s in enumerate(streams):
+        nb, nt = min(int(hdr[s, 0]), nbits_max), min(int(hdr[s, 1]), nfec_max)
+        sample_info[j] = nb, nt, 1
+        bits[j, :nb] = blob[s, bo:bo + nb].view(np.int8)
+        for t in range(nt):
+            o = fo + t * 264
+            fec[j, t, :2] = np.frombuffer(blob[s, o:o + 8].tobytes(), np.int32)
+            fec[j, t, 2:] = blob[s, o + 8:o + 264]
+        try:
+            state[j] = dem.state(int(s))
+        except J.JsdrError:  # (the fast variant: an uncertified stream's getters fail, include/jsdr_hip.h)
+            sample_info[j, 2] = 0
+    for name, arr in (("bpsk_streams", streams.astype(np.float64)), ("bpsk_sample_info", sample_info), ("bpsk_bits", bits),
+                      ("bpsk_fec", fec), ("bpsk_state", state)):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def usable_cores():
@@ -492,7 +563,10 @@ def live_traffic_table(a, samples_per_launch):
     # the child runs under the PARENT's interpreter (a real ELF binary: the program right after `--` must not be a launcher that
     # re-execs, and a different python3 on PATH may lack this process's packages)
     py = os.path.realpath(sys.executable) if sys.executable else "python3"
-    child = [x for x in sys.argv[1:]] + ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-validate", "--no-compare-serial",
+    argv = sys.argv[1:]
+    child = [x for i, x in enumerate(argv)  # (the child writes no outputs: --dump-outputs is this run's)
+             if not (x.startswith("--dump-outputs") or (i > 0 and argv[i - 1] == "--dump-outputs"))]
+    child += ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-validate", "--no-compare-serial",
                                          "--no-autotune", "--no-live-traffic"]
     tmp = tempfile.mkdtemp(prefix="jsdr_pmc_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp", JSDR_BENCH_CHILD="1")
@@ -545,6 +619,8 @@ def live_traffic_table(a, samples_per_launch):
 def main():
     global RATE
     a = parse()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if a.rate != RATE:
         if a.workload != "bpsk":
             raise SystemExit("--rate needs --workload bpsk (the pipeline line is BASELINE's 96 kHz configuration)")
@@ -807,6 +883,21 @@ def main():
         side_by_side = best
     else:
         dt, snap = timed_region()
+    if a.dump_outputs and rank == 0:
+        # what the last timed step computed, before anything below runs the pipeline again (rank 0's streams)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        outs = [o for o in (fft, d_pix, d_fir, d_audio, dem) if o is not None]
+        share = (DUMP_BYTES - (1 << 16)) // len(outs)  # (64 KiB left for the .npy headers)
+        if fft is not None:
+            dump_device_rows(a.dump_outputs, "psd", d_psd, nframes, N_FFT + 2, np.float32, np.float32, share)
+        if d_pix is not None:
+            dump_device_rows(a.dump_outputs, "waterfall", d_pix, nframes, wf, np.uint32, np.float64, share)
+        if d_fir is not None:
+            dump_device_rows(a.dump_outputs, "fir", d_fir, S, 2 * (L // a.fir_decim), np.float64, np.float64, share)
+        if d_audio is not None:
+            dump_device_rows(a.dump_outputs, "audio", d_audio, S * L // N_FFT, 2 * N_FFT, np.int16, np.float32, share)
+        if dem is not None:
+            dump_bpsk(J, a.dump_outputs, dem, S, share)
     per_rank_ms = None
     if D:
         per_rank = [None] * N

@@ -24,7 +24,7 @@ the correctly rounded value of sin/cos of the double argument, computed in exact
 import math
 import os
 import re
-from fractions import Fraction
+from exact_trig import _sincos_exact
 
 import numpy as np
 
@@ -380,28 +380,6 @@ def FECDecode(raw, RSdecdata):
 
 
 # ------------------------------------------------------------------------------------- sin / cos tables
-def _round_fraction(q):
-    return float(q)  # Fraction -> float is correctly rounded (round-half-even) in CPython
-
-
-def _sincos_exact(x):
-    """correctly rounded (sin x, cos x) of the double x, via Taylor series in exact rationals"""
-    q = Fraction(x)
-    s = Fraction(0)
-    c = Fraction(0)
-    term = Fraction(1)
-    n = 0
-    # |x| <= 2 pi: 80 terms leave a remainder far below 2^-200
-    while n < 80:
-        if n % 2 == 0:
-            c += term if (n // 2) % 2 == 0 else -term
-        else:
-            s += term if (n // 2) % 2 == 0 else -term
-        n += 1
-        term = term * q / n
-    return _round_fraction(s), _round_fraction(c)
-
-
 def sincos_tables(size=256):
     sin_tab, cos_tab = [], []
     for n in range(size):

@@ -135,6 +135,7 @@ def test_bpsk_snapshot_for_a_concurrent_reader():
     lock while the main thread feeds frames; every snapshot must be one whole frame's results (never torn), frames
     must only move forward, and the final one must equal the getters."""
     import threading
+    import time
     import oracle_lib as O
     n = 2048 * 120
     iq, _, _ = O.make_dbpsk_stream(8, 0, n, noise_sigma=700.0)
@@ -142,7 +143,7 @@ def test_bpsk_snapshot_for_a_concurrent_reader():
     d = J.Bpsk(nstreams=1)
     with pytest.raises(J.JsdrError):
         d.snapshot()  # nothing received yet
-    seen, stop, bad = [], threading.Event(), []
+    seen, stop, bad, reads = [], threading.Event(), [], [0]
 
     def reader():
         last = 0
@@ -156,11 +157,18 @@ def test_bpsk_snapshot_for_a_concurrent_reader():
                 bad.append((sn.frames, c[:3]))
             last = sn.frames
             seen.append(sn.frames)
+            reads[0] += 1
 
     t = threading.Thread(target=reader)
     t.start()
     for k in range(120):
         d.receive(buf[k * 4096:(k + 1) * 4096])
+        # a receive() takes ~0.1 ms: left to the GIL's 5 ms switch interval the reader may not run at all while the writer
+        # does.  So the writer waits until the reader has read once since this frame returned; the reader's polling goes
+        # on, unlocked, through the next receive()
+        r, t0 = reads[0], time.monotonic()
+        while reads[0] == r and time.monotonic() - t0 < 1.0:
+            time.sleep(1e-4)
     stop.set()
     t.join()
     assert not bad, bad[:5]

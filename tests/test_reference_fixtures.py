@@ -139,7 +139,7 @@ def test_fft_twiddle_table_is_cos_sin_to_the_last_bit_or_one(fxf):
     the correctly rounded cos / sin of the exact angle 2 pi k / n: equal, or one unit in the last place apart"""
     from fractions import Fraction
 
-    import java_restatement as JR
+    from exact_trig import _sincos_exact
 
     pi = Fraction(314159265358979323846264338327950288419716939937510582097494459230781640628620899, 10 ** 80)
     for n in (1024, 2048, 4096):
@@ -148,7 +148,7 @@ def test_fft_twiddle_table_is_cos_sin_to_the_last_bit_or_one(fxf):
         off = 0
         for kk in range(0, n // 2, 7):  # a seventh of the table keeps the exact arithmetic short
             ang = 2 * pi * kk / n
-            s, c = JR._sincos_exact(ang)
+            s, c = _sincos_exact(ang)
             for got, want in ((w[2 * kk], c), (w[2 * kk + 1], -s)):
                 if got != want:
                     off += 1
