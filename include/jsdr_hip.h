@@ -195,6 +195,27 @@ int jsdr_bpsk_uncertified_streams(jsdr_bpsk *h, int32_t *ids, int cap, int *coun
 int jsdr_bpsk_stream_recovered(jsdr_bpsk *h, int stream, int *recovered); /* 1: served by the exact shadow (replayed) */
 int jsdr_bpsk_recover_uncertified(jsdr_bpsk *h, const int16_t *const *raw_dev_calls, const int64_t *nsamples_calls, int ncalls,
                                   int64_t stream_stride_i16, int ic, int qc, int *recovered, void *stream);
+/* Live control: FUNcubeBPSKDemod.actionPerformed (:165-190) between two calls, applied to every stream of the handle.
+ * Takes effect from the next sample of the next call; nothing else is reset (tuPhase, the down-sampler and matched-filter
+ * histories, vcoPhase, the bit clock and energies, the 5200-bit FEC register and the counters carry on).  Both calls wait
+ * for the handle's own pending work first: the previous call's tail and FEC finish with the settings they started with.
+ *   set_tuning: tuning = tuning_hz; tuPhaseInc = 2 pi tuning / rate; dmMaxCorr = 0.  Any finite value: tuning <= 0 follows
+ *     :388-396 (samples pass through unmixed once tuPhase <= 0; tuning == 0 freezes tuPhase).
+ *   set_mode: doFFT = do_fft, doUp = do_up; tuPhaseInc recomputed; dmMaxCorr = 0.  A switch between the tune and the
+ *     FFT-acquire front end keeps the down-sampler history across it exactly (the first call after it carries the seam; calls
+ *     in FFT-acquire mode must be whole frames, and the first tune call after FFT-acquire frames at least 26 samples).  The
+ *     FFT-acquire buffers of a handle created in the tune mode are allocated, zeroed, at its first switch.
+ *   Calling either with the current values still zeroes dmMaxCorr, as the Java does.
+ * JSDR_ERR, with the handle exactly as it was, for a null handle, a non-finite tuning, set_mode(do_fft = 1) on a frame size
+ * FFT-acquire mode cannot take or when its buffers cannot be allocated (jsdr_last_error says which), and on a
+ * JSDR_VARIANT_FAST handle (jsdr_bpsk_recover_uncertified replays from creation and would replay the wrong tuning; a
+ * handle that has been retuned cannot become FAST either).  get_control: the values now in effect. */
+int jsdr_bpsk_set_tuning(jsdr_bpsk *h, double tuning_hz);
+int jsdr_bpsk_set_mode(jsdr_bpsk *h, int do_fft, int do_up);
+int jsdr_bpsk_get_control(jsdr_bpsk *h, double *tuning_hz, int *do_fft, int *do_up);
+/* FUNcubeBPSKDemod.setup (:192-209) on an unchanged AudioDescriptor: tuning, doFFT, doUp and tuPhaseInc from the
+ * configuration, dmMaxCorr left as it is (setup resets no DSP state); otherwise as set_tuning + set_mode */
+int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up);
 /* receive(float[]) / raw form for stream 0 of a 1-stream handle (:357-364) */
 int jsdr_bpsk_receive_f32(jsdr_bpsk *h, const float *iq_host);
 int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc);
@@ -373,6 +394,10 @@ int jsdr_group_batch_i16(jsdr_group *g, const int16_t *const *raw_dev, int64_t s
 int jsdr_group_sync(jsdr_group *g);
 int jsdr_group_gathered(jsdr_group *g, int index, const uint8_t **slots_dev, int64_t *bytes);
 int jsdr_group_read_slot(jsdr_group *g, int index, int stream, uint8_t *slot_host);
+/* jsdr_bpsk_set_tuning / jsdr_bpsk_set_mode on every member, after the group's pending steps; every member is checked
+ * before any is changed */
+int jsdr_group_set_tuning(jsdr_group *g, double tuning_hz);
+int jsdr_group_set_mode(jsdr_group *g, int do_fft, int do_up);
 
 #ifdef __cplusplus
 }

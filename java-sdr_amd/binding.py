@@ -520,6 +520,23 @@ class Bpsk:
     def sync(self):
         _check(lib().jsdr_bpsk_sync(self.h), "jsdr_bpsk_sync")
 
+    # live control, FUNcubeBPSKDemod.actionPerformed (:165-190): between calls, every stream, nothing else reset
+    def set_tuning(self, tuning_hz):
+        _check(lib().jsdr_bpsk_set_tuning(self.h, C.c_double(tuning_hz)), "jsdr_bpsk_set_tuning")
+
+    def set_mode(self, do_fft, do_up):
+        _check(lib().jsdr_bpsk_set_mode(self.h, int(do_fft), int(do_up)), "jsdr_bpsk_set_mode")
+
+    def reconfigure(self, tuning_hz, do_fft, do_up):
+        """setup() (:192-209) on an unchanged format: the configuration's values, dmMaxCorr kept"""
+        _check(lib().jsdr_bpsk_reconfigure(self.h, C.c_double(tuning_hz), int(do_fft), int(do_up)), "jsdr_bpsk_reconfigure")
+
+    def control(self):
+        """(tuning_hz, do_fft, do_up) now in effect"""
+        t, f, u = C.c_double(), C.c_int(), C.c_int()
+        _check(lib().jsdr_bpsk_get_control(self.h, C.byref(t), C.byref(f), C.byref(u)), "jsdr_bpsk_get_control")
+        return t.value, f.value, u.value
+
     def counters(self, stream=0):
         out = np.empty(10, np.int32)
         _check(lib().jsdr_bpsk_get_counters(self.h, stream, _addr(out)), "jsdr_bpsk_get_counters")
@@ -626,6 +643,12 @@ class Group:
 
     def sync(self):
         _check(lib().jsdr_group_sync(self.h), "jsdr_group_sync")
+
+    def set_tuning(self, tuning_hz):
+        _check(lib().jsdr_group_set_tuning(self.h, C.c_double(tuning_hz)), "jsdr_group_set_tuning")
+
+    def set_mode(self, do_fft, do_up):
+        _check(lib().jsdr_group_set_mode(self.h, int(do_fft), int(do_up)), "jsdr_group_set_mode")
 
     def read_slot(self, index, stream):
         out = np.empty(self.slot_bytes, np.uint8)

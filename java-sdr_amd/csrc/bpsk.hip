@@ -23,6 +23,7 @@
 #include "bpsk_fec.h"
 #include "bpsk_fft.h"
 #include <math.h>
+#include <cmath>
 #include <atomic>
 #include <thread>
 #include <stddef.h>
@@ -370,6 +371,119 @@ __global__ __launch_bounds__(256) void k_front_any(FrontArgs a, int D)
         const int kv = a.kvco[j];
         a.dm[(long long)s * a.dm_stride + 64 + j] = make_double2(oi * sc[kv], oq * sc[256 + kv]);  // :515-516
     }
+}
+
+// ------------------------------------------------------------------------------------------- k_front_split
+// The front end of a call whose samples are not all on one side of the tuner's sign test (:388): after a retune
+// (jsdr_bpsk_set_tuning) tuPhase may walk through 0 inside a call, or the 26 history samples may have been taken on the
+// other side.  k_front_any's loop, one thread per output, with a 9-bit tuner index per sample: entries 0..255 are the
+// reference's tables, entry 256 is (1.0, 1.0), which passes the sample through exactly (i * 1.0 == i): RxDownSample(i, q)
+// of :395.  sc9 = cos[0..256] then sin[0..256].  dh (the first tune call after FFT-acquire frames): the history is the FFT
+// path's doubles (I == Q, unmixed) instead of raw samples.  Runs only for calls right after an action, never in the steady state.
+template <bool F32IN>
+__global__ __launch_bounds__(256) void k_front_split(FrontArgs a, const unsigned short *ktu9, const double *sc9, int D,
+                                                     const FftFrontState *dh)
+{
+    __shared__ double sc[514];
+    for (int i = threadIdx.x; i < 514; i += blockDim.x) sc[i] = sc9[i];
+    __syncthreads();
+    const int s = blockIdx.y;
+    const double HOWARD = 0.9 * 32768.0;  // :469
+    const int *raw = a.raw + (long long)s * a.stride_pairs;
+    const float2 *rawf = a.rawf + (long long)s * a.stride_pairs;
+    const int2 *hist = a.hist + (long long)s * 32;
+    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < a.nds; j += (long long)gridDim.x * blockDim.x) {
+        const long long n_new = (long long)a.first_out + (long long)D * j;
+        double fi = 0.0, fq = 0.0;
+        for (int age = 0; age < DS_N; age++) {
+            const long long n = n_new - age;  // >= -26
+            double di, dq;
+            if (n < 0 && dh) {  // the first tune call after FFT-acquire frames: dsBuf holds their re values (I == Q, :464)
+                di = dh[s].hist[26 + n];
+                dq = di;
+            } else if constexpr (F32IN) {
+                float2 f;
+                if (n >= 0) {
+                    f = rawf[n];
+                } else {
+                    const int2 h = hist[26 + n];
+                    f = make_float2(__int_as_float(h.x), __int_as_float(h.y));
+                }
+                di = (double)f.x;
+                dq = (double)f.y;
+            } else {
+                int w;
+                if (n >= 0) {
+                    w = raw[n];
+                    const int si = java_short_add((int)(short)(w & 0xffff), a.ic);
+                    const int sq = java_short_add(w >> 16, a.qc);
+                    w = (si & 0xffff) | (sq << 16);
+                } else {
+                    w = hist[26 + n].x;
+                }
+                di = (double)i16_to_float_java((int)(short)(w & 0xffff));
+                dq = (double)i16_to_float_java(w >> 16);
+            }
+            const int k = ktu9[26 + n];
+            di = di * sc[k];
+            dq = dq * sc[257 + k];
+            const double tp = c_bpsk.ds_taps[age];
+            fi += di * tp;
+            fq += dq * tp;
+        }
+        const double oi = fi * HOWARD, oq = fq * HOWARD;  // :486
+        const int kv = a.kvco[j];
+        a.dm[(long long)s * a.dm_stride + 64 + j] = make_double2(oi * sc[kv], oq * sc[257 + kv]);  // :515-516
+    }
+}
+
+// jsdr_bpsk_set_mode, tune -> FFT-acquire: the tune path's dsBuf as two columns of doubles, mixed exactly as k_front mixes
+// them (or passed through, :395) -- I into the FFT state's history, Q into a copy of the FFT state for the second run
+struct SeamHist {
+    unsigned char khist[26];  // tuner table index of the 26 samples before the call
+    unsigned char mhist[26];  // 1: mixed, 0: passed through
+};
+__global__ __launch_bounds__(32) void k_seam_hist(const int2 *hist, int is_float, const double *sincos, SeamHist sh, FftFrontState *st,
+                                                  FftFrontState *st2)
+{
+    const int s = blockIdx.x, t = threadIdx.x;
+    if (t < 26) {
+        const int2 hv = hist[(long long)s * 32 + t];
+        double di, dq;
+        if (is_float) {
+            di = (double)__int_as_float(hv.x);
+            dq = (double)__int_as_float(hv.y);
+        } else {
+            di = (double)i16_to_float_java((int)(short)(hv.x & 0xffff));
+            dq = (double)i16_to_float_java(hv.x >> 16);
+        }
+        if (sh.mhist[t]) {
+            const int k = sh.khist[t];
+            di = di * sincos[k];
+            dq = dq * sincos[256 + k];
+        }
+        st[s].hist[t] = di;
+        st2[s].hist[t] = dq;
+    }
+    if (t == 0) {
+        st2[s].avePeakPower = st[s].avePeakPower;
+        st2[s].aveCentreBin = st[s].aveCentreBin;
+        st2[s].centreBin = st[s].centreBin;
+    }
+}
+
+// ... and the Q rail of the outputs whose windows reach into that history, from the second run's row
+__global__ __launch_bounds__(64) void k_seam_q(double2 *dm, long long dm_stride, const double2 *dm2, long long dm2_stride, int J)
+{
+    const int s = blockIdx.x, j = threadIdx.x;
+    if (j < J) dm[(long long)s * dm_stride + 64 + j].y = dm2[(long long)s * dm2_stride + 64 + j].y;
+}
+
+// jsdr_bpsk_set_tuning / _set_mode: dmMaxCorr = 0 (:189) in every stream
+__global__ void k_reset_maxcorr(TailState *st, int nstreams)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < nstreams) st[s].dmMaxCorr = 0;
 }
 
 // lane-span geometry of the register-staged front end: a lane owns RD samples = R outputs, its window NS samples
@@ -2341,6 +2455,8 @@ struct Schedule {
     unsigned char khist0[26] = {0};
     double tu1 = 0, vco1 = 0;  // state at its end
     int ds1 = 0, mix = 1, tper = 0;
+    int f0 = 1;                // sample 0 of the call is mixed (tuPhase > 0) ...
+    long long n0 = 0;          // ... and so is every sample before n0, none from it on (n0 = L: no crossing)
     long long nds = 0;
     std::vector<unsigned char> ktu, kvco;
     std::vector<double2> tcs;
@@ -2357,7 +2473,8 @@ struct SnapPack {
 
 struct SideJob;
 struct jsdr_bpsk {
-    int rate = 0, nsf = 0, tuning = 0, do_fft = 0, do_up = 0, nstreams = 0, decim = 0;
+    double tuning = 0.0;  // FUNcubeBPSKDemod.tuning (a double: freqDialog may give what +-10 never reaches)
+    int rate = 0, nsf = 0, do_fft = 0, do_up = 0, nstreams = 0, decim = 0;
     long long max_batch = 0, max_ds = 0;
     int max_bits = 0;
     int trig_cap = MIN_TRIG;  // FECDecode calls (sync hits) one stream can log per call; sized from max_bits at create
@@ -2374,6 +2491,21 @@ struct jsdr_bpsk {
     unsigned char h_khist[26] = {0};   // tuner indices of the 26 samples before the next call
     unsigned char c_khist[26] = {0};
     int mix = 1, c_mix = 1;
+    // live control (jsdr_bpsk_set_tuning): which side of the sign test (:388) each sample fell on
+    int c_f0 = 1;
+    long long c_n0 = 0;
+    bool retuned = false;
+    // live mode switches (jsdr_bpsk_set_mode): the FFT-acquire buffers exist (at create, or from the first switch on), the
+    // first call after a switch still to come, and the second run's scratch of a tune -> FFT switch
+    bool fft_ready = false;
+    int seam = 0;
+    DevBuf<FftFrontState> fft_state2;
+    DevBuf<double2> dm2;
+    long long dm2_stride = 0;              // a live-control call has run (the fast variant's replay from creation would not see it)
+    unsigned char h_mhist[26] = {0};   // 1: the 26 samples before the next call were mixed, 0: passed through
+    DevBuf<unsigned short> ktu9;       // k_front_split: [26 + L] 9-bit tuner index (256: pass-through)
+    DevBuf<double> sincos9;            // cos[0..256], sin[0..256] with (1.0, 1.0) at 256
+    std::vector<unsigned short> h_ktu9;
     int c_kshift = -1;
     std::vector<unsigned char> h_kvco;
     // device
@@ -2552,6 +2684,7 @@ static void acq_prof_mark(void *ctx, int phase, bool begin, hipStream_t st)
 }
 
 static const double JPI = 3.14159265358979323846;
+enum { SEAM_NONE = 0, SEAM_TO_FFT = 1, SEAM_TO_TUNE = 2 };
 
 // FUNcubeBPSKDemod.java:384-390 / :511-516 -- advance the phase accumulators exactly as the reference does and record
 // the table index each sample will use.  Input independent: a function of the phase state at the start of the call,
@@ -2594,6 +2727,23 @@ static void compute_schedule(Schedule &sc, bool do_fft, double tuPhaseInc, int d
     }
     // tuPhase > 0 holds for every sample (tuning > 0) or for none (tuning <= 0): one flag per call
     sc.mix = (nmix == L) ? 1 : (nmix == 0 ? 0 : -1);
+    sc.f0 = sc.mix == 0 ? 0 : 1;
+    sc.n0 = L;
+    if (sc.mix < 0) {
+        // tuPhase crossed 0 inside the call (a retune, jsdr_bpsk_set_tuning): once <= 0 it is monotone, so there is exactly
+        // one crossing.  Stepped again the same way to find it (calls after a retune only).
+        double t = sc.tu0;
+        for (long long n = 0; n < L; n++) {
+            t += tuPhaseInc;
+            if (t > two_pi) t -= two_pi;
+            const int m = t > 0.0 ? 1 : 0;
+            if (n == 0) sc.f0 = m;
+            else if (m != sc.f0) {
+                sc.n0 = n;
+                break;
+            }
+        }
+    }
     sc.tu1 = tu;
     sc.vco1 = vco;
     sc.ds1 = cnt;
@@ -2674,6 +2824,8 @@ static long long build_schedule(jsdr_bpsk *h, long long L)
     if (pf.tper > 0) h->h_tcs.swap(pf.tcs);
     h->c_tper = pf.tper;
     h->mix = h->c_mix = pf.mix;
+    h->c_f0 = pf.f0;
+    h->c_n0 = pf.n0;
     h->tuPhase = h->c_tu1 = pf.tu1;
     h->vcoPhase = h->c_vco1 = pf.vco1;
     h->dsCnt = h->c_ds1 = pf.ds1;
@@ -3074,14 +3226,28 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
                  "bpsk: stream stride %lld too small for %lld samples", stride_i16, L);
     JSDR_REQUIRE(!h->do_fft || (L % h->nsf) == 0, "bpsk: FFT-acquire mode needs whole frames (%lld %% %d != 0)", L, h->nsf);
     JSDR_REQUIRE(h->variant == 0 || raw_dev, "bpsk: the fast variant takes int16 input (its certification pass re-reads the raw samples)");
+    JSDR_REQUIRE(h->seam != SEAM_TO_TUNE || L >= 26, "bpsk: the first tune-mode call after FFT-acquire frames needs at least 26 samples "
+                 "(the input history is rebuilt from them)");
     const int first_out = h->decim - 1 - h->dsCnt;
     const long long g_first = h->n_ds;
+    unsigned char kh0[26], mh0[26];  // the tuner indices / mix flags of the 26 samples before the call (build_schedule moves them on)
+    memcpy(kh0, h->h_khist, 26);
+    memcpy(mh0, h->h_mhist, 26);
     const long long nds = build_schedule(h, L);
     JSDR_REQUIRE(nds <= h->max_ds, "bpsk: internal: %lld decimated samples exceed capacity %lld", nds, h->max_ds);
-    JSDR_REQUIRE(h->do_fft || h->mix >= 0, "bpsk: tuner phase changes sign inside a call (unsupported)");
+    // after a retune the call's samples, or the 26 history samples its first windows reach into, may lie on both sides of
+    // the tuner's sign test (:388): those calls take k_front_split (in the steady state every flag is the call's own)
+    const int f0 = h->c_f0;  // (both paths of build_schedule leave the call's in c_f0 / c_n0)
+    const long long n0 = h->c_n0;
+    if (h->n_in == 0) memset(h->h_mhist, f0, 26);  // (the history of a stream's first call is zeros: either side is exact)
+    bool split = false;
+    if (!h->do_fft) {
+        split = h->mix < 0 || h->seam == SEAM_TO_TUNE;
+        for (int i = 0; i < 26 && !split; i++) split = h->h_mhist[i] != (unsigned char)f0;
+    }
     if (!h->do_fft) {
         const bool want_float = rawf_dev != nullptr;
-        if (h->n_in > 0 && want_float != h->hist_is_float) {  // the previous call came through the other input form
+        if (h->n_in > 0 && want_float != h->hist_is_float && h->seam != SEAM_TO_TUNE) {  // the previous call came through the other input form
             JSDR_HIP_TRY(hipMemsetAsync(h->hist_bad.p, 0, sizeof(int), st));
             hipLaunchKernelGGL(k_hist_convert, dim3((unsigned)((h->nstreams * 32 + 255) / 256)), dim3(256), 0, st,
                                h->hist_in[h->hist_cur].p, h->nstreams, want_float ? 1 : 0, h->hist_bad.p);
@@ -3100,8 +3266,8 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     // no tuner at all), 32-bit sample indices
     const bool std_decim = h->decim == 4 || h->decim == 5 || h->decim == 10 || h->decim == 20;  // the specialised front ends
     const int fm_rd = h->decim == 4 ? 20 : h->decim * 4;  // D * R of the k_fm instantiation
-    const bool per_ok = !h->do_fft && h->mix == 1 && h->c_tper > 0 && fm_rd % h->c_tper == 0;
-    const bool fm_ok = h->use_fm && std_decim && !h->do_fft && raw_dev && !rawf_dev && nds > 0 && L <= 0x3fffffffLL &&
+    const bool per_ok = !h->do_fft && !split && h->mix == 1 && h->c_tper > 0 && fm_rd % h->c_tper == 0;
+    const bool fm_ok = h->use_fm && std_decim && !h->do_fft && !split && raw_dev && !rawf_dev && nds > 0 && L <= 0x3fffffffLL &&
                        (h->mix == 0 || per_ok);
     const int kshift = 0;
     const bool fresh = !h->cache_valid;
@@ -3120,7 +3286,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     double2 *tcs_p = h->tcs.p + (size_t)h->tab_cur * (256 + FM_TABLE_SLACK);
     // the 1 B/sample index table is only read by the kernels without the periodic table (k_front, k_front_reg<PER = false>)
     const bool reg_will_run = front_reg_enabled() && std_decim && raw_dev && !rawf_dev && L <= 0x3fffffffLL && L >= 64;
-    const bool need_ktu = !h->do_fft && !fm_ok && !(per_ok && reg_will_run) && h->mix != 0;
+    const bool need_ktu = !h->do_fft && !split && !fm_ok && !(per_ok && reg_will_run) && h->mix != 0;
     if (need_ktu && (!h->ktu_uploaded || kshift != h->c_kshift)) {
         h->c_kshift = kshift;
         if (h2d_call(h, h->ktu.p + kshift, h->h_ktu.data(), (size_t)L + 26, st) != JSDR_OK) return JSDR_ERR;
@@ -3188,6 +3354,28 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         // synchronously, so they are safe to reuse on return
         h->cache_valid = true;
     }
+    if (split && nds > 0) {
+        // k_front_split's index table: the schedule's index where the sample was mixed, 256 (pass-through) where not
+        if (!h->ktu9.p && h->ktu9.alloc((size_t)h->max_batch + 26) != JSDR_OK) return JSDR_ERR;
+        if (!h->sincos9.p) {
+            std::vector<double> t(514);
+            for (int k = 0; k < 256; k++) {
+                t[(size_t)k] = h->h_sincos[(size_t)k];
+                t[(size_t)(257 + k)] = h->h_sincos[(size_t)(256 + k)];
+            }
+            t[256] = 1.0;
+            t[513] = 1.0;
+            if (h->sincos9.alloc(514) != JSDR_OK) return JSDR_ERR;
+            JSDR_HIP_TRY(hipMemcpy(h->sincos9.p, t.data(), sizeof(double) * 514, hipMemcpyHostToDevice));
+        }
+        h->h_ktu9.resize((size_t)L + 26);
+        for (int i = 0; i < 26; i++) h->h_ktu9[(size_t)i] = (h->h_mhist[i] && h->seam != SEAM_TO_TUNE) ? h->h_ktu[(size_t)i] : 256;
+        for (long long n = 0; n < L; n++) {
+            const int m = (n < n0) ? f0 : !f0;
+            h->h_ktu9[(size_t)(26 + n)] = m ? h->h_ktu[(size_t)(26 + n)] : 256;
+        }
+        if (h2d_call(h, h->ktu9.p, h->h_ktu9.data(), sizeof(unsigned short) * ((size_t)L + 26), st) != JSDR_OK) return JSDR_ERR;
+    }
     // the 64-sample halo of VCO-mixed samples lives where the previous call's path left it
     if (nds > 0 && !h->do_fft && fm_ok != h->halo_in_dmh) {
         if (fm_ok)
@@ -3219,6 +3407,11 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     fa.tcs = per_ok ? tcs_p : nullptr;
     fa.tper = h->c_tper;
     bool hist_done = false;  // the next call's input history has been written (k_fm_prep does it in the k_fm path)
+    if (h->do_fft && nds > 0 && h->halo_in_dmh) {  // (the last tune call left the matched filter's halo in dmh)
+        JSDR_HIP_TRY(hipMemcpy2DAsync(h->dm.p, (size_t)h->dm_stride * sizeof(double2), h->dmh[h->dmh_cur].p, 64 * sizeof(double2),
+                                      64 * sizeof(double2), (size_t)h->nstreams, hipMemcpyDeviceToDevice, st));
+        h->halo_in_dmh = false;
+    }
     if (h->do_fft) {
         FftFrontArgs xa;
         xa.raw = fa.raw;
@@ -3241,6 +3434,8 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         xa.nds = nds;
         xa.ds_taps = h->ds_taps_dev.p;
         xa.phase_clk = h->phase_clk.p;
+        // the front end over the frames of xa (a lambda: the first call after a switch from the tune mode runs it twice)
+        auto fft_front = [&](FftFrontArgs &xa) -> int {
         // round 6: frames of 2^k samples, two or more per stream in the call: three phases over FRAMES (bpsk_acq.hip); a call of
         // one frame per stream (a live receive()) keeps the fused kernel -- one launch instead of four
         // The 2^k frames' three-phase kernels are the faster ones per frame as well (n = 2048, 1024 x 2^20: 8.65 against 9.1 ms);
@@ -3300,6 +3495,56 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
                                   : (h->fft_mixed ? launch_front_fftm(xa, h->fm_np, h->fm_rad, h->fm_off, h->fm_off1, h->fft2x_ek.p, S, st) : launch_front_fft(xa, S, st));
         if (frc != JSDR_OK) return JSDR_ERR;
         }
+            return JSDR_OK;
+        };
+        if (h->seam == SEAM_TO_FFT) {
+            // the first FFT-acquire call after jsdr_bpsk_set_mode switched from the tune mode.  dsBuf holds distinct I and Q
+            // columns (tuner-mixed samples), the FFT front ends assume I == Q (:464 RxDownSample(re, re)); only the outputs
+            // whose 27-tap windows reach back into that history differ.  The call runs with the I column as its history
+            // (every output's fi is exact), then its first frame runs again from a copy of the FFT state with the Q column
+            // into a scratch row (fq of those outputs is exact: the front end sums one rail, o = fi HOWARD, dm = (o cos, o sin)),
+            // and k_seam_q takes the Q rail of those outputs from it.  Once per switch.
+            SeamHist sh;
+            memcpy(sh.khist, kh0, 26);
+            memcpy(sh.mhist, mh0, 26);
+            hipLaunchKernelGGL(k_seam_hist, dim3((unsigned)S), dim3(32), 0, st, h->hist_in[h->hist_cur].p, h->hist_is_float ? 1 : 0,
+                               h->sincos.p, sh, h->fft_state.p, h->fft_state2.p);
+            JSDR_LAUNCH_CHECK();
+        }
+        if (fft_front(xa) != JSDR_OK) return JSDR_ERR;
+        if (h->seam == SEAM_TO_FFT) {
+            const int D = h->decim;
+            const long long nds1 = first_out < h->nsf ? (long long)((h->nsf - 1 - first_out) / D + 1) : 0;  // outputs of frame 0
+            long long J = first_out <= 25 ? (long long)((25 - first_out) / D + 1) : 0;  // outputs whose windows reach back
+            if (J > nds1) J = nds1;
+            if (J > nds) J = nds;
+            if (J > 0) {
+                const char *keep = h->front_name;
+                FftFrontArgs x1 = xa;
+                x1.nframes = 1;
+                x1.st = h->fft_state2.p;
+                x1.dm = h->dm2.p;
+                x1.dm_stride = h->dm2_stride;
+                x1.nds = nds1;
+                x1.phase_clk = nullptr;
+                if (fft_front(x1) != JSDR_OK) return JSDR_ERR;
+                h->front_name = keep;
+                hipLaunchKernelGGL(k_seam_q, dim3((unsigned)S), dim3(64), 0, st, h->dm.p, h->dm_stride, h->dm2.p, h->dm2_stride, (int)J);
+                JSDR_LAUNCH_CHECK();
+            }
+            h->seam = SEAM_NONE;
+        }
+    } else if (nds > 0 && split) {
+        ProfScope ps(h, PK_FRONT, st);
+        h->front_name = "k_front_split";
+        const FftFrontState *dh = h->seam == SEAM_TO_TUNE ? h->fft_state.p : nullptr;  // FFT -> tune: the history is doubles
+        long long gx = (nds + 255) / 256;
+        if (gx > 4096) gx = 4096;
+        if (fa.rawf)
+            hipLaunchKernelGGL(k_front_split<true>, dim3((unsigned)gx, (unsigned)S), dim3(256), 0, st, fa, h->ktu9.p, h->sincos9.p, h->decim, dh);
+        else
+            hipLaunchKernelGGL(k_front_split<false>, dim3((unsigned)gx, (unsigned)S), dim3(256), 0, st, fa, h->ktu9.p, h->sincos9.p, h->decim, dh);
+        JSDR_LAUNCH_CHECK();
     } else if (nds > 0 && fm_ok) {
         // wait for the tail that last read y[y_cur] (two calls ago) before the fused kernel overwrites it
         if (h->overlap && h->tail_pending[h->y_cur]) {
@@ -3461,6 +3706,19 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         //  every register of every SIMD, a tail wave finds no room until it ends -- and runs beside the first 5 ms of that call's
         //  k_fm: profiles/r04_b_timeline.txt.  Holding it back on the host until the next call's start measured slower.)
         if (run_side(h, job) != JSDR_OK) return JSDR_ERR;
+    }
+    if (!h->do_fft && h->seam == SEAM_TO_TUNE) {
+        h->seam = SEAM_NONE;
+        h->hist_is_float = rawf_dev != nullptr;
+    }
+    if (!h->do_fft) {
+        // the mix flags of the 26 samples before the next call
+        unsigned char nh[26];
+        for (int i = 0; i < 26; i++) {
+            const long long n = L - 26 + i;
+            nh[i] = n < 0 ? h->h_mhist[L + i] : (unsigned char)((n < n0) ? f0 : !f0);
+        }
+        memcpy(h->h_mhist, nh, 26);
     }
     h->last_y = yb;
     h->n_in += L;
@@ -3632,6 +3890,7 @@ int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuni
             jsdr_bpsk_destroy(h);
             return JSDR_ERR;
         }
+        h->fft_ready = true;
         if (const char *e = knob("JSDR_ACQ3")) h->acq_mode = atoi(e) != 0 ? 1 : 0;
         if (const char *e = knob("JSDR_FFT_PHASECLK"))
             if (atoi(e) != 0 && (h->phase_clk.alloc(16 + 2 * 4096) != JSDR_OK || h->phase_clk.zero() != JSDR_OK)) h->phase_clk.release();
@@ -3747,6 +4006,10 @@ int jsdr_bpsk_destroy(jsdr_bpsk *h)
     h->shadow_in.release();
     h->shadow_slots.release();
     h->vco_cs.release();
+    h->ktu9.release();
+    h->sincos9.release();
+    h->fft_state2.release();
+    h->dm2.release();
 #ifdef JSDR_X_T8CLK
     {
         unsigned long long cc[8] = {0};
@@ -3895,7 +4158,7 @@ int jsdr_bpsk_recover_uncertified(jsdr_bpsk *h, const int16_t *const *raw_dev_ca
         }
     if (fresh == 0) return JSDR_OK;  // nothing new to recover (the shadow, if any, is up to date)
     jsdr_bpsk *sh = nullptr;
-    if (jsdr_bpsk_create(&sh, h->rate, h->nsf, h->tuning, 0, h->do_up, (int)ids.size(), h->max_batch) != JSDR_OK) return JSDR_ERR;
+    if (jsdr_bpsk_create(&sh, h->rate, h->nsf, (int)h->tuning, 0, h->do_up, (int)ids.size(), h->max_batch) != JSDR_OK) return JSDR_ERR;
     if (h->shadow) (void)jsdr_bpsk_destroy(h->shadow);
     h->shadow = nullptr;
     h->shadow_ids = ids;
@@ -4403,7 +4666,170 @@ int jsdr_bpsk_set_variant(jsdr_bpsk *h, int variant)
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || variant == JSDR_VARIANT_FAST, "jsdr_bpsk_set_variant: unknown variant %d", variant);
     JSDR_REQUIRE(h->n_in == 0, "jsdr_bpsk_set_variant: the variant is fixed once samples have been received");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->do_fft, "jsdr_bpsk_set_variant: the fast variant covers the tune mode only");
+    JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->retuned, "jsdr_bpsk_set_variant: the fast variant has no live control, and this handle was retuned");
     h->variant = variant;
+    return JSDR_OK;
+}
+
+// ------------------------------------------------------------------------------------------- live control
+// FUNcubeBPSKDemod.actionPerformed (:177-190) between two calls.  Every check comes first: a refused call leaves the handle
+// exactly as it was.  Then the handle's own work is waited for (the previous call's tail and FEC on the side stream finish
+// with the settings they were launched with), the schedule prefetch is joined and both schedule caches are dropped (their
+// key does not hold tuPhaseInc), and dmMaxCorr is zeroed in every stream.  tuPhase, the down-sampler and matched-filter
+// histories, vcoPhase, the tail state, the FEC register and the counters carry on.
+}  // extern "C"
+
+int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who)
+{
+    JSDR_REQUIRE(h, "%s: null handle", who);
+    JSDR_REQUIRE(h->variant == JSDR_VARIANT_EXACT,
+                 "%s: the fast variant has no live control (jsdr_bpsk_recover_uncertified replays from creation)", who);
+    if (do_fft > 0 && !h->do_fft) {
+        // the frame rule of jsdr_bpsk_create's FFT-acquire mode
+        const int n = h->nsf;
+        const bool pow2 = n >= 1024 && n <= 8192 && (n & (n - 1)) == 0;
+        const bool lds = fftm_supported(n) || (h->decim >= 4 && (pow2 || fft2x_supported(n)));
+        JSDR_REQUIRE(lds || acqg_supported(n), "%s: FFT-acquire mode cannot take this handle's frame size (%d samples: it needs 416 .. "
+                     "4194304 samples whose prime factors r above 7 keep n r within 2^31); the handle is unchanged", who, n);
+    }
+    return JSDR_OK;
+}
+
+// the FFT-acquire buffers of a handle created in the tune mode, allocated and zeroed at its first switch (as jsdr_bpsk_create
+// sets them up for do_fft, and Java's field initialisers, :403-405), and the scratch of the tune -> FFT seam.  All or nothing.
+static int fft_mode_alloc(jsdr_bpsk *h)
+{
+    const int n = h->nsf;
+    const size_t S = (size_t)h->nstreams;
+    const long long stride2 = 64 + n / h->decim + 2 + 64;
+    if (h->fft_ready && h->fft_state2.p && h->dm2.p) return JSDR_OK;
+    const bool pow2 = n >= 1024 && n <= 8192 && (n & (n - 1)) == 0;
+    const bool gen = !(fftm_supported(n) || (h->decim >= 4 && (pow2 || fft2x_supported(n))));
+    const bool f2x = !gen && !pow2 && fft2x_supported(n);
+    DevBuf<FftFrontState> st, st2;
+    DevBuf<double2> tw, vcs, ek, dm2;
+    DevBuf<double> r0;
+    std::vector<double2> w;
+    AcqgPlan plan;
+    int np = 0, rad[12] = {0}, off[12] = {0}, off1[12] = {0};
+    bool ok = st2.alloc(S) == JSDR_OK && dm2.alloc(S * (size_t)stride2) == JSDR_OK && st2.zero() == JSDR_OK && dm2.zero() == JSDR_OK;
+    if (ok && !h->fft_ready) {
+        ok = st.alloc(S) == JSDR_OK && vcs.alloc((size_t)h->max_ds) == JSDR_OK &&
+             tw.alloc(gen ? 3 * (size_t)n + 64 : pow2 ? (size_t)n : (size_t)65536) == JSDR_OK &&
+             (!f2x || (ek.alloc(S * fft2x_scratch_ek(n)) == JSDR_OK && r0.alloc(S * fft2x_scratch_r0(n)) == JSDR_OK)) &&
+             (!(!gen && !pow2 && !f2x && fftm_supported(n) && fftm_scratch(n) > 0) || ek.alloc(S * fftm_scratch(n)) == JSDR_OK);
+        if (ok) {
+            if (gen) acqg_twiddles(w, n, &plan);
+            else if (pow2) fft_twiddles_f64(w, n);
+            else if (f2x) fft2x_twiddles(w, n, &np, rad, off, off1);
+            else fftm_twiddles(w, n, &np, rad, off, off1);
+            ok = w.size() <= tw.n && hipMemcpy(tw.p, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice) == hipSuccess &&
+                 st.zero() == JSDR_OK;
+        }
+    }
+    if (ok) ok = hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        st.release();
+        st2.release();
+        tw.release();
+        vcs.release();
+        ek.release();
+        dm2.release();
+        r0.release();
+        set_error("jsdr_bpsk_set_mode: could not allocate the FFT-acquire buffers (%zu streams of %d-sample frames); the handle is unchanged",
+                  S, n);
+        return JSDR_ERR;
+    }
+    std::swap(h->fft_state2, st2);
+    std::swap(h->dm2, dm2);
+    h->dm2_stride = stride2;
+    if (!h->fft_ready) {
+        std::swap(h->fft_state, st);
+        std::swap(h->vco_cs, vcs);
+        std::swap(h->fft_tw, tw);
+        std::swap(h->fft2x_ek, ek);
+        std::swap(h->fft2x_r0, r0);
+        h->fft_mixed = !pow2 && !gen;
+        h->fft_2x = f2x;
+        h->gen_plan = plan;
+        h->fm_np = np;
+        memcpy(h->fm_rad, rad, sizeof(rad));
+        memcpy(h->fm_off, off, sizeof(off));
+        memcpy(h->fm_off1, off1, sizeof(off1));
+        h->fft_ready = true;
+    }
+    return JSDR_OK;
+}
+
+static int live_apply(jsdr_bpsk *h, double tuning, int do_fft, int do_up, bool zero_maxcorr)
+{
+    if (sync_last(h) != JSDR_OK) return JSDR_ERR;
+    if (h->worker.joinable()) h->worker.join();
+    hipStream_t st = h->last_stream;
+    // the one step that can fail comes first: nothing of the handle has changed when it does
+    if (zero_maxcorr) {
+        hipLaunchKernelGGL(k_reset_maxcorr, dim3((unsigned)((h->nstreams + 255) / 256)), dim3(256), 0, st, h->tail.p, h->nstreams);  // :190
+        JSDR_LAUNCH_CHECK();
+        JSDR_HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (h->do_fft && (do_up != h->do_up || !do_fft) && h->acq_scratch.p) {
+        // the three-phase scratch holds a frame's spectrum band, whose width depends on doUp: re-cut it into frames of the
+        // new size, or drop it to be allocated again at the next call that needs it
+        const size_t per = acq3_frame_bytes(h->nsf, do_up) + 64 + (h->gen_plan.on ? acqg_image_bytes(h->nsf) : 0);
+        const long long chunk = (long long)((h->acq_scratch.n - 512) / (per * (size_t)h->nstreams));
+        if (chunk >= 1) {
+            h->acq_chunk = (int)(chunk < h->acq_chunk ? chunk : h->acq_chunk);
+        } else {
+            h->acq_scratch.release();
+            h->acq_chunk = 0;
+        }
+    }
+    if (do_fft != h->do_fft) {
+        // the first call in the new mode carries the seam; a switch back before any call cancels it
+        const int want = do_fft ? SEAM_TO_FFT : SEAM_TO_TUNE;
+        h->seam = h->seam != SEAM_NONE ? SEAM_NONE : want;
+        h->do_fft = do_fft;
+    }
+    h->tuning = tuning;
+    h->do_up = do_up;
+    h->tuPhaseInc = 2.0 * JPI * tuning / (double)h->rate;  // :189
+    h->retuned = true;
+    h->prefetch.valid = false;
+    h->cache_valid = false;
+    return JSDR_OK;
+}
+
+extern "C" {
+
+int jsdr_bpsk_set_tuning(jsdr_bpsk *h, double tuning_hz)
+{
+    if (bpsk_live_check(h, -1, "jsdr_bpsk_set_tuning") != JSDR_OK) return JSDR_ERR;
+    JSDR_REQUIRE(std::isfinite(tuning_hz), "jsdr_bpsk_set_tuning: tuning %g Hz is not finite", tuning_hz);
+    return live_apply(h, tuning_hz, h->do_fft, h->do_up, true);
+}
+
+int jsdr_bpsk_set_mode(jsdr_bpsk *h, int do_fft, int do_up)
+{
+    if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_set_mode") != JSDR_OK) return JSDR_ERR;
+    if (do_fft && !h->do_fft && fft_mode_alloc(h) != JSDR_OK) return JSDR_ERR;
+    return live_apply(h, h->tuning, do_fft != 0, do_up != 0, true);
+}
+
+int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
+{
+    if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
+    JSDR_REQUIRE(std::isfinite(tuning_hz), "jsdr_bpsk_reconfigure: tuning %g Hz is not finite", tuning_hz);
+    if (do_fft && !h->do_fft && fft_mode_alloc(h) != JSDR_OK) return JSDR_ERR;
+    return live_apply(h, tuning_hz, do_fft != 0, do_up != 0, false);
+}
+
+int jsdr_bpsk_get_control(jsdr_bpsk *h, double *tuning_hz, int *do_fft, int *do_up)
+{
+    JSDR_REQUIRE(h && tuning_hz && do_fft && do_up, "jsdr_bpsk_get_control: null argument");
+    *tuning_hz = h->tuning;
+    *do_fft = h->do_fft;
+    *do_up = h->do_up;
     return JSDR_OK;
 }
 

@@ -18,7 +18,10 @@
 #include <deque>
 #include <mutex>
 #include <thread>
+#include <cmath>
 #include <vector>
+
+int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who);  // bpsk.hip: the checks of jsdr_bpsk_set_tuning / _set_mode
 
 namespace jsdr {
 
@@ -655,6 +658,48 @@ int jsdr_group_read_slot(jsdr_group *h, int index, int stream, uint8_t *slot_hos
     (void)hipSetDevice(prev);
     JSDR_HIP_TRY(e);
     return JSDR_OK;
+}
+
+struct LiveArgs {
+    Group *g;
+    double tuning;
+    int do_fft, do_up, mode;
+};
+
+static int rank_live(void *p, int index)
+{
+    LiveArgs *a = static_cast<LiveArgs *>(p);
+    jsdr_bpsk *d = a->g->ranks[index]->dem;
+    return a->mode ? jsdr_bpsk_set_mode(d, a->do_fft, a->do_up) : jsdr_bpsk_set_tuning(d, a->tuning);
+}
+
+static int group_live(jsdr_group *h, LiveArgs a, const char *who)
+{
+    JSDR_REQUIRE(h, "%s: null handle", who);
+    Group *g = h->g;
+    JSDR_REQUIRE(!g->broken.load(), "%s: the group is broken (a gather failed)", who);
+    JSDR_REQUIRE(a.mode || std::isfinite(a.tuning), "%s: tuning %g Hz is not finite", who, a.tuning);
+    for (Rank *r : g->ranks)
+        if (bpsk_live_check(r->dem, a.mode ? a.do_fft : -1, who) != JSDR_OK) return JSDR_ERR;
+    if (jsdr_group_sync(h) != JSDR_OK) return JSDR_ERR;
+    a.g = g;
+    std::vector<Job> jobs(g->ndev);
+    for (auto &j : jobs) {
+        j.kind = Job::CALL;
+        j.fn = rank_live;
+        j.arg = &a;
+    }
+    return post_all(g, jobs);
+}
+
+int jsdr_group_set_tuning(jsdr_group *h, double tuning_hz)
+{
+    return group_live(h, LiveArgs{nullptr, tuning_hz, 0, 0, 0}, "jsdr_group_set_tuning");
+}
+
+int jsdr_group_set_mode(jsdr_group *h, int do_fft, int do_up)
+{
+    return group_live(h, LiveArgs{nullptr, 0.0, do_fft, do_up, 1}, "jsdr_group_set_mode");
 }
 
 }  // extern "C"

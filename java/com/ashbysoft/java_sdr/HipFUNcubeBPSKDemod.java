@@ -21,7 +21,8 @@ public class HipFUNcubeBPSKDemod extends IUIComponent implements IAudioHandler, 
     private final boolean rawPath;
     private IAudio audio;
     private long handle;
-    private int tuning;
+    private AudioDescriptor audioDesc;
+    private double tuning;   // a double, as the reference's: "bpsk-freq" may give what +-10 never reaches
     private boolean doFFT, doUp;
     // results of the last completed receive(), refreshed through HipNative.bpskSnapshot -- a lock-free host-side read
     // (no device call), so the painting thread never waits for the GPU and never blocks the audio thread
@@ -50,34 +51,85 @@ public class HipFUNcubeBPSKDemod extends IUIComponent implements IAudioHandler, 
             setup((IAudio) val);
     }
 
-    /** the menu actions of :177-190 that change the demodulator: a new tuning or mode restarts it, as setup() does */
-    public synchronized void retune(int newTuning, boolean fft, boolean upper) {
-        config.setIntConfig(name + "-" + CFG_TUNING, newTuning);
-        config.setIntConfig(name + "-" + CFG_DOFFT, fft ? 1 : 0);
-        config.setIntConfig(name + "-" + CFG_UPPER, upper ? 1 : 0);
-        setup(audio);
+    /** the menu actions of :177-190 on the live handle: the tuner, the band and the front end change from the next sample on,
+     *  every other piece of state (the down-sampler, matched filter and bit clock, the FEC register, the counters) carries on */
+    public synchronized void plus10() {
+        setFrequency(tuning + 10.0);
+    }
+
+    public synchronized void sub10() {
+        setFrequency(tuning - 10.0);
+    }
+
+    /** "bpsk-freq": what freqDialog returned */
+    public synchronized void setFrequency(double hz) {
+        HipLiveControl.bpskSetTuning(handle, hz);
+        tuning = hz;
+        config.setIntConfig(name + "-" + CFG_TUNING, (int) tuning);
+    }
+
+    /** "bpsk-fft-tune": the same handle switches front ends, its down-sampler history carried across exactly */
+    public synchronized void toggleFft() {
+        HipLiveControl.bpskSetMode(handle, doFFT ? 0 : 1, doUp ? 1 : 0);
+        doFFT = !doFFT;
+        config.setIntConfig(name + "-" + CFG_DOFFT, doFFT ? 1 : 0);
+        config.setIntConfig(name + "-" + CFG_TUNING, (int) tuning);
+    }
+
+    /** "bpsk-high" */
+    public synchronized void toggleHigh() {
+        HipLiveControl.bpskSetMode(handle, doFFT ? 1 : 0, doUp ? 0 : 1);
+        doUp = !doUp;
+        config.setIntConfig(name + "-" + CFG_UPPER, doUp ? 1 : 0);
+        config.setIntConfig(name + "-" + CFG_TUNING, (int) tuning);
     }
 
     private synchronized void setup(IAudio aud) {
+        AudioDescriptor ad = aud.getAudioDescriptor();
+        int newTuning = config.getIntConfig(name + "-" + CFG_TUNING, 12000);
+        boolean newFFT = 0 != config.getIntConfig(name + "-" + CFG_DOFFT, 0);
+        boolean newUp = 0 != config.getIntConfig(name + "-" + CFG_UPPER, 0);
+        if (handle != 0 && audio != null && sameFormat(ad, audioDesc)) {
+            // :192-209 resets no DSP state: an unchanged format keeps the handle and takes the configuration's values
+            // (tuning truncated to the int the configuration holds, as :195 reads it) without the action's dmMaxCorr = 0
+            HipLiveControl.bpskReconfigure(handle, newTuning, newFFT ? 1 : 0, newUp ? 1 : 0);
+            tuning = newTuning;
+            doFFT = newFFT;
+            doUp = newUp;
+            if (aud != audio) {
+                audio.remHandler(this);
+                audio.remRawHandler(this);
+                audio = aud;
+                if (rawPath)
+                    audio.addRawHandler(this);
+                else
+                    audio.addHandler(this);
+            }
+            return;
+        }
         if (audio != null) {
             audio.remHandler(this);
             audio.remRawHandler(this);
         }
         audio = aud;
-        AudioDescriptor ad = aud.getAudioDescriptor();
-        tuning = config.getIntConfig(name + "-" + CFG_TUNING, 12000);
-        doFFT = 0 != config.getIntConfig(name + "-" + CFG_DOFFT, 0);
-        doUp = 0 != config.getIntConfig(name + "-" + CFG_UPPER, 0);
+        audioDesc = ad;
+        tuning = newTuning;
+        doFFT = newFFT;
+        doUp = newUp;
         long old = handle;
         handle = 0;  // bpskCreate throws when it fails (a frame FFT-acquire mode does not support, no device memory):
                      // the freed pointer must not stay behind for a later getter, close() or setup()
         if (old != 0)
             HipNative.bpskDestroy(old);
-        handle = HipNative.bpskCreate(ad.rate, ad.blen / ad.size, tuning, doFFT ? 1 : 0, doUp ? 1 : 0);
+        handle = HipNative.bpskCreate(ad.rate, ad.blen / ad.size, (int) tuning, doFFT ? 1 : 0, doUp ? 1 : 0);
         if (rawPath)
             audio.addRawHandler(this);
         else
             audio.addHandler(this);
+    }
+
+    private static boolean sameFormat(AudioDescriptor a, AudioDescriptor b) {
+        return b != null && a.rate == b.rate && a.blen == b.blen && a.size == b.size && a.chns == b.chns && a.bits == b.bits;
     }
 
     public synchronized void receive(float[] buf) {
@@ -101,7 +153,7 @@ public class HipFUNcubeBPSKDemod extends IUIComponent implements IAudioHandler, 
             publish.setPublish(name + "-bpsk-centre", centre);
         } else {      // :377-378
             publish.setPublish(name + "-bpsk-centre", -1);
-            publish.setPublish(name + "-bpsk-tune", tuning);
+            publish.setPublish(name + "-bpsk-tune", (int) tuning);
         }
         repaint();
     }

@@ -192,6 +192,29 @@ JNIEXPORT void JNICALL Java_com_ashbysoft_java_1sdr_HipNative_bpskDestroy(JNIEnv
     if (rc != JSDR_OK) fail(e);
 }
 
+/* live control, FUNcubeBPSKDemod.java:165-190 (HipLiveControl.java): the same handle, nothing else reset */
+JNIEXPORT void JNICALL Java_com_ashbysoft_java_1sdr_HipLiveControl_bpskSetTuning(JNIEnv *e, jclass c, jlong h, jdouble tuning)
+{
+    bpsk_ctx *x = CTX(bpsk_ctx, h);
+    if (null_handle(e, x, "bpskSetTuning")) return;
+    if (jsdr_bpsk_set_tuning(x->h, tuning) != JSDR_OK) fail(e);
+}
+
+JNIEXPORT void JNICALL Java_com_ashbysoft_java_1sdr_HipLiveControl_bpskSetMode(JNIEnv *e, jclass c, jlong h, jint doFFT, jint doUp)
+{
+    bpsk_ctx *x = CTX(bpsk_ctx, h);
+    if (null_handle(e, x, "bpskSetMode")) return;
+    if (jsdr_bpsk_set_mode(x->h, doFFT, doUp) != JSDR_OK) fail(e);
+}
+
+JNIEXPORT void JNICALL Java_com_ashbysoft_java_1sdr_HipLiveControl_bpskReconfigure(JNIEnv *e, jclass c, jlong h, jdouble tuning,
+                                                                                     jint doFFT, jint doUp)
+{
+    bpsk_ctx *x = CTX(bpsk_ctx, h);
+    if (null_handle(e, x, "bpskReconfigure")) return;
+    if (jsdr_bpsk_reconfigure(x->h, tuning, doFFT, doUp) != JSDR_OK) fail(e);
+}
+
 JNIEXPORT void JNICALL Java_com_ashbysoft_java_1sdr_HipNative_bpskReceive(JNIEnv *e, jclass c, jlong h, jfloatArray buf)
 {
     bpsk_ctx *x = CTX(bpsk_ctx, h);
