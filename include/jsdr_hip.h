@@ -216,6 +216,30 @@ int jsdr_bpsk_get_control(jsdr_bpsk *h, double *tuning_hz, int *do_fft, int *do_
 /* FUNcubeBPSKDemod.setup (:192-209) on an unchanged AudioDescriptor: tuning, doFFT, doUp and tuPhaseInc from the
  * configuration, dmMaxCorr left as it is (setup resets no DSP state); otherwise as set_tuning + set_mode */
 int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up);
+/* Channel handle: jsdr.java's nfcs FUNcubeBPSKDemod tabs (:479-483, each "FUNcube<idx>" with its own bpsk-tuning / -upper,
+ * FUNcubeBPSKDemod.java:129,195-200) fed the same audio.  One handle of ninputs x nchannels demodulators in the tune mode
+ * (doBufferTune, :366-397); channel c of input i is stream i * nchannels + c, so every per-stream getter, pack_slots and
+ * the slot layout apply unchanged.  Every channel has its own tuning (tuning_hz[c], any finite value; <= 0: pass-through
+ * per :388-396) and doUp (do_up[c], may be NULL: 0; stored and reported, no effect in the tune mode).  1 <= nchannels <= 16.
+ * Each input is read from memory once for all its channels.  Results are bit-identical to nchannels independent
+ * demodulators created with those tunings and fed the same input.
+ *   jsdr_bpsk_batch_i16: stream_stride_i16 is the stride between INPUTS (>= 2 nsamples when ninputs > 1).
+ *   receive_i16 / receive_f32 on a 1-input handle feed the frame to every channel.  receive_f32 takes the frames JavaAudio
+ *     produces ((float)s/32767f values, run through the int16 kernels) and refuses any other float with JSDR_ERR.
+ *   set_channel_tuning: actionPerformed's tuning change (:177-189) on the streams of that channel on every input: tuning,
+ *     tuPhaseInc = 2 pi tuning / rate, dmMaxCorr = 0; everything else carries on, the other channels are not touched.
+ *   set_channel_mode: do_fft must be 0; do_up stored; dmMaxCorr = 0 on that channel.  set_tuning / set_mode / reconfigure
+ *     apply to every channel; get_control reports channel 0.
+ *   channel_info: an ordinary handle reports nstreams x 1 (and takes channel 0 in the per-channel calls).
+ * JSDR_ERR, the handle unchanged: do_fft = 1 in set_mode / set_channel_mode / reconfigure, set_variant(FAST), snapshot_read
+ * when nchannels > 1, a channel out of range, a non-finite tuning; float input through batch calls.  Not covered:
+ * FFT-acquire channels, the FAST variant, jsdr_group, JNI / Java classes, a per-channel snapshot. */
+int jsdr_bpsk_create_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                              const double *tuning_hz, const int *do_up, int64_t max_batch_samples);
+int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels);
+int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz);
+int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up);
+int jsdr_bpsk_get_channel_control(jsdr_bpsk *h, int channel, double *tuning_hz, int *do_fft, int *do_up);
 /* receive(float[]) / raw form for stream 0 of a 1-stream handle (:357-364) */
 int jsdr_bpsk_receive_f32(jsdr_bpsk *h, const float *iq_host);
 int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc);

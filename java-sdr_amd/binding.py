@@ -610,6 +610,67 @@ class Bpsk:
             pass
 
 
+class BpskChannels(Bpsk):
+    """`ninputs` inputs x len(tunings) independently tuned FUNcubeBPSKDemod instances (jsdr.java:479-483's nfcs tabs fed the
+    same audio).  Channel c of input i is stream i * nchannels + c; every getter takes (input, channel)."""
+
+    def __init__(self, rate, blen, tunings, do_up=None, ninputs=1, max_batch_samples=None, size=4):
+        tunings = [float(t) for t in tunings]
+        self.samples = blen // size
+        self.ninputs = ninputs
+        self.nchannels = len(tunings)
+        self.nstreams = ninputs * self.nchannels
+        self.max_batch = max_batch_samples or self.samples
+        self.h = C.c_void_p()
+        tu = (C.c_double * max(self.nchannels, 1))(*tunings)
+        up = None if do_up is None else (C.c_int * max(self.nchannels, 1))(*[int(v) for v in do_up])
+        _check(lib().jsdr_bpsk_create_channels(C.byref(self.h), rate, self.samples, ninputs, self.nchannels, tu if tunings else None,
+                                               up, C.c_int64(self.max_batch)), "jsdr_bpsk_create_channels")
+
+    def stream(self, inp, ch):
+        return inp * self.nchannels + ch
+
+    def channel_info(self):
+        a, b = C.c_int(), C.c_int()
+        _check(lib().jsdr_bpsk_channel_info(self.h, C.byref(a), C.byref(b)), "jsdr_bpsk_channel_info")
+        return a.value, b.value
+
+    def batch_i16(self, raw_dev, input_stride_i16, nsamples, ic=0, qc=0, stream=None):
+        """input_stride_i16: between INPUTS"""
+        super().batch_i16(raw_dev, input_stride_i16, nsamples, ic, qc, stream)
+
+    def set_channel_tuning(self, channel, tuning_hz):
+        _check(lib().jsdr_bpsk_set_channel_tuning(self.h, int(channel), C.c_double(tuning_hz)), "jsdr_bpsk_set_channel_tuning")
+
+    def set_channel_mode(self, channel, do_fft, do_up):
+        _check(lib().jsdr_bpsk_set_channel_mode(self.h, int(channel), int(do_fft), int(do_up)), "jsdr_bpsk_set_channel_mode")
+
+    def channel_control(self, channel):
+        """(tuning_hz, do_fft, do_up) of that channel"""
+        t, f, u = C.c_double(), C.c_int(), C.c_int()
+        _check(lib().jsdr_bpsk_get_channel_control(self.h, int(channel), C.byref(t), C.byref(f), C.byref(u)),
+               "jsdr_bpsk_get_channel_control")
+        return t.value, f.value, u.value
+
+    def counters(self, inp=0, ch=0):
+        return super().counters(self.stream(inp, ch))
+
+    def bits(self, inp=0, ch=0):
+        return super().bits(self.stream(inp, ch))
+
+    def fec_results(self, inp=0, ch=0):
+        return super().fec_results(self.stream(inp, ch))
+
+    def decoded(self, inp=0, ch=0):
+        return super().decoded(self.stream(inp, ch))
+
+    def trace(self, inp=0, ch=0):
+        return super().trace(self.stream(inp, ch))
+
+    def state(self, inp=0, ch=0):
+        return super().state(self.stream(inp, ch))
+
+
 class Group:
     """jsdr_group_*: `total_streams` demodulators of ONE process over `ndev` devices, one host thread per device, the result
     slots gathered to every device after each call (RCCL, or device-to-device copies with gather_copy=True)."""

@@ -37,6 +37,7 @@ SOURCES = {
     "bpsk_acq.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
     "bpsk_fftm.hip": ["-ffp-contract=off"],
     "bpsk_acqg.hip": ["-ffp-contract=off"],
+    "bpsk_chan.hip": ["-ffp-contract=off"],
     "group.hip": [],
 }
 

@@ -22,6 +22,7 @@
 // DESIGN.md has the lane/LDS mapping of each kernel and its roofline.
 #include "bpsk_fec.h"
 #include "bpsk_fft.h"
+#include "bpsk_chan.h"
 #include <math.h>
 #include <cmath>
 #include <atomic>
@@ -2462,6 +2463,25 @@ struct Schedule {
     std::vector<double2> tcs;
 };
 
+// one channel of a channel handle (jsdr_bpsk_create_channels): its tuner (FUNcubeBPSKDemod.java:381-390, :196) and the
+// cache of its last schedule.  The table is of 9-bit indices (256: the sample passed through unmixed, :395).
+struct BpskChan {
+    double tuning = 0.0, tuPhase = 0.0, tuPhaseInc = 0.0;
+    int do_up = 0;
+    unsigned short khist[26] = {0};  // indices of the 26 samples before the next call
+    // the schedule last computed for this channel, keyed by the state it started from
+    bool valid = false;
+    double k_tu0 = 0.0, k_inc = 0.0;
+    long long k_L = -1;
+    bool k_first = false;
+    unsigned short k_hist0[26] = {0};
+    double tu1 = 0.0;                 // tuPhase at its end
+    unsigned short khist1[26] = {0};  // the indices of its last 26 samples
+    int per = 0;                      // > 0: tab holds one period (entry (n + 26) mod per); 0: tab holds 26 + L entries
+    std::vector<unsigned short> tab;
+    DevBuf<unsigned short> dev;       // the device copy of tab
+};
+
 struct SnapPack {
     TailState t;
     int last[2];
@@ -2623,6 +2643,13 @@ struct jsdr_bpsk {
     };
     std::vector<ProfRec> prof_recs;
     std::vector<hipEvent_t> prof_pool;
+    // channel handle (jsdr_bpsk_create_channels): nch > 0 channels per input, stream = input * nch + channel
+    int nch = 0, nin = 0;
+    BpskChan *chan = nullptr;
+    bool vco_valid = false;          // the shared VCO schedule of the last call, keyed by (vcoPhase, dsCnt, L) at its start
+    double v_vco0 = 0.0, v_vco1 = 0.0;
+    int v_ds0 = 0, v_ds1 = 0;
+    long long v_L = -1;
 };
 
 enum { PK_FRONT = 0, PK_HIST, PK_MATCHED, PK_DMHIST, PK_TAIL, PK_SYNC, PK_SYNCFIN, PK_FEC, PK_FM, PK_SYNCT, PK_PREP,
@@ -3216,10 +3243,261 @@ static int run_side(jsdr_bpsk *h, const SideJob &j)
     return JSDR_OK;
 }
 
+// ------------------------------------------------------------------------------------------- channel handles
+// The tuner schedule of one channel for a call of L samples from the state in its key (k_tu0, k_inc, k_hist0, first):
+// compute_schedule's tuner recurrence, step for step, with the sign test (:388) folded into the index (256: pass-through).
+// Then the shortest period p <= 256 that holds over every sample of the call (and the 26 history samples, except at the
+// stream's start, where they are zeros and their factor does not matter) -- one period is all the device needs.
+static void chan_compute(BpskChan &c, long long L, bool first)
+{
+    const double two_pi = 2.0 * JPI;
+    std::vector<unsigned short> full((size_t)L + 26);
+    memcpy(full.data(), c.k_hist0, sizeof(c.k_hist0));
+    double tu = c.k_tu0;
+    const double inc = c.k_inc;
+    unsigned short *kt = full.data() + 26;
+    for (long long n = 0; n < L; n++) {
+        tu += inc;
+        if (tu > two_pi) tu -= two_pi;
+        kt[n] = tu > 0.0 ? (unsigned short)((int)(tu * (double)256 / two_pi) % 256) : (unsigned short)256;
+    }
+    c.tu1 = tu;
+    memcpy(c.khist1, full.data() + L, sizeof(c.khist1));
+    const long long off = first ? 26 : 0;
+    const long long len = L + 26 - off;
+    const unsigned short *k = full.data() + off;
+    c.per = 0;
+    for (int p = 1; p <= 256 && p < len; p++) {
+        bool same = true;
+        for (long long i = 0; i + p < len && same; i++) same = k[i] == k[i + p];
+        if (!same) continue;
+        c.per = p;
+        c.tab.resize((size_t)p);
+        for (int e = 0; e < p; e++) c.tab[(size_t)e] = k[(((e - off) % p) + p) % p];  // the entry of the samples n + 26 == e mod p
+        break;
+    }
+    if (c.per == 0) c.tab.swap(full);
+    c.k_L = L;
+    c.k_first = first;
+    c.valid = true;
+}
+
+static bool chan_key_equal(const BpskChan &a, const BpskChan &b)
+{
+    return a.k_tu0 == b.k_tu0 && a.k_inc == b.k_inc && a.k_L == b.k_L && a.k_first == b.k_first &&
+           memcmp(a.k_hist0, b.k_hist0, sizeof(a.k_hist0)) == 0;
+}
+
+// Every channel's schedule for a call of L samples: a channel whose state has come back to where its cached schedule
+// started takes that one (a periodic tuning with a call length of whole periods: nothing to build after its first calls);
+// channels with equal keys share one computation; the rest are built in parallel, one thread per schedule (at most 16, the
+// most channels a handle has), for calls long enough to pay for the threads.  *fresh[c]: the device copy must be sent.
+static void chan_schedules(jsdr_bpsk *h, long long L, bool first, bool *fresh)
+{
+    std::vector<int> lead;
+    std::vector<int> follow(h->nch, -1);
+    for (int c = 0; c < h->nch; c++) {
+        BpskChan &ch = h->chan[c];
+        fresh[c] = false;
+        if (ch.valid && ch.k_L == L && ch.k_first == first && ch.k_tu0 == ch.tuPhase && ch.k_inc == ch.tuPhaseInc &&
+            memcmp(ch.k_hist0, ch.khist, sizeof(ch.khist)) == 0)
+            continue;
+        ch.k_tu0 = ch.tuPhase;
+        ch.k_inc = ch.tuPhaseInc;
+        ch.k_L = L;
+        ch.k_first = first;
+        memcpy(ch.k_hist0, ch.khist, sizeof(ch.khist));
+        fresh[c] = true;
+        for (int l : lead)
+            if (chan_key_equal(h->chan[l], ch)) follow[c] = l;
+        if (follow[c] < 0) lead.push_back(c);
+    }
+    if (lead.size() >= 2 && L >= 65536) {
+        std::vector<std::thread> pool;
+        for (int l : lead) pool.emplace_back([h, l, L, first] { chan_compute(h->chan[l], L, first); });
+        for (auto &t : pool) t.join();
+    } else {
+        for (int l : lead) chan_compute(h->chan[l], L, first);
+    }
+    h->sched_sync += (long long)lead.size();
+    for (int c = 0; c < h->nch; c++) {
+        if (follow[c] < 0) continue;
+        const BpskChan &src = h->chan[follow[c]];
+        BpskChan &ch = h->chan[c];
+        ch.tu1 = src.tu1;
+        memcpy(ch.khist1, src.khist1, sizeof(ch.khist1));
+        ch.per = src.per;
+        ch.tab = src.tab;
+        ch.valid = true;
+    }
+    for (int c = 0; c < h->nch; c++) {
+        BpskChan &ch = h->chan[c];
+        ch.tuPhase = ch.tu1;
+        memcpy(ch.khist, ch.khist1, sizeof(ch.khist));
+    }
+}
+
+// The shared VCO schedule (:511-516): the same for every channel and input.  Left in h->h_kvco; returns the outputs of the call.
+static long long chan_vco(jsdr_bpsk *h, long long L, bool *fresh)
+{
+    *fresh = false;
+    if (!(h->vco_valid && h->v_L == L && h->v_vco0 == h->vcoPhase && h->v_ds0 == h->dsCnt)) {
+        const double two_pi = 2.0 * JPI;
+        const double vinc = 2.0 * JPI * 1200.0 / (double)9600;  // VCO_PHASE_INC (:88)
+        h->h_kvco.clear();
+        h->h_kvco.reserve((size_t)(L / h->decim + 2));
+        double vco = h->vcoPhase;
+        int cnt = h->dsCnt;
+        for (long long n = 0; n < L; n++) {
+            if (++cnt >= h->decim) {
+                cnt = 0;
+                vco += vinc;
+                if (vco > two_pi) vco -= two_pi;
+                h->h_kvco.push_back((unsigned char)((int)(vco * (double)256 / two_pi) % 256));
+            }
+        }
+        h->v_vco0 = h->vcoPhase;
+        h->v_ds0 = h->dsCnt;
+        h->v_L = L;
+        h->v_vco1 = vco;
+        h->v_ds1 = cnt;
+        h->vco_valid = true;
+        *fresh = true;
+    }
+    h->vcoPhase = h->v_vco1;
+    h->dsCnt = h->v_ds1;
+    return (long long)h->h_kvco.size();
+}
+
+// A call of a channel handle: every channel of every input through k_chan_front, then the per-stream matched filter, tail,
+// sync and FEC exactly as bpsk_run launches them for an ordinary handle of ninputs x nchannels streams.
+static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, long long stride_i16, long long L, int ic,
+                    int qc, hipStream_t st)
+{
+    JSDR_REQUIRE(raw_dev && !rawf_dev, "bpsk channels: the channel handle takes int16 input");
+    JSDR_REQUIRE(L > 0 && L <= h->max_batch, "bpsk: nsamples=%lld outside (0, max_batch_samples=%lld]", L, h->max_batch);
+    JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nin == 1 || stride_i16 >= 2 * L),
+                 "bpsk channels: input stride %lld too small for %lld samples", stride_i16, L);
+    const int first_out = h->decim - 1 - h->dsCnt;
+    const long long g_first = h->n_ds;
+    const bool first = h->n_in == 0;
+    bool vfresh = false;
+    const long long nds = chan_vco(h, L, &vfresh);
+    JSDR_REQUIRE(nds <= h->max_ds, "bpsk: internal: %lld decimated samples exceed capacity %lld", nds, h->max_ds);
+    bool fresh[CHAN_MAX];
+    chan_schedules(h, L, first, fresh);
+    if (vfresh && nds > 0)
+        if (h2d_call(h, h->kvco.p, h->h_kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
+    for (int c = 0; c < h->nch; c++)
+        if (fresh[c])
+            if (h2d_call(h, h->chan[c].dev.p, h->chan[c].tab.data(), sizeof(unsigned short) * h->chan[c].tab.size(), st) != JSDR_OK)
+                return JSDR_ERR;
+    if (h->rx_frame_bytes) {  // receive(): the frame waits at the pinned arena's head
+        JSDR_HIP_TRY(hipMemcpyAsync(h->stage_raw.p, h->pin, h->rx_frame_bytes, hipMemcpyHostToDevice, st));
+        h->rx_frame_bytes = 0;
+    }
+    const int S = h->nstreams;
+    const int *raw = reinterpret_cast<const int *>(raw_dev);
+    if (nds > 0) {
+        ChanFrontArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.raw = raw;
+        fa.stride_pairs = stride_i16 / 2;
+        fa.ic = ic;
+        fa.qc = qc;
+        fa.hist = h->hist_in[h->hist_cur].p;
+        for (int c = 0; c < h->nch; c++) {
+            fa.k9[c] = h->chan[c].dev.p;
+            fa.per[c] = h->chan[c].per;
+        }
+        fa.nch = h->nch;
+        fa.kvco = h->kvco.p;
+        fa.sc9 = h->sincos9.p;
+        fa.ds_taps = h->ds_taps_dev.p;
+        fa.dm = h->dm.p;
+        fa.dm_stride = h->dm_stride;
+        fa.nds = nds;
+        fa.first_out = first_out;
+        fa.decim = h->decim;
+        ProfScope ps(h, PK_FRONT, st);
+        h->front_name = "k_chan_front";
+        if (launch_chan_front(fa, h->nin, st) != JSDR_OK) return JSDR_ERR;
+    }
+    {
+        HistArgs ha;  // per input
+        ha.raw = raw;
+        ha.rawf = nullptr;
+        ha.stride_pairs = stride_i16 / 2;
+        ha.nsamples = L;
+        ha.ic = ic;
+        ha.qc = qc;
+        ha.hist_old = h->hist_in[h->hist_cur].p;
+        ha.hist_new = h->hist_in[h->hist_cur ^ 1].p;
+        ha.nstreams = h->nin;
+        ProfScope ps(h, PK_HIST, st);
+        hipLaunchKernelGGL(k_hist_in, dim3((unsigned)((h->nin * 32 + 255) / 256)), dim3(256), 0, st, ha);
+        JSDR_LAUNCH_CHECK();
+        h->hist_cur ^= 1;
+    }
+    const int yb = h->y_cur;
+    if (h->overlap && h->tail_pending[yb]) {
+        // the tail that last read y[yb] (two calls ago) must be done before the matched filter overwrites it
+        JSDR_HIP_TRY(hipStreamWaitEvent(st, h->ev_tail_done[yb], 0));
+        h->tail_pending[yb] = false;
+    }
+    if (nds > 0) {
+        MatchedArgs ma;
+        ma.dm = h->dm.p;
+        ma.dm_stride = h->dm_stride;
+        ma.y = h->y[yb].p + Y_PAD;
+        ma.y_stride = h->y_stride;
+        ma.nds = nds;
+        ma.g_first = g_first;
+        const long long b0 = g_first - (((g_first - 64) % 65 + 65) % 65);
+        ma.tile0 = b0;
+        const long long ntiles = (g_first + nds - b0 + 4159) / 4160;
+        const size_t lds = (64 + 4160) * sizeof(double2);
+        JSDR_LDS_ATTR(k_matched<false>, lds);
+        {
+            ProfScope ps(h, PK_MATCHED, st);
+            hipLaunchKernelGGL(k_matched<false>, dim3((unsigned)ntiles, (unsigned)S), dim3(512), lds, st, ma);
+        }
+        JSDR_LAUNCH_CHECK();
+        ProfScope ps2(h, PK_DMHIST, st);
+        hipLaunchKernelGGL(k_dm_history, dim3((unsigned)S), dim3(64), 0, st, h->dm.p, h->dm_stride, nds, S);
+        JSDR_LAUNCH_CHECK();
+    }
+    {
+        SideJob job;
+        job.valid = true;
+        job.yb = yb;
+        job.nds = nds;
+        job.g_first = g_first;
+        job.first_out = first_out;
+        job.ic = ic;
+        job.qc = qc;
+        job.raw = raw;
+        job.stride_pairs = stride_i16 / 2;
+        job.kvco_p = h->kvco.p;
+        job.tcs_p = h->tcs.p;
+        job.st = st;
+        if (h->overlap) JSDR_HIP_TRY(hipEventRecord(h->ev_matched, st));
+        if (run_side(h, job) != JSDR_OK) return JSDR_ERR;
+    }
+    h->tuPhase = h->chan[0].tuPhase;
+    h->last_y = yb;
+    h->n_in += L;
+    h->n_ds += nds;
+    h->last_nds = nds;
+    h->last_stream = st;
+    return JSDR_OK;
+}
+
 static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, long long stride_i16, long long L,
                     int ic, int qc, hipStream_t st)
 {
     JSDR_REQUIRE(h, "bpsk: null handle");
+    if (h->nch > 0) return chan_run(h, raw_dev, rawf_dev, stride_i16, L, ic, qc, st);
     JSDR_REQUIRE(raw_dev || rawf_dev, "bpsk: null input");
     JSDR_REQUIRE(L > 0 && L <= h->max_batch, "bpsk: nsamples=%lld outside (0, max_batch_samples=%lld]", L, h->max_batch);
     JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nstreams == 1 || stride_i16 >= 2 * L),
@@ -3954,6 +4232,12 @@ int jsdr_bpsk_destroy(jsdr_bpsk *h)
 {
     if (!h) return JSDR_OK;
     if (h->worker.joinable()) h->worker.join();
+    if (h->chan) {
+        (void)hipDeviceSynchronize();
+        for (int c = 0; c < h->nch; c++) h->chan[c].dev.release();
+        delete[] h->chan;
+        h->chan = nullptr;
+    }
     h->sincos.release();
     h->ktu.release();
     h->kvco.release();
@@ -4219,7 +4503,8 @@ int jsdr_bpsk_last_launch(jsdr_bpsk *h, int64_t *work_items, int64_t *workgroups
 int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
 {
     JSDR_REQUIRE(h && raw_host, "jsdr_bpsk_receive_i16: null argument");
-    JSDR_REQUIRE(h->nstreams == 1, "jsdr_bpsk_receive_i16: handle has %d streams; receive() is the 1-stream form",
+    JSDR_REQUIRE(h->nstreams == 1 || (h->nch > 0 && h->nin == 1),
+                 "jsdr_bpsk_receive_i16: handle has %d streams; receive() is the 1-stream form (or a 1-input channel handle)",
                  h->nstreams);
     h->pin_call = true;
     h->pin_off = 0;
@@ -4235,7 +4520,7 @@ int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
     if (rc == JSDR_OK)
         rc = bpsk_run(h, reinterpret_cast<const int16_t *>(h->stage_raw.p), nullptr, 2LL * h->nsf, h->nsf, ic, qc, 0);
     h->rx_frame_bytes = 0;
-    if (rc == JSDR_OK) rc = publish_snapshot(h);  // synchronises: the arena is free again
+    if (rc == JSDR_OK) rc = h->nstreams == 1 ? publish_snapshot(h) : sync_last(h);  // synchronises: the arena is free again
     if (rc != JSDR_OK) (void)hipDeviceSynchronize();  // (a failed call, wherever it failed: nothing may still be reading the arena)
     h->pin_call = false;
     return rc;
@@ -4244,6 +4529,24 @@ int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
 int jsdr_bpsk_receive_f32(jsdr_bpsk *h, const float *iq_host)
 {
     JSDR_REQUIRE(h && iq_host, "jsdr_bpsk_receive_f32: null argument");
+    if (h->nch > 0) {
+        // a channel handle takes what IAudioHandler delivers, (float)s / 32767f values (JavaAudio.java:281-288), through the
+        // int16 kernels; any other float frame is refused
+        JSDR_REQUIRE(h->nin == 1, "jsdr_bpsk_receive_f32: the channel handle has %d inputs; receive() takes a 1-input handle", h->nin);
+        std::vector<int16_t> q(2 * (size_t)h->nsf);
+        for (size_t i = 0; i < q.size(); i++) {
+            const float f = iq_host[i];
+            float v = f * 32767.0f;
+            if (!(v == v)) v = 1e9f;  // NaN: refused below
+            v = v > 32767.0f ? 32767.0f : (v < -32768.0f ? -32768.0f : v);
+            const int sv = (int)__builtin_rintf(v);
+            const float back = (float)sv / 32767.0f;
+            JSDR_REQUIRE(memcmp(&back, &f, 4) == 0, "jsdr_bpsk_receive_f32: sample %zu (%g) is not a (float)s/32767f value; a channel "
+                         "handle takes the frames JavaAudio produces (the int16 kernels) and refuses other floats", i, (double)f);
+            q[i] = (int16_t)sv;
+        }
+        return jsdr_bpsk_receive_i16(h, q.data(), 0, 0);
+    }
     JSDR_REQUIRE(h->nstreams == 1, "jsdr_bpsk_receive_f32: handle has %d streams; receive() is the 1-stream form",
                  h->nstreams);
     h->pin_call = true;
@@ -4387,6 +4690,7 @@ static int publish_snapshot(jsdr_bpsk *h)
     jsdr_bpsk_snapshot &sn = h->snap[w];
     counters_from(h, pk.t, pk.last, pk.cdec, pk.centreBin, sn.counters);
     state_from(h, pk.t, pk.avePeakPower, pk.aveCentreBin, sn.state);
+    if (h->nch > 0) sn.state[0] = h->chan[0].tuPhase;
     memcpy(sn.decoded, pk.decoded, 256);
     static_assert(sizeof(sn.bits) == sizeof(pk.bits), "snapshot bit capacity");
     memcpy(sn.bits, pk.bits, sizeof(sn.bits));
@@ -4530,6 +4834,7 @@ int jsdr_bpsk_get_state(jsdr_bpsk *h, int stream, double out[18])
         acb = fs.aveCentreBin;
     }
     state_from(h, t, app, acb, out);
+    if (h->nch > 0) out[0] = h->chan[stream % h->nch].tuPhase;
     return JSDR_OK;
 }
 
@@ -4543,6 +4848,7 @@ int jsdr_bpsk_sync(jsdr_bpsk *h)
 int jsdr_bpsk_snapshot_read(jsdr_bpsk *h, jsdr_bpsk_snapshot *out)
 {
     JSDR_REQUIRE(h && out, "jsdr_bpsk_snapshot_read: null argument");
+    JSDR_REQUIRE(h->nch <= 1, "jsdr_bpsk_snapshot_read: a channel handle of %d channels has no snapshot (read the getters per stream)", h->nch);
     for (int attempt = 0; attempt < 1000; attempt++) {
         const int cur = h->snap_cur.load(std::memory_order_acquire);
         JSDR_REQUIRE(cur >= 0, "jsdr_bpsk_snapshot_read: nothing received yet");
@@ -4664,6 +4970,7 @@ int jsdr_bpsk_set_variant(jsdr_bpsk *h, int variant)
 {
     JSDR_REQUIRE(h, "jsdr_bpsk_set_variant: null handle");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || variant == JSDR_VARIANT_FAST, "jsdr_bpsk_set_variant: unknown variant %d", variant);
+    JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || h->nch == 0, "jsdr_bpsk_set_variant: a channel handle has no fast variant");
     JSDR_REQUIRE(h->n_in == 0, "jsdr_bpsk_set_variant: the variant is fixed once samples have been received");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->do_fft, "jsdr_bpsk_set_variant: the fast variant covers the tune mode only");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->retuned, "jsdr_bpsk_set_variant: the fast variant has no live control, and this handle was retuned");
@@ -4800,18 +5107,61 @@ static int live_apply(jsdr_bpsk *h, double tuning, int do_fft, int do_up, bool z
     return JSDR_OK;
 }
 
+// actionPerformed on channel `ch` (-1: every channel) of a channel handle, after the handle's pending work: tuning (and
+// tuPhaseInc, :189) and / or doUp, and dmMaxCorr = 0 (:190) in the streams of those channels on every input.  tuPhase and
+// every other piece of state carry on; the other channels are not touched.  The one step that can fail comes first.
+__global__ void k_reset_maxcorr_chan(TailState *st, int nin, int nch, int ch)
+{
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < nin * nch && (ch < 0 || s % nch == ch)) st[s].dmMaxCorr = 0;
+}
+
+static int chan_apply(jsdr_bpsk *h, int ch, const double *tuning, const int *do_up, bool zero_maxcorr, const char *who)
+{
+    JSDR_REQUIRE(ch >= -1 && ch < h->nch, "%s: channel %d out of range (the handle has %d); the handle is unchanged", who, ch, h->nch);
+    JSDR_REQUIRE(!tuning || std::isfinite(*tuning), "%s: tuning %g Hz is not finite; the handle is unchanged", who, tuning ? *tuning : 0.0);
+    if (sync_last(h) != JSDR_OK) return JSDR_ERR;
+    if (zero_maxcorr) {
+        hipStream_t st = h->last_stream;
+        hipLaunchKernelGGL(k_reset_maxcorr_chan, dim3((unsigned)((h->nstreams + 255) / 256)), dim3(256), 0, st, h->tail.p, h->nin,
+                           h->nch, ch);
+        JSDR_LAUNCH_CHECK();
+        JSDR_HIP_TRY(hipStreamSynchronize(st));
+    }
+    for (int c = 0; c < h->nch; c++) {
+        if (ch >= 0 && c != ch) continue;
+        BpskChan &cc = h->chan[c];
+        if (tuning) {
+            cc.tuning = *tuning;
+            cc.tuPhaseInc = 2.0 * JPI * *tuning / (double)h->rate;  // :189
+        }
+        if (do_up) cc.do_up = *do_up;
+    }
+    h->tuning = h->chan[0].tuning;
+    h->tuPhaseInc = h->chan[0].tuPhaseInc;
+    h->do_up = h->chan[0].do_up;
+    h->retuned = true;
+    return JSDR_OK;
+}
+
 extern "C" {
 
 int jsdr_bpsk_set_tuning(jsdr_bpsk *h, double tuning_hz)
 {
     if (bpsk_live_check(h, -1, "jsdr_bpsk_set_tuning") != JSDR_OK) return JSDR_ERR;
     JSDR_REQUIRE(std::isfinite(tuning_hz), "jsdr_bpsk_set_tuning: tuning %g Hz is not finite", tuning_hz);
+    if (h->nch > 0) return chan_apply(h, -1, &tuning_hz, nullptr, true, "jsdr_bpsk_set_tuning");
     return live_apply(h, tuning_hz, h->do_fft, h->do_up, true);
 }
 
 int jsdr_bpsk_set_mode(jsdr_bpsk *h, int do_fft, int do_up)
 {
     if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_set_mode") != JSDR_OK) return JSDR_ERR;
+    if (h->nch > 0) {
+        JSDR_REQUIRE(!do_fft, "jsdr_bpsk_set_mode: a channel handle runs in the tune mode only; the handle is unchanged");
+        const int up = do_up != 0;
+        return chan_apply(h, -1, nullptr, &up, true, "jsdr_bpsk_set_mode");
+    }
     if (do_fft && !h->do_fft && fft_mode_alloc(h) != JSDR_OK) return JSDR_ERR;
     return live_apply(h, h->tuning, do_fft != 0, do_up != 0, true);
 }
@@ -4820,6 +5170,11 @@ int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
 {
     if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
     JSDR_REQUIRE(std::isfinite(tuning_hz), "jsdr_bpsk_reconfigure: tuning %g Hz is not finite", tuning_hz);
+    if (h->nch > 0) {
+        JSDR_REQUIRE(!do_fft, "jsdr_bpsk_reconfigure: a channel handle runs in the tune mode only; the handle is unchanged");
+        const int up = do_up != 0;
+        return chan_apply(h, -1, &tuning_hz, &up, false, "jsdr_bpsk_reconfigure");
+    }
     if (do_fft && !h->do_fft && fft_mode_alloc(h) != JSDR_OK) return JSDR_ERR;
     return live_apply(h, tuning_hz, do_fft != 0, do_up != 0, false);
 }
@@ -4830,6 +5185,106 @@ int jsdr_bpsk_get_control(jsdr_bpsk *h, double *tuning_hz, int *do_fft, int *do_
     *tuning_hz = h->tuning;
     *do_fft = h->do_fft;
     *do_up = h->do_up;
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_create_channels(jsdr_bpsk **out, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                              const double *tuning_hz, const int *do_up, int64_t max_batch_samples)
+{
+    JSDR_REQUIRE(out, "jsdr_bpsk_create_channels: null handle pointer");
+    *out = nullptr;
+    JSDR_REQUIRE(nchannels >= 1 && nchannels <= CHAN_MAX, "jsdr_bpsk_create_channels: nchannels %d outside 1 .. %d", nchannels, (int)CHAN_MAX);
+    JSDR_REQUIRE(ninputs >= 1 && (long long)ninputs * nchannels <= 65535, "jsdr_bpsk_create_channels: %d inputs x %d channels", ninputs,
+                 nchannels);
+    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_create_channels: null tuning array");
+    for (int c = 0; c < nchannels; c++)
+        JSDR_REQUIRE(std::isfinite(tuning_hz[c]), "jsdr_bpsk_create_channels: tuning of channel %d (%g Hz) is not finite", c, tuning_hz[c]);
+    if (max_batch_samples < nsamples_per_frame) max_batch_samples = nsamples_per_frame;
+    JSDR_REQUIRE(max_batch_samples <= 0x3fffffffLL, "jsdr_bpsk_create_channels: max_batch_samples %lld above 2^30 - 1",
+                 (long long)max_batch_samples);
+    jsdr_bpsk *h = nullptr;
+    if (jsdr_bpsk_create(&h, rate, nsamples_per_frame, 0, 0, do_up ? do_up[0] != 0 : 0, ninputs * nchannels, max_batch_samples) != JSDR_OK)
+        return JSDR_ERR;
+    h->nch = nchannels;
+    h->nin = ninputs;
+    h->use_fm = false;
+    h->chan = new BpskChan[nchannels];
+    bool ok = h->sincos9.alloc(514) == JSDR_OK;
+    for (int c = 0; c < nchannels && ok; c++) {
+        BpskChan &cc = h->chan[c];
+        cc.tuning = tuning_hz[c];
+        cc.tuPhaseInc = 2.0 * JPI * tuning_hz[c] / (double)rate;  // :196
+        cc.do_up = do_up ? do_up[c] != 0 : 0;
+        ok = cc.dev.alloc((size_t)h->max_batch + 26) == JSDR_OK;
+    }
+    if (ok) {
+        std::vector<double> t(514);  // cos[0..256], sin[0..256] with (1.0, 1.0) at 256: k_front_split's table
+        for (int k = 0; k < 256; k++) {
+            t[(size_t)k] = h->h_sincos[(size_t)k];
+            t[(size_t)(257 + k)] = h->h_sincos[(size_t)(256 + k)];
+        }
+        t[256] = 1.0;
+        t[513] = 1.0;
+        ok = hipMemcpy(h->sincos9.p, t.data(), sizeof(double) * 514, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    if (!ok) {
+        set_error("jsdr_bpsk_create_channels: device allocation failed (%d channels of %lld samples)", nchannels, (long long)h->max_batch);
+        jsdr_bpsk_destroy(h);
+        return JSDR_ERR;
+    }
+    h->tuning = h->chan[0].tuning;
+    h->tuPhaseInc = h->chan[0].tuPhaseInc;
+    h->do_up = h->chan[0].do_up;
+    *out = h;
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels)
+{
+    JSDR_REQUIRE(h && ninputs && nchannels, "jsdr_bpsk_channel_info: null argument");
+    *ninputs = h->nch > 0 ? h->nin : h->nstreams;
+    *nchannels = h->nch > 0 ? h->nch : 1;
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz)
+{
+    JSDR_REQUIRE(h, "jsdr_bpsk_set_channel_tuning: null handle");
+    if (h->nch == 0) {  // an ordinary handle is one channel
+        JSDR_REQUIRE(channel == 0, "jsdr_bpsk_set_channel_tuning: channel %d out of range (the handle has 1)", channel);
+        return jsdr_bpsk_set_tuning(h, tuning_hz);
+    }
+    JSDR_REQUIRE(channel >= 0, "jsdr_bpsk_set_channel_tuning: channel %d out of range (the handle has %d); the handle is unchanged",
+                 channel, h->nch);
+    return chan_apply(h, channel, &tuning_hz, nullptr, true, "jsdr_bpsk_set_channel_tuning");
+}
+
+int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up)
+{
+    JSDR_REQUIRE(h, "jsdr_bpsk_set_channel_mode: null handle");
+    if (h->nch == 0) {
+        JSDR_REQUIRE(channel == 0, "jsdr_bpsk_set_channel_mode: channel %d out of range (the handle has 1)", channel);
+        return jsdr_bpsk_set_mode(h, do_fft, do_up);
+    }
+    JSDR_REQUIRE(channel >= 0 && channel < h->nch, "jsdr_bpsk_set_channel_mode: channel %d out of range (the handle has %d); the handle "
+                 "is unchanged", channel, h->nch);
+    JSDR_REQUIRE(!do_fft, "jsdr_bpsk_set_channel_mode: a channel handle runs in the tune mode only; the handle is unchanged");
+    const int up = do_up != 0;
+    return chan_apply(h, channel, nullptr, &up, true, "jsdr_bpsk_set_channel_mode");
+}
+
+int jsdr_bpsk_get_channel_control(jsdr_bpsk *h, int channel, double *tuning_hz, int *do_fft, int *do_up)
+{
+    JSDR_REQUIRE(h && tuning_hz && do_fft && do_up, "jsdr_bpsk_get_channel_control: null argument");
+    if (h->nch == 0) {
+        JSDR_REQUIRE(channel == 0, "jsdr_bpsk_get_channel_control: channel %d out of range (the handle has 1)", channel);
+        return jsdr_bpsk_get_control(h, tuning_hz, do_fft, do_up);
+    }
+    JSDR_REQUIRE(channel >= 0 && channel < h->nch, "jsdr_bpsk_get_channel_control: channel %d out of range (the handle has %d)", channel,
+                 h->nch);
+    *tuning_hz = h->chan[channel].tuning;
+    *do_fft = 0;
+    *do_up = h->chan[channel].do_up;
     return JSDR_OK;
 }
 

@@ -1,0 +1,30 @@
+// bpsk_chan.h -- the channel handle's tune-mode front end (bpsk_chan.hip), launched from bpsk.hip.
+#pragma once
+#include "common.h"
+
+namespace jsdr {
+
+enum { CHAN_MAX = 16 };
+
+struct ChanFrontArgs {
+    const int *raw;                     // int16 pairs as dwords, [ninputs][stride_pairs]
+    long long stride_pairs;             // between inputs
+    int ic, qc;
+    const int2 *hist;                   // [ninputs][32]: the 26 inputs before this call, DC-corrected int16 pair (.x)
+    const unsigned short *k9[CHAN_MAX]; // per channel: 9-bit tuner index table (256: pass-through)
+    int per[CHAN_MAX];                  // per channel: period of k9 (entry (n + 26) mod per), or 0: k9[26 + n]
+    int nch;
+    const unsigned char *kvco;          // [nds] shared VCO table index
+    const double *sc9;                  // cos[0..256], sin[0..256], (1.0, 1.0) at 256
+    const double *ds_taps;              // [27]
+    double2 *dm;                        // [ninputs * nch][dm_stride]: 64 history + nds VCO-mixed samples
+    long long dm_stride;
+    long long nds;
+    int first_out;                      // input index whose arrival completes output 0
+    int decim;
+    int nout;                           // outputs per workgroup (set by the launcher)
+};
+
+int launch_chan_front(const ChanFrontArgs &a, int ninputs, hipStream_t st);
+
+}  // namespace jsdr
