@@ -772,6 +772,12 @@ class Demod:
                                           _addr(audio_dev), C.c_int64(audio_stride_i16), C.c_void_p(stream)),
                "jsdr_demod_batch_i16")
 
+    def batch_f32(self, iq_dev, stride_f32, nsamples, audio_dev, audio_stride_i16, stream=None):
+        """float IQ [S][stride_f32] (JavaAudio's (float)s/32767f frames, or any float) -> int16 audio, as batch_i16"""
+        _check(lib().jsdr_demod_batch_f32(self.h, _addr(iq_dev), C.c_int64(stride_f32), C.c_int64(nsamples),
+                                          _addr(audio_dev), C.c_int64(audio_stride_i16), C.c_void_p(stream)),
+               "jsdr_demod_batch_f32")
+
     def batch_host_i16(self, raw, nsamples, ic=0, qc=0):
         """raw: int16 [S][2*nsamples] on the host -> audio int16 [S][2*nsamples]"""
         raw = np.ascontiguousarray(raw, np.int16).reshape(self.S, 2 * nsamples)
