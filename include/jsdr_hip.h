@@ -352,6 +352,34 @@ int jsdr_demod_receive_f32(jsdr_demod *h, const float *buf_host, int16_t *audio_
 /* the reference's `max` / `avg` fields after the last frame of the last call (:465-467) */
 int jsdr_demod_frame_stats(jsdr_demod *h, int stream, float *max_out, float *avg_out);
 int jsdr_demod_state(jsdr_demod *h, float *car_out, float *phi_out);
+/* Channel handle: demod.java's controls each pick a channel out of the passband (the band-pass of weights(), the NCO at
+ * flo, filterMove, the mode / AGC / FIR / down-conversion switches, :184-218, 341-375); one handle of ninputs x nchannels
+ * receivers, each channel with its own controls.  Channel c of input i is stream i * nchannels + c.  1 <= nchannels <= 16;
+ * ninputs * nchannels and the frames per call obey jsdr_demod_create's limits.  Every channel starts as a new ordinary
+ * handle does (MODE_OFF, switches 0, flo = INT_MIN, fhi = INT_MAX, weights 0, car = phi = 0).  Each input is read and
+ * converted once for all its channels (k_demod_chan); results are bit-identical to nchannels ordinary handles fed the same
+ * input and given the same controls.
+ *   configure_channel: actionPerformed's mode / AGC / FIR / down-conversion change (:184-218) on that channel: fields only.
+ *   channel_weights: weights() (:341-375) for that channel: its delay line cleared on every input (after the handle's
+ *     pending calls, without waiting for the device) and, for a band-pass, phi set and car restarted at 0; the other
+ *     channels' rings, car and FM state carry on.  w_out / phi_out may be NULL.  filterMove's range check is the caller's.
+ *   get_channel: the controls now in effect; channel_state: that channel's car and phi.
+ *   configure / weights apply to every channel; state reports channel 0; frame_stats takes the stream i * nchannels + c.
+ *   batch_i16 / batch_f32: stream_stride is between INPUTS, audio_stride between the ninputs * nchannels output rows.
+ *   receive_f32 on a 1-input handle: one 2n-float frame in, nchannels 2n-sample frames out, channel c at c * 2n.
+ *   channel_info: an ordinary handle reports nstreams x 1 (and takes channel 0 in the per-channel calls).
+ *   The float rows of AM channels (of every channel, for frames above 10240 samples) are allocated when a call first
+ *     needs more of them than before: that call waits for the whole device once (a live switch to AM included).
+ * JSDR_ERR, every channel's controls and state as before the call: a channel out of range, a mode outside 0..4, a null
+ * handle or output pointer, nsamples not whole frames or above max_batch, strides too small, receive_f32 with ninputs > 1,
+ * bad create_channels arguments (checked before any device work).  Not covered: JNI / Java classes, jsdr_group. */
+int jsdr_demod_create_channels(jsdr_demod **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                               int64_t max_batch_samples);
+int jsdr_demod_channel_info(jsdr_demod *h, int *ninputs, int *nchannels);
+int jsdr_demod_configure_channel(jsdr_demod *h, int channel, int mode, int dofir, int dodwn, int doagc);
+int jsdr_demod_channel_weights(jsdr_demod *h, int channel, int flo, int fhi, float w_out[21], float *phi_out);
+int jsdr_demod_get_channel(jsdr_demod *h, int channel, int *mode, int *dofir, int *dodwn, int *doagc, int *flo, int *fhi);
+int jsdr_demod_channel_state(jsdr_demod *h, int channel, float *car_out, float *phi_out);
 /* per-kernel HIP-event timing of the batch calls (bench.py), as jsdr_bpsk_profile_* */
 int jsdr_demod_profile_enable(jsdr_demod *h, int on);
 int jsdr_demod_profile_count(void);

@@ -820,6 +820,72 @@ class Demod:
             pass
 
 
+class DemodChannels(Demod):
+    """`ninputs` inputs x `nchannels` independently controlled demod.receive channels (each its own band, NCO, mode and
+    switches).  Channel c of input i is stream i * nchannels + c; `frame_stats` takes that stream index."""
+
+    def __init__(self, rate=96000, n=2048, ninputs=1, nchannels=1, max_batch_samples=None):
+        self.rate, self.n, self.ninputs, self.nchannels = rate, n, ninputs, nchannels
+        self.S = ninputs * nchannels
+        self.max_batch = max_batch_samples or n
+        self.h = C.c_void_p()
+        _check(lib().jsdr_demod_create_channels(C.byref(self.h), rate, n, ninputs, nchannels, C.c_int64(self.max_batch)),
+               "jsdr_demod_create_channels")
+
+    def stream(self, inp, ch):
+        return inp * self.nchannels + ch
+
+    def channel_info(self):
+        a, b = C.c_int(), C.c_int()
+        _check(lib().jsdr_demod_channel_info(self.h, C.byref(a), C.byref(b)), "jsdr_demod_channel_info")
+        return a.value, b.value
+
+    def configure_channel(self, channel, mode, dofir=0, dodwn=0, doagc=0):
+        _check(lib().jsdr_demod_configure_channel(self.h, int(channel), int(mode), int(dofir), int(dodwn), int(doagc)),
+               "jsdr_demod_configure_channel")
+
+    def channel_weights(self, channel, flo, fhi):
+        w = np.empty(21, np.float32)
+        phi = C.c_float()
+        _check(lib().jsdr_demod_channel_weights(self.h, int(channel), int(flo), int(fhi), _addr(w), C.byref(phi)),
+               "jsdr_demod_channel_weights")
+        return w, np.float32(phi.value)
+
+    def channel_control(self, channel):
+        """(mode, dofir, dodwn, doagc, flo, fhi) of that channel"""
+        v = [C.c_int() for _ in range(6)]
+        _check(lib().jsdr_demod_get_channel(self.h, int(channel), *[C.byref(x) for x in v]), "jsdr_demod_get_channel")
+        return tuple(x.value for x in v)
+
+    def channel_state(self, channel):
+        car, phi = C.c_float(), C.c_float()
+        _check(lib().jsdr_demod_channel_state(self.h, int(channel), C.byref(car), C.byref(phi)), "jsdr_demod_channel_state")
+        return np.float32(car.value), np.float32(phi.value)
+
+    def batch_i16(self, raw_dev, input_stride_i16, nsamples, audio_dev, audio_stride_i16, ic=0, qc=0, stream=None):
+        """input_stride_i16: between INPUTS; audio_stride_i16: between the ninputs * nchannels output rows"""
+        super().batch_i16(raw_dev, input_stride_i16, nsamples, audio_dev, audio_stride_i16, ic, qc, stream)
+
+    def batch_f32(self, iq_dev, input_stride_f32, nsamples, audio_dev, audio_stride_i16, stream=None):
+        super().batch_f32(iq_dev, input_stride_f32, nsamples, audio_dev, audio_stride_i16, stream)
+
+    def batch_host_i16(self, raw, nsamples, ic=0, qc=0):
+        """raw: int16 [ninputs][2*nsamples] on the host -> audio int16 [ninputs][nchannels][2*nsamples]"""
+        raw = np.ascontiguousarray(raw, np.int16).reshape(self.ninputs, 2 * nsamples)
+        d_in = DeviceBuffer.from_host(raw)
+        d_out = DeviceBuffer(self.S * 2 * nsamples * 2)
+        self.batch_i16(d_in, 2 * nsamples, nsamples, d_out, 2 * nsamples, ic, qc)
+        return d_out.to_host(np.int16).reshape(self.ninputs, self.nchannels, 2 * nsamples)
+
+    def receive(self, buf):
+        """one frame (2n floats) of a 1-input handle -> int16 [nchannels][2n]"""
+        buf = np.ascontiguousarray(buf, np.float32)
+        assert buf.size == 2 * self.n
+        out = np.empty(self.nchannels * 2 * self.n, np.int16)
+        _check(lib().jsdr_demod_receive_f32(self.h, _addr(buf), _addr(out)), "jsdr_demod_receive_f32")
+        return out.reshape(self.nchannels, 2 * self.n)
+
+
 # ------------------------------------------------------------------ formats either side (SURVEY 8f next-4)
 class RecordingInfo(C.Structure):
     _fields_ = [("format", C.c_int), ("encoding", C.c_int), ("channels", C.c_int), ("rate", C.c_int),

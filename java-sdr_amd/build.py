@@ -30,6 +30,7 @@ SOURCES = {
     "synth.hip": [],
     "formats.hip": [],
     "demod.hip": ["-ffp-contract=off"],
+    "demod_chan.hip": ["-ffp-contract=off"],
     "bpsk.hip": ["-ffp-contract=off"],
     "bpsk_fft.hip": ["-ffp-contract=off"],
     # (no atomic optimiser: it turns the one-lane ticket atomicAdd into atomic + s_waitcnt vmcnt(0) + v_readfirstlane on the spot,

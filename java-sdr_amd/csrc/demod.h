@@ -1,0 +1,69 @@
+// demod.h -- what demod.hip (the ordinary handle and its kernels) and demod_chan.hip (the channel handle's kernels) share.
+#pragma once
+#include "common.h"
+
+namespace jsdr {
+
+enum { MODE_OFF = 0, MODE_RAW = 1, MODE_AM = 2, MODE_NFM = 3, MODE_WFM = 4 };  // demod.java:39-43
+constexpr int DHALO = 21;   // 20 older samples of the 21-tap filter + the FM detector's previous sample
+constexpr int DTILE = 2048;
+constexpr int DPER = DTILE / 256;  // 8 samples per thread and tile
+
+// LDS image of the tile's filter input: one pad slot per 8 so that the 8-sample lane stride of the blocked
+// filter walks distinct banks
+__device__ __forceinline__ int xpad8(int i) { return i + (i >> 3); }
+
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// Java's (int) of a float -- NaN -> 0, out of range saturates, else truncation -- is what v_cvt_i32_f32 does by
+// itself (C's (int) is undefined out of range, so the compiler may not assume it: spelled out, the three cases
+// cost five more instructions per sample)
+__device__ __forceinline__ int demod_f2i(float v)
+{
+    int r;
+    asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(v));
+    return r;
+}
+
+// (short)(sam * 32767f) to both channels (:478-481): the low half of the int, twice
+__device__ __forceinline__ int demod_lr(float x) { const int sv = demod_f2i(x * 32767.0f); return (int)__builtin_amdgcn_perm((unsigned)sv, (unsigned)sv, 0x01000100u); }
+
+// ---- channel handles (jsdr_demod_create_channels): ninputs x K receivers, channel c of input i is stream i * K + c
+enum { DCHAN_MAX = 16 };
+
+struct DemodChanConst {
+    float w[21];
+    float fmgain;
+    int mode, dofir, dodwn, doagc;
+    int nco_row;  // row of the call's carrier table (dodwn)
+    int dslot;    // slot of this channel's float rows in d (AM, or every channel of a long frame); -1: none
+};
+
+struct DemodChanArgs {
+    const int *raw;            // int16 pairs [ninputs][stride_pairs]
+    const float2 *rawf;        // or float pairs
+    long long stride_pairs;    // between INPUTS
+    long long L;               // samples per input in this call
+    int n, nfr, ic, qc;
+    int ninputs, K;
+    const float2 *hist;        // [ninputs * K][21] filter input before the call
+    const float2 *lilq;        // [ninputs * K] FM detector state before the call
+    const float2 *nco;         // [rows][nco_pitch] (cos, sin) of each distinct carrier table
+    long long nco_pitch;
+    float *d;                  // [dslots * ninputs][L], row dslot * ninputs + i
+    unsigned *fmax_bits;       // [dslots * ninputs][nfr]
+    int *out;                  // int16 (L,R) pairs, row i * K + c
+    long long out_stride_pairs;
+    float *stats;              // [ninputs * K][nfr] (max, avg)
+    int slot_chan[DCHAN_MAX];  // channel of each dslot
+    DemodChanConst c[DCHAN_MAX];
+};
+
+// k_demod_chan (frames of up to 5 tiles: one workgroup per frame of one input) or k_demod_chan_front (one per tile, every
+// channel to d); then k_demod_chan_state
+int launch_demod_chan(const DemodChanArgs &a, bool f32in, bool fused, hipStream_t st);
+int launch_demod_chan_state(const DemodChanArgs &a, bool f32in, float2 *hist_new, float2 *lilq_new, hipStream_t st);
+// the AM mean subtraction / AGC / int16 output of the d rows (favg: k_demod_mean's result for the AM rows)
+int launch_demod_chan_out(const DemodChanArgs &a, int drows, const float *favg, hipStream_t st);
+
+}  // namespace jsdr

@@ -16,15 +16,14 @@
 // Kernels: k_demod_front (raw -> demodulated float per sample + per-frame max), k_demod_mean (AM only),
 // k_demod_out (-> int16 L,R), k_demod_state (history for the next call), k_demod_nco.
 #include "common.h"
+#include "demod.h"
 #include <math.h>
 #include <stdlib.h>
+#include <thread>
 #include <vector>
 
 namespace jsdr {
 
-enum { MODE_OFF = 0, MODE_RAW = 1, MODE_AM = 2, MODE_NFM = 3, MODE_WFM = 4 };  // demod.java:39-43
-constexpr int DHALO = 21;   // 20 older samples of the 21-tap filter + the FM detector's previous sample
-constexpr int DTILE = 2048;
 
 struct DemodConst {
     float w[21];
@@ -83,12 +82,6 @@ __device__ __forceinline__ float2 demod_mixed_at(const DemodConst &c, const floa
     return v;
 }
 
-// LDS image of the tile's filter input: one pad slot per 8 so that the 8-sample lane stride of the blocked
-// filter below walks distinct banks
-__device__ __forceinline__ int xpad8(int i) { return i + (i >> 3); }
-
-typedef float v2f __attribute__((ext_vector_type(2)));
-
 // the sample just before the tile: xs[xpad8(20)] is x(g0 - 1)
 __device__ __forceinline__ float2 demod_mixed(const DemodConst &c, const float2 *xs, const float2 *nco, long long g)
 {
@@ -99,7 +92,6 @@ __device__ __forceinline__ float2 demod_mixed(const DemodConst &c, const float2 
 // windows overlap, so 28 LDS reads feed 8 outputs (3.5 per sample instead of 21), and I/Q ride in one packed
 // register pair: acc = acc + x*w is v_pk_mul_f32 + v_pk_add_f32, each half rounded separately exactly like the
 // reference's two scalar statements (:388-389).
-constexpr int DPER = DTILE / 256;  // 8 samples per thread and tile
 constexpr int DXS = DTILE + DHALO + (DTILE + DHALO) / 8 + 1;
 
 // tile j of frame f of stream s -> this thread's 8 detected samples dv[] (sam[s] after :441-462) and the running
@@ -298,19 +290,6 @@ __global__ __launch_bounds__(256) void k_demod_front(DemodArgs a)
     const unsigned mx = demod_block_max(mbits, red);
     if (tid == 0) atomicMax(&a.fmax_bits[(long long)s * a.nfr + f], mx);
 }
-
-// Java's (int) of a float -- NaN -> 0, out of range saturates, else truncation -- is what v_cvt_i32_f32 does by
-// itself (C's (int) is undefined out of range, so the compiler may not assume it: spelled out, the three cases
-// cost five more instructions per sample)
-__device__ __forceinline__ int demod_f2i(float v)
-{
-    int r;
-    asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(v));
-    return r;
-}
-
-// (short)(sam * 32767f) to both channels (:478-481): the low half of the int, twice
-__device__ __forceinline__ int demod_lr(float x) { const int sv = demod_f2i(x * 32767.0f); return (int)__builtin_amdgcn_perm((unsigned)sv, (unsigned)sv, 0x01000100u); }
 
 // Every mode but AM, frames of at most NT tiles: one workgroup per frame keeps the detected samples in registers,
 // takes the frame maximum itself and writes the int16 audio (:465-481) -- no float round trip through HBM and no
@@ -551,11 +530,27 @@ struct jsdr_demod {
     };
     std::vector<Rec> recs;
     std::vector<hipEvent_t> pool;
+    // channel handles (jsdr_demod_create_channels): nstreams = nin * nch, channel c of input i is stream i * nch + c; every
+    // channel has its own controls and carrier phase (the handle-wide fields above are unused)
+    bool chan = false;
+    int nin = 0, nch = 1;
+    struct Chan {
+        int mode = MODE_OFF, dofir = 0, dodwn = 0, doagc = 0;
+        int flo = (-2147483647 - 1), fhi = 2147483647;
+        float w[21] = {0};
+        float phi = 0.0f, car = 0.0f;
+    };
+    std::vector<Chan> ch;
+    long long nco_pitch = 0;   // entries between two carrier tables of a set
+    DevBuf<float> dch;         // [dslots * nin][L] float rows (AM channels; every channel of a frame above 5 tiles)
+    hipEvent_t ev_done = nullptr, ev_clear = nullptr;  // end of the last call; a channel ring cleared after it
+    bool done_any = false, clear_pending = false;
 };
 
-enum { DK_NCO = 0, DK_FRONT, DK_STATE, DK_MEAN, DK_OUT, DK_COUNT };
+enum { DK_NCO = 0, DK_FRONT, DK_STATE, DK_MEAN, DK_OUT, DK_CHAN, DK_COUNT };
+// (DK_CHAN: every launch of a channel handle but the shared k_demod_nco / k_demod_mean)
 static const char *const kDemodKernels[DK_COUNT] = {"k_demod_nco", "k_demod_front", "k_demod_state", "k_demod_mean",
-                                                    "k_demod_out"};
+                                                    "k_demod_out", "k_demod_chan"};
 struct DemodProf {
     jsdr_demod *h;
     hipStream_t st;
@@ -591,6 +586,34 @@ struct DemodProf {
 
 static double dsinl(double x) { return (double)sinl((long double)x); }
 static double dcosl(double x) { return (double)cosl((long double)x); }
+
+// demod.weights() (:341-375) for the band [flo, fhi] at `rate` into w; a band-pass (false for flo = INT_MIN, the all-pass
+// impulse) also sets phi
+static bool demod_weights_of(int rate, int flo, int fhi, float w[21], float *phi)
+{
+    const int len = 21;
+    if ((-2147483647 - 1) == flo) {
+        for (int i = 0; i < len; i++) w[i] = 0;
+        w[(len - 1) / 2] = 1;
+        return false;
+    }
+    const float frate = (float)rate;
+    const float nlo = (float)flo / frate;
+    const float nhi = (float)fhi / frate;
+    const int ord = len - 1;
+    const double PI = 3.14159265358979323846;
+    for (int n = 0; n < len; n++) {
+        if (n == ord / 2) {
+            w[n] = 2.0f * (nhi - nlo);
+        } else {
+            w[n] = (float)((dsinl(2 * PI * nhi * (double)(n - ord / 2)) / (PI * (double)(n - ord / 2))) -
+                           (dsinl(2 * PI * nlo * (double)(n - ord / 2)) / (PI * (double)(n - ord / 2))));
+        }
+        w[n] *= (float)(0.54 - 0.46 * dcosl(2 * PI * (double)n / (double)ord));
+    }
+    *phi = (float)(2 * PI * nlo);
+    return true;
+}
 
 template <bool F32IN>
 static int demod_run(jsdr_demod *h, const int16_t *raw_dev, const float *rawf_dev, int64_t stride_i16, int64_t L, int ic,
@@ -711,6 +734,196 @@ static int demod_run(jsdr_demod *h, const int16_t *raw_dev, const float *rawf_de
     return JSDR_OK;
 }
 
+// one call of a channel handle: stride_i16 between INPUTS, audio_stride_i16 between the nin * nch output rows
+template <bool F32IN>
+static int demod_chan_run(jsdr_demod *h, const int16_t *raw_dev, const float *rawf_dev, int64_t stride_i16, int64_t L, int ic,
+                          int qc, int16_t *audio_dev, int64_t audio_stride_i16, hipStream_t st)
+{
+    JSDR_REQUIRE((raw_dev || rawf_dev) && audio_dev, "demod: null buffer");
+    JSDR_REQUIRE(L > 0 && L <= h->max_batch && L % h->n == 0,
+                 "demod: nsamples=%lld must be a positive multiple of the frame (%d) and at most max_batch_samples=%lld",
+                 (long long)L, h->n, h->max_batch);
+    JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nin == 1 || stride_i16 >= 2 * L) && (audio_stride_i16 & 1) == 0 &&
+                     (h->nstreams == 1 || audio_stride_i16 >= 2 * L),
+                 "demod: input or output row stride too small for %lld samples", (long long)L);
+    const int K = h->nch;
+    const int nfr = (int)(L / h->n);
+    const bool fused = (h->n + DTILE - 1) / DTILE <= 5;
+    DemodChanArgs a = {};
+    // float rows in d: the AM channels (their mean needs the whole frame), then, for frames above 5 tiles, every other one
+    int nslots = 0;
+    for (int c = 0; c < K; c++) {
+        a.c[c].dslot = -1;
+        if (h->ch[c].mode == MODE_AM) {
+            a.c[c].dslot = nslots;
+            a.slot_chan[nslots++] = c;
+        }
+    }
+    const int nam = nslots;
+    if (!fused)
+        for (int c = 0; c < K; c++)
+            if (h->ch[c].mode != MODE_AM) {
+                a.c[c].dslot = nslots;
+                a.slot_chan[nslots++] = c;
+            }
+    const int drows = nslots * h->nin;
+    if ((size_t)drows * (size_t)L > h->dch.n) {
+        JSDR_HIP_TRY(hipDeviceSynchronize());  // earlier calls may still use the smaller buffer
+        if (h->dch.alloc((size_t)drows * (size_t)L) != JSDR_OK) return JSDR_ERR;
+    }
+    // distinct carrier tables: one per (car, phi) among the down-converting channels
+    int rows = 0;
+    uint32_t key[DCHAN_MAX][2];
+    for (int c = 0; c < K; c++) {
+        a.c[c].nco_row = 0;
+        if (!h->ch[c].dodwn) continue;
+        uint32_t k2[2];
+        memcpy(&k2[0], &h->ch[c].car, 4);
+        memcpy(&k2[1], &h->ch[c].phi, 4);
+        int r = 0;
+        while (r < rows && (key[r][0] != k2[0] || key[r][1] != k2[1])) r++;
+        if (r == rows) {
+            key[r][0] = k2[0];
+            key[r][1] = k2[1];
+            rows++;
+        }
+        a.c[c].nco_row = r;
+    }
+    const int set = (int)(h->calls++ & 1);
+    if (rows) {
+        if (h->used[set]) JSDR_HIP_TRY(hipEventSynchronize(h->ev_used[set]));  // the call before last has let go of this set
+        float endcar[DCHAN_MAX];
+        // :427-429 in float, exactly as demod_run steps it; one host thread per distinct table
+        auto build = [&](int r) {
+            float *tab = h->car_pinned[set] + (size_t)r * h->nco_pitch;
+            float car, phi;
+            memcpy(&car, &key[r][0], 4);
+            memcpy(&phi, &key[r][1], 4);
+            const float two_pi = (float)(2 * 3.14159265358979323846);
+            for (int64_t g = 0; g < L; g++) {
+                tab[g] = car;
+                car -= phi;
+                if (__builtin_expect(car < 0.0f, 0)) {
+                    asm volatile("" : "+x"(car));
+                    car += two_pi;
+                }
+            }
+            endcar[r] = car;
+        };
+        if (rows == 1 || L < 65536) {  // (a thread start costs more than a short table)
+            for (int r = 0; r < rows; r++) build(r);
+        } else {
+            std::vector<std::thread> th;
+            for (int r = 0; r < rows; r++) th.emplace_back(build, r);
+            for (auto &t : th) t.join();
+        }
+        for (int c = 0; c < K; c++)
+            if (h->ch[c].dodwn) h->ch[c].car = endcar[a.c[c].nco_row];
+        const long long cnt = (long long)(rows - 1) * h->nco_pitch + L;
+        JSDR_HIP_TRY(hipMemcpyAsync(h->car_dev[set].p, h->car_pinned[set], sizeof(float) * (size_t)cnt, hipMemcpyHostToDevice,
+                                    h->copy_stream));
+        {
+            DemodProf ps(h, DK_NCO, h->copy_stream);
+            hipLaunchKernelGGL(k_demod_nco, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->copy_stream, h->car_dev[set].p,
+                               cnt, h->nco[set].p);
+            JSDR_LAUNCH_CHECK();
+        }
+        JSDR_HIP_TRY(hipEventRecord(h->ev_table[set], h->copy_stream));
+        JSDR_HIP_TRY(hipStreamWaitEvent(st, h->ev_table[set], 0));
+    }
+    if (h->clear_pending) {  // a channel's ring cleared since the last call
+        JSDR_HIP_TRY(hipStreamWaitEvent(st, h->ev_clear, 0));
+        h->clear_pending = false;
+    }
+    a.raw = reinterpret_cast<const int *>(raw_dev);
+    a.rawf = reinterpret_cast<const float2 *>(rawf_dev);
+    a.stride_pairs = stride_i16 / 2;
+    a.L = L;
+    a.n = h->n;
+    a.nfr = nfr;
+    a.ic = ic;
+    a.qc = qc;
+    a.ninputs = h->nin;
+    a.K = K;
+    a.hist = h->hist[h->cur].p;
+    a.lilq = h->lilq[h->cur].p;
+    a.nco = h->nco[set].p;
+    a.nco_pitch = h->nco_pitch;
+    a.d = h->dch.p;
+    a.fmax_bits = h->fmax.p;
+    a.out = reinterpret_cast<int *>(audio_dev);
+    a.out_stride_pairs = audio_stride_i16 / 2;
+    a.stats = h->stats.p;
+    for (int c = 0; c < K; c++) {
+        const jsdr_demod::Chan &ch = h->ch[c];
+        memcpy(a.c[c].w, ch.w, sizeof(a.c[c].w));
+        a.c[c].fmgain = (float)h->rate / (MODE_NFM == ch.mode ? 5000.0f : 75000.0f);  // :410
+        a.c[c].mode = ch.mode;
+        a.c[c].dofir = ch.dofir;
+        a.c[c].dodwn = ch.dodwn;
+        a.c[c].doagc = ch.doagc;
+    }
+    if (!fused) JSDR_HIP_TRY(hipMemsetAsync(h->fmax.p, 0, sizeof(unsigned) * (size_t)drows * nfr, st));
+    {
+        DemodProf ps(h, DK_CHAN, st);
+        if (launch_demod_chan(a, F32IN, fused, st) != JSDR_OK) return JSDR_ERR;
+    }
+    {
+        DemodProf ps(h, DK_CHAN, st);
+        if (launch_demod_chan_state(a, F32IN, h->hist[h->cur ^ 1].p, h->lilq[h->cur ^ 1].p, st) != JSDR_OK) return JSDR_ERR;
+    }
+    h->cur ^= 1;
+    if (nam) {
+        const long long nft = (long long)nam * h->nin * nfr;  // the AM rows come first
+        DemodProf ps(h, DK_MEAN, st);
+        hipLaunchKernelGGL(k_demod_mean, dim3((unsigned)((nft + 63) / 64)), dim3(64), 0, st, h->dch.p, (long long)L, h->n, nfr,
+                           nft, h->favg.p);
+        JSDR_LAUNCH_CHECK();
+    }
+    if (drows) {
+        DemodProf ps(h, DK_CHAN, st);
+        if (launch_demod_chan_out(a, drows, h->favg.p, st) != JSDR_OK) return JSDR_ERR;
+    }
+    if (rows) {
+        JSDR_HIP_TRY(hipEventRecord(h->ev_used[set], st));
+        h->used[set] = true;
+    }
+    JSDR_HIP_TRY(hipEventRecord(h->ev_done, st));
+    h->done_any = true;
+    h->last_nfr = nfr;
+    return JSDR_OK;
+}
+
+// receive(float[]) of a 1-input channel handle: one frame in, nch frames of audio out (channel c at c * 2n)
+static int demod_chan_receive(jsdr_demod *h, const float *buf_host, int16_t *audio_host)
+{
+    JSDR_REQUIRE(h->nin == 1, "jsdr_demod_receive_f32: the frame-by-frame form needs a 1-input handle");
+    const size_t in_bytes = sizeof(float) * 2 * (size_t)h->n, out_bytes = sizeof(int) * (size_t)h->n * h->nch;
+    if (!h->pin_tried) {
+        h->pin.alloc(in_bytes + out_bytes);
+        h->pin_tried = true;
+    }
+    if (h->pin.p) {
+        memcpy(h->pin.p, buf_host, in_bytes);
+        SyncOnExit guard;
+        JSDR_HIP_TRY(hipMemcpyAsync(h->stage_in.p, h->pin.p, in_bytes, hipMemcpyHostToDevice, 0));
+        if (demod_chan_run<true>(h, nullptr, h->stage_in.p, 2 * (int64_t)h->n, h->n, 0, 0,
+                                 reinterpret_cast<int16_t *>(h->stage_out.p), 2 * (int64_t)h->n, 0) != JSDR_OK)
+            return JSDR_ERR;
+        JSDR_HIP_TRY(hipMemcpyAsync(h->pin.p + in_bytes, h->stage_out.p, out_bytes, hipMemcpyDeviceToHost, 0));
+        JSDR_HIP_TRY(hipStreamSynchronize(0));
+        guard.armed = false;
+        memcpy(audio_host, h->pin.p + in_bytes, out_bytes);
+        return JSDR_OK;
+    }
+    JSDR_HIP_TRY(hipMemcpy(h->stage_in.p, buf_host, in_bytes, hipMemcpyHostToDevice));
+    if (demod_chan_run<true>(h, nullptr, h->stage_in.p, 2 * (int64_t)h->n, h->n, 0, 0, reinterpret_cast<int16_t *>(h->stage_out.p),
+                             2 * (int64_t)h->n, 0) != JSDR_OK)
+        return JSDR_ERR;
+    JSDR_HIP_TRY(hipMemcpy(audio_host, h->stage_out.p, out_bytes, hipMemcpyDeviceToHost));
+    return JSDR_OK;
+}
+
 extern "C" {
 
 int jsdr_demod_create(jsdr_demod **out, int rate, int nsamples_per_frame, int nstreams, int64_t max_batch_samples)
@@ -776,6 +989,9 @@ int jsdr_demod_destroy(jsdr_demod *h)
     h->fmax.release();
     h->stage_in.release();
     h->stage_out.release();
+    h->dch.release();
+    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
+    if (h->ev_clear) (void)hipEventDestroy(h->ev_clear);
     for (auto &r : h->recs) {
         (void)hipEventDestroy(r.a);
         (void)hipEventDestroy(r.b);
@@ -817,6 +1033,12 @@ int jsdr_demod_configure(jsdr_demod *h, int mode, int dofir, int dodwn, int doag
 {
     JSDR_REQUIRE(h, "jsdr_demod_configure: null handle");
     JSDR_REQUIRE(mode >= MODE_OFF && mode <= MODE_WFM, "jsdr_demod_configure: mode %d outside 0..4 (demod.java:39-43)", mode);
+    for (auto &c : h->ch) {  // a channel handle: every channel
+        c.mode = mode;
+        c.dofir = dofir != 0;
+        c.dodwn = dodwn != 0;
+        c.doagc = doagc != 0;
+    }
     h->mode = mode;
     h->dofir = dofir != 0;
     h->dodwn = dodwn != 0;
@@ -828,30 +1050,28 @@ int jsdr_demod_configure(jsdr_demod *h, int mode, int dofir, int dodwn, int doag
 int jsdr_demod_weights(jsdr_demod *h, int flo, int fhi, float w_out[21], float *phi_out)
 {
     JSDR_REQUIRE(h, "jsdr_demod_weights: null handle");
-    const int len = 21;
+    if (h->chan) {  // every channel
+        float w[21], phi = 0.0f;
+        const bool bandpass = demod_weights_of(h->rate, flo, fhi, w, &phi);
+        for (auto &c : h->ch) {
+            c.flo = flo;
+            c.fhi = fhi;
+            memcpy(c.w, w, sizeof(w));
+            if (bandpass) {
+                c.phi = phi;
+                c.car = 0.0f;
+            }
+        }
+        JSDR_HIP_TRY(hipDeviceSynchronize());
+        if (h->hist[0].zero() != JSDR_OK || h->hist[1].zero() != JSDR_OK) return JSDR_ERR;
+        JSDR_HIP_TRY(hipDeviceSynchronize());
+        if (w_out) memcpy(w_out, w, sizeof(w));
+        if (phi_out) *phi_out = h->ch[0].phi;
+        return JSDR_OK;
+    }
     h->flo = flo;
     h->fhi = fhi;
-    if ((-2147483647 - 1) == flo) {
-        for (int i = 0; i < len; i++) h->wfir[i] = 0;
-        h->wfir[(len - 1) / 2] = 1;
-    } else {
-        const float rate = (float)h->rate;
-        const float nlo = (float)flo / rate;
-        const float nhi = (float)fhi / rate;
-        const int ord = len - 1;
-        const double PI = 3.14159265358979323846;
-        for (int n = 0; n < len; n++) {
-            if (n == ord / 2) {
-                h->wfir[n] = 2.0f * (nhi - nlo);
-            } else {
-                h->wfir[n] = (float)((dsinl(2 * PI * nhi * (double)(n - ord / 2)) / (PI * (double)(n - ord / 2))) -
-                                     (dsinl(2 * PI * nlo * (double)(n - ord / 2)) / (PI * (double)(n - ord / 2))));
-            }
-            h->wfir[n] *= (float)(0.54 - 0.46 * dcosl(2 * PI * (double)n / (double)ord));
-        }
-        h->phi = (float)(2 * PI * nlo);
-        h->car = 0.0f;
-    }
+    if (demod_weights_of(h->rate, flo, fhi, h->wfir, &h->phi)) h->car = 0.0f;
     JSDR_HIP_TRY(hipDeviceSynchronize());
     if (h->hist[0].zero() != JSDR_OK || h->hist[1].zero() != JSDR_OK) return JSDR_ERR;
     JSDR_HIP_TRY(hipDeviceSynchronize());
@@ -863,6 +1083,9 @@ int jsdr_demod_weights(jsdr_demod *h, int flo, int fhi, float w_out[21], float *
 int jsdr_demod_batch_i16(jsdr_demod *h, const int16_t *raw_dev, int64_t stream_stride_i16, int64_t nsamples, int ic, int qc,
                          int16_t *audio_dev, int64_t audio_stride_i16, void *stream)
 {
+    if (h && h->chan)
+        return demod_chan_run<false>(h, raw_dev, nullptr, stream_stride_i16, nsamples, ic, qc, audio_dev, audio_stride_i16,
+                                     as_stream(stream));
     return demod_run<false>(h, raw_dev, nullptr, stream_stride_i16, nsamples, ic, qc, audio_dev, audio_stride_i16,
                             as_stream(stream));
 }
@@ -870,6 +1093,9 @@ int jsdr_demod_batch_i16(jsdr_demod *h, const int16_t *raw_dev, int64_t stream_s
 int jsdr_demod_batch_f32(jsdr_demod *h, const float *iq_dev, int64_t stream_stride_f32, int64_t nsamples, int16_t *audio_dev,
                          int64_t audio_stride_i16, void *stream)
 {
+    if (h && h->chan)
+        return demod_chan_run<true>(h, nullptr, iq_dev, stream_stride_f32, nsamples, 0, 0, audio_dev, audio_stride_i16,
+                                    as_stream(stream));
     return demod_run<true>(h, nullptr, iq_dev, stream_stride_f32, nsamples, 0, 0, audio_dev, audio_stride_i16,
                            as_stream(stream));
 }
@@ -878,6 +1104,7 @@ int jsdr_demod_batch_f32(jsdr_demod *h, const float *iq_dev, int64_t stream_stri
 int jsdr_demod_receive_f32(jsdr_demod *h, const float *buf_host, int16_t *audio_host)
 {
     JSDR_REQUIRE(h && buf_host && audio_host, "jsdr_demod_receive_f32: null argument");
+    if (h->chan) return demod_chan_receive(h, buf_host, audio_host);
     JSDR_REQUIRE(h->nstreams == 1, "jsdr_demod_receive_f32: the frame-by-frame form needs a 1-stream handle");
     const size_t in_bytes = sizeof(float) * 2 * (size_t)h->n, out_bytes = sizeof(int) * (size_t)h->n;
     if (!h->pin_tried) {  // the first receive() of the handle (PinnedStage, common.h)
@@ -922,8 +1149,127 @@ int jsdr_demod_frame_stats(jsdr_demod *h, int stream, float *max_out, float *avg
 int jsdr_demod_state(jsdr_demod *h, float *car_out, float *phi_out)
 {
     JSDR_REQUIRE(h, "jsdr_demod_state: null handle");
-    if (car_out) *car_out = h->car;
-    if (phi_out) *phi_out = h->phi;
+    if (car_out) *car_out = h->chan ? h->ch[0].car : h->car;  // a channel handle: channel 0
+    if (phi_out) *phi_out = h->chan ? h->ch[0].phi : h->phi;
+    return JSDR_OK;
+}
+
+int jsdr_demod_create_channels(jsdr_demod **out, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                               int64_t max_batch_samples)
+{
+    JSDR_REQUIRE(out, "jsdr_demod_create_channels: null handle pointer");
+    *out = nullptr;
+    JSDR_REQUIRE(rate > 0 && nsamples_per_frame > 0, "jsdr_demod_create_channels: rate and nsamples_per_frame must be positive");
+    JSDR_REQUIRE(ninputs >= 1, "jsdr_demod_create_channels: ninputs = %d, at least 1", ninputs);
+    JSDR_REQUIRE(nchannels >= 1 && nchannels <= DCHAN_MAX, "jsdr_demod_create_channels: nchannels = %d outside 1..%d", nchannels,
+                 (int)DCHAN_MAX);
+    if (max_batch_samples <= 0) max_batch_samples = nsamples_per_frame;
+    JSDR_REQUIRE(max_batch_samples % nsamples_per_frame == 0, "jsdr_demod_create_channels: max_batch_samples must be whole frames");
+    const long long S = (long long)ninputs * nchannels, nf = max_batch_samples / nsamples_per_frame;
+    JSDR_REQUIRE(S <= 65535, "jsdr_demod_create_channels: ninputs * nchannels = %lld streams, at most 65535", S);
+    JSDR_REQUIRE(nf <= 65535, "jsdr_demod_create_channels: max_batch_samples is %lld frames, at most 65535", nf);
+    JSDR_REQUIRE(S * nf < (1LL << 31) && nf * ((nsamples_per_frame + DTILE - 1) / DTILE) < (1LL << 31),
+                 "jsdr_demod_create_channels: batch too large");
+    jsdr_demod *h = new jsdr_demod();
+    h->chan = true;
+    h->rate = rate;
+    h->n = nsamples_per_frame;
+    h->nin = ninputs;
+    h->nch = nchannels;
+    h->nstreams = (int)S;
+    h->max_batch = max_batch_samples;
+    h->ch.resize((size_t)nchannels);
+    h->nco_pitch = (max_batch_samples + 8 + 1) & ~1LL;  // even: every table 16-byte aligned; spare slots past each
+    const size_t tab = (size_t)nchannels * (size_t)h->nco_pitch, nfs = (size_t)S * (size_t)nf;
+    bool ok = true;
+    for (int k = 0; k < 2; k++)
+        ok = ok && h->hist[k].alloc((size_t)S * DHALO) == JSDR_OK && h->lilq[k].alloc((size_t)S) == JSDR_OK &&
+             h->hist[k].zero() == JSDR_OK && h->lilq[k].zero() == JSDR_OK;
+    for (int k = 0; k < 2; k++)
+        ok = ok && h->nco[k].alloc(tab) == JSDR_OK && h->nco[k].zero() == JSDR_OK && h->car_dev[k].alloc(tab) == JSDR_OK &&
+             hipHostMalloc(reinterpret_cast<void **>(&h->car_pinned[k]), sizeof(float) * tab, hipHostMallocDefault) == hipSuccess &&
+             hipEventCreateWithFlags(&h->ev_table[k], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&h->ev_used[k], hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) == hipSuccess &&
+         hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) == hipSuccess &&
+         hipEventCreateWithFlags(&h->ev_clear, hipEventDisableTiming) == hipSuccess;
+    ok = ok && h->favg.alloc(nfs) == JSDR_OK && h->stats.alloc(2 * nfs) == JSDR_OK && h->fmax.alloc(nfs) == JSDR_OK &&
+         h->stage_in.alloc(2 * (size_t)h->n) == JSDR_OK && h->stage_out.alloc((size_t)h->n * nchannels) == JSDR_OK &&
+         h->favg.zero() == JSDR_OK && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        jsdr_demod_destroy(h);
+        return JSDR_ERR;
+    }
+    *out = h;
+    return JSDR_OK;
+}
+
+int jsdr_demod_channel_info(jsdr_demod *h, int *ninputs, int *nchannels)
+{
+    JSDR_REQUIRE(h && ninputs && nchannels, "jsdr_demod_channel_info: null argument");
+    *ninputs = h->chan ? h->nin : h->nstreams;
+    *nchannels = h->chan ? h->nch : 1;
+    return JSDR_OK;
+}
+
+#define DEMOD_CHANNEL_OK(fn)                                                                                                   \
+    JSDR_REQUIRE(h, fn ": null handle");                                                                                       \
+    JSDR_REQUIRE(channel >= 0 && channel < (h->chan ? h->nch : 1), fn ": channel %d outside 0..%d", channel,                 \
+                 (h->chan ? h->nch : 1) - 1)
+
+int jsdr_demod_configure_channel(jsdr_demod *h, int channel, int mode, int dofir, int dodwn, int doagc)
+{
+    DEMOD_CHANNEL_OK("jsdr_demod_configure_channel");
+    JSDR_REQUIRE(mode >= MODE_OFF && mode <= MODE_WFM, "jsdr_demod_configure_channel: mode %d outside 0..4 (demod.java:39-43)", mode);
+    if (!h->chan) return jsdr_demod_configure(h, mode, dofir, dodwn, doagc);
+    jsdr_demod::Chan &c = h->ch[channel];
+    c.mode = mode;
+    c.dofir = dofir != 0;
+    c.dodwn = dodwn != 0;
+    c.doagc = doagc != 0;
+    return JSDR_OK;
+}
+
+// weights() for one channel: its ring cleared on every input after the handle's pending calls (the next call waits for
+// that, nothing else does); the other channels carry on
+int jsdr_demod_channel_weights(jsdr_demod *h, int channel, int flo, int fhi, float w_out[21], float *phi_out)
+{
+    DEMOD_CHANNEL_OK("jsdr_demod_channel_weights");
+    if (!h->chan) return jsdr_demod_weights(h, flo, fhi, w_out, phi_out);
+    jsdr_demod::Chan c = h->ch[channel];
+    c.flo = flo;
+    c.fhi = fhi;
+    if (demod_weights_of(h->rate, flo, fhi, c.w, &c.phi)) c.car = 0.0f;
+    if (h->done_any) JSDR_HIP_TRY(hipStreamWaitEvent(h->copy_stream, h->ev_done, 0));
+    JSDR_HIP_TRY(hipMemset2DAsync(h->hist[h->cur].p + (size_t)channel * DHALO, sizeof(float2) * DHALO * (size_t)h->nch, 0,
+                                  sizeof(float2) * DHALO, (size_t)h->nin, h->copy_stream));
+    JSDR_HIP_TRY(hipEventRecord(h->ev_clear, h->copy_stream));
+    h->clear_pending = true;
+    h->ch[channel] = c;
+    if (w_out) memcpy(w_out, c.w, sizeof(c.w));
+    if (phi_out) *phi_out = c.phi;
+    return JSDR_OK;
+}
+
+int jsdr_demod_get_channel(jsdr_demod *h, int channel, int *mode, int *dofir, int *dodwn, int *doagc, int *flo, int *fhi)
+{
+    DEMOD_CHANNEL_OK("jsdr_demod_get_channel");
+    JSDR_REQUIRE(mode && dofir && dodwn && doagc && flo && fhi, "jsdr_demod_get_channel: null argument");
+    if (!h->chan) {
+        *mode = h->mode, *dofir = h->dofir, *dodwn = h->dodwn, *doagc = h->doagc, *flo = h->flo, *fhi = h->fhi;
+        return JSDR_OK;
+    }
+    const jsdr_demod::Chan &c = h->ch[channel];
+    *mode = c.mode, *dofir = c.dofir, *dodwn = c.dodwn, *doagc = c.doagc, *flo = c.flo, *fhi = c.fhi;
+    return JSDR_OK;
+}
+
+int jsdr_demod_channel_state(jsdr_demod *h, int channel, float *car_out, float *phi_out)
+{
+    DEMOD_CHANNEL_OK("jsdr_demod_channel_state");
+    JSDR_REQUIRE(car_out && phi_out, "jsdr_demod_channel_state: null argument");
+    *car_out = h->chan ? h->ch[channel].car : h->car;
+    *phi_out = h->chan ? h->ch[channel].phi : h->phi;
     return JSDR_OK;
 }
 
