@@ -232,10 +232,38 @@ int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
  *     apply to every channel; get_control reports channel 0.
  *   channel_info: an ordinary handle reports nstreams x 1 (and takes channel 0 in the per-channel calls).
  * JSDR_ERR, the handle unchanged: do_fft = 1 in set_mode / set_channel_mode / reconfigure, set_variant(FAST), snapshot_read
- * when nchannels > 1, a channel out of range, a non-finite tuning; float input through batch calls.  Not covered:
- * FFT-acquire channels, the FAST variant, jsdr_group, JNI / Java classes, a per-channel snapshot. */
+ * when nchannels > 1, a channel out of range, a non-finite tuning; float input through batch calls.  Not covered on this
+ * handle: FFT-acquire channels (jsdr_bpsk_create_mode_channels below has them), the FAST variant, jsdr_group, JNI / Java
+ * classes, a per-channel snapshot. */
 int jsdr_bpsk_create_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
                               const double *tuning_hz, const int *do_up, int64_t max_batch_samples);
+/* Channel handle whose channels are each in the tune mode or in FFT-acquire ("FFT/Tune", FUNcubeBPSKDemod.java:180-186),
+ * fixed at creation: do_fft[c] (may be NULL: every channel in the tune mode), each FFT-acquire channel searching its own
+ * half of the band, do_up[c] ("Track high", :183-189).  Streams, getters, pack_slots, the slot layout, receive_* and the
+ * per-channel calls are jsdr_bpsk_create_channels'; handles from that creator keep every refusal they have.
+ *   Tune-mode channels behave exactly as there.  FFT-acquire channels follow doBufferFFT (:406-464): the tuner never
+ *     runs (tuPhase stands still, tuning is stored and reported), state doubles 6 / 7 (avePeakPower, aveCentreBin) and
+ *     counter centreBin are live for their streams and 0 for the others.  Results are bit-identical to an ordinary handle
+ *     created with that (tuning, do_fft, do_up) and fed the same calls.
+ *   The forward half of doBufferFFT (conversion, forward transform, |X|; :416-427) runs once per INPUT and frame, whatever
+ *     the number of FFT-acquire channels: frames of 1024 .. 8192 samples (2^k) in one transform that serves both bands,
+ *     every other frame once per band in use (at most twice).  A handle whose FFT-acquire channels all search one band
+ *     pays nothing for the other.  jsdr_bpsk_acq_last_launch: the frames transformed forward and the frames inverted by
+ *     the last call (inverted: inputs x FFT-acquire channels x frames).
+ *   With at least one FFT-acquire channel every call is whole frames, and the frame must be one FFT-acquire takes (416
+ *     samples and more).  Frames other than 2^k of 1024 .. 8192 and 9600 / 4800 / 4410 -- 19200 among them, and the other
+ *     frames an ordinary handle runs through its fused kernels -- take the any-frame passes.
+ *   set_channel_mode(c, do_fft, do_up): do_fft must equal the channel's creation mode; do_up on an FFT-acquire channel is
+ *     "Track high": the band changes from the next call, centreBin, avePeakPower, aveCentreBin and everything else carry
+ *     on, dmMaxCorr = 0 on that channel (also when do_up is the current value), other channels untouched.  set_mode /
+ *     reconfigure take a do_fft that changes no channel's mode (so none at all on a handle with both kinds).
+ * JSDR_ERR, the handle unchanged: a change of a channel's do_fft by any route, a call that is not whole frames,
+ * set_variant(FAST), snapshot_read when nchannels > 1, a channel out of range, a non-finite tuning -- all checked before
+ * any device work.  Not covered: switching a channel between the modes live, the FAST variant, jsdr_group, JNI / Java
+ * classes, a per-channel snapshot. */
+int jsdr_bpsk_create_mode_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                                   const double *tuning_hz, const int *do_fft, const int *do_up, int64_t max_batch_samples);
+int jsdr_bpsk_acq_last_launch(jsdr_bpsk *h, int64_t *fwd_frames, int64_t *inv_frames);
 int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels);
 int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz);
 int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up);

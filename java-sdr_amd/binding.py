@@ -614,7 +614,9 @@ class BpskChannels(Bpsk):
     """`ninputs` inputs x len(tunings) independently tuned FUNcubeBPSKDemod instances (jsdr.java:479-483's nfcs tabs fed the
     same audio).  Channel c of input i is stream i * nchannels + c; every getter takes (input, channel)."""
 
-    def __init__(self, rate, blen, tunings, do_up=None, ninputs=1, max_batch_samples=None, size=4):
+    def __init__(self, rate, blen, tunings, do_up=None, ninputs=1, max_batch_samples=None, size=4, do_fft=None):
+        """do_fft (per channel, fixed at creation): the channels that run FFT-acquire, each searching the band its do_up names
+        (jsdr_bpsk_create_mode_channels); None: jsdr_bpsk_create_channels, every channel in the tune mode"""
         tunings = [float(t) for t in tunings]
         self.samples = blen // size
         self.ninputs = ninputs
@@ -624,8 +626,20 @@ class BpskChannels(Bpsk):
         self.h = C.c_void_p()
         tu = (C.c_double * max(self.nchannels, 1))(*tunings)
         up = None if do_up is None else (C.c_int * max(self.nchannels, 1))(*[int(v) for v in do_up])
+        if do_fft is not None:
+            ff = (C.c_int * max(self.nchannels, 1))(*[int(v) for v in do_fft])
+            _check(lib().jsdr_bpsk_create_mode_channels(C.byref(self.h), rate, self.samples, ninputs, self.nchannels,
+                                                        tu if tunings else None, ff, up, C.c_int64(self.max_batch)),
+                   "jsdr_bpsk_create_mode_channels")
+            return
         _check(lib().jsdr_bpsk_create_channels(C.byref(self.h), rate, self.samples, ninputs, self.nchannels, tu if tunings else None,
                                                up, C.c_int64(self.max_batch)), "jsdr_bpsk_create_channels")
+
+    def acq_last_launch(self):
+        """(frames transformed forward, frames inverted) by the last call's FFT-acquire channels"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(lib().jsdr_bpsk_acq_last_launch(self.h, C.byref(a), C.byref(b)), "jsdr_bpsk_acq_last_launch")
+        return a.value, b.value
 
     def stream(self, inp, ch):
         return inp * self.nchannels + ch

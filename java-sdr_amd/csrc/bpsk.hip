@@ -2468,6 +2468,7 @@ struct Schedule {
 struct BpskChan {
     double tuning = 0.0, tuPhase = 0.0, tuPhaseInc = 0.0;
     int do_up = 0;
+    int do_fft = 0;                  // jsdr_bpsk_create_mode_channels: the channel runs FFT-acquire (fixed at creation)
     unsigned short khist[26] = {0};  // indices of the 26 samples before the next call
     // the schedule last computed for this channel, keyed by the state it started from
     bool valid = false;
@@ -2650,13 +2651,28 @@ struct jsdr_bpsk {
     double v_vco0 = 0.0, v_vco1 = 0.0;
     int v_ds0 = 0, v_ds1 = 0;
     long long v_L = -1;
+    // jsdr_bpsk_create_mode_channels: every channel in the tune mode or in FFT-acquire, fixed at creation.  nfftch of them run
+    // FFT-acquire (bpsk_acq_chan.hip); fft_state is then CHANNEL-major, [nch][nin]
+    bool mode_chan = false;
+    int nfftch = 0;
+    long long acq_fwd_frames = 0, acq_inv_frames = 0;  // jsdr_bpsk_acq_last_launch
 };
 
+// whether a stream runs FFT-acquire (state doubles 6 / 7 and counter centreBin are live), and where its FftFrontState sits
+static bool stream_fft(const jsdr_bpsk *h, int stream)
+{
+    return h->nch > 0 ? (h->nfftch > 0 && h->chan[stream % h->nch].do_fft != 0) : h->do_fft != 0;
+}
+static size_t fft_state_at(const jsdr_bpsk *h, int stream)
+{
+    return h->nch > 0 ? (size_t)(stream % h->nch) * (size_t)h->nin + (size_t)(stream / h->nch) : (size_t)stream;
+}
+
 enum { PK_FRONT = 0, PK_HIST, PK_MATCHED, PK_DMHIST, PK_TAIL, PK_SYNC, PK_SYNCFIN, PK_FEC, PK_FM, PK_SYNCT, PK_PREP,
-       PK_ACQ_FWD, PK_ACQ_SCAN, PK_ACQ_INV, PK_ACQ_EDGES, PK_COUNT };
+       PK_ACQ_FWD, PK_ACQ_SCAN, PK_ACQ_INV, PK_ACQ_EDGES, PK_ACQC_FWD, PK_COUNT };
 static const char *const kProfNames[PK_COUNT] = {"k_front", "k_hist_in", "k_matched", "k_dm_history", "k_tail", "k_sync",
                                                  "k_sync_fin", "k_fec_bpsk", "k_fm", "k_sync_t", "k_fm_prep",
-                                                 "k_acq_fwd", "k_acq_scan", "k_acq_inv", "k_acq_edges"};
+                                                 "k_acq_fwd", "k_acq_scan", "k_acq_inv", "k_acq_edges", "k_acqc_fwd"};
 
 static hipEvent_t prof_event(jsdr_bpsk *h)
 {
@@ -2694,7 +2710,7 @@ struct ProfScope {
 // the three-phase front end's launches (bpsk_acq.hip) under the same timing scopes
 struct AcqProfCtx {
     jsdr_bpsk *h;
-    hipEvent_t a[4];
+    hipEvent_t a[5];  // (phase 4: the channel handle's both-band forward kernel)
 };
 static void acq_prof_mark(void *ctx, int phase, bool begin, hipStream_t st)
 {
@@ -3221,7 +3237,7 @@ static int run_side(jsdr_bpsk *h, const SideJob &j)
             add(h->fec_last.p, sp->last, 2 * sizeof(int));
             add(h->cnt_dec.p, &sp->cdec, sizeof(int));
             add(h->nbits.p, &sp->nbits, sizeof(int));
-            if (h->do_fft) {
+            if (stream_fft(h, 0)) {
                 add(&h->fft_state.p->centreBin, &sp->centreBin, sizeof(int));
                 add(&h->fft_state.p->avePeakPower, &sp->avePeakPower, 2 * sizeof(double));  // avePeakPower, aveCentreBin
             }
@@ -3299,6 +3315,7 @@ static void chan_schedules(jsdr_bpsk *h, long long L, bool first, bool *fresh)
     for (int c = 0; c < h->nch; c++) {
         BpskChan &ch = h->chan[c];
         fresh[c] = false;
+        if (ch.do_fft) continue;  // doBufferFFT never runs the tuner (:406-464): tuPhase stands still
         if (ch.valid && ch.k_L == L && ch.k_first == first && ch.k_tu0 == ch.tuPhase && ch.k_inc == ch.tuPhaseInc &&
             memcmp(ch.k_hist0, ch.khist, sizeof(ch.khist)) == 0)
             continue;
@@ -3332,6 +3349,7 @@ static void chan_schedules(jsdr_bpsk *h, long long L, bool first, bool *fresh)
     }
     for (int c = 0; c < h->nch; c++) {
         BpskChan &ch = h->chan[c];
+        if (ch.do_fft) continue;
         ch.tuPhase = ch.tu1;
         memcpy(ch.khist, ch.khist1, sizeof(ch.khist));
     }
@@ -3378,6 +3396,33 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     JSDR_REQUIRE(L > 0 && L <= h->max_batch, "bpsk: nsamples=%lld outside (0, max_batch_samples=%lld]", L, h->max_batch);
     JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nin == 1 || stride_i16 >= 2 * L),
                  "bpsk channels: input stride %lld too small for %lld samples", stride_i16, L);
+    JSDR_REQUIRE(h->nfftch == 0 || (L % h->nsf) == 0, "bpsk channels: a handle with FFT-acquire channels needs whole frames (%lld %% %d != 0); "
+                 "the handle is unchanged", L, h->nsf);
+    if (h->nfftch > 0 && !h->acq_scratch.p) {
+        // the one step of the call that can fail for want of memory comes before anything of the handle has moved on
+        int mask = 0;
+        for (int c = 0; c < h->nch; c++)
+            if (h->chan[c].do_fft) mask |= h->chan[c].do_up ? 2 : 1;
+        const size_t per = acq3c_frame_bytes(h->nsf, mask, h->gen_plan.on);
+        {
+            // per INPUT and frame, for the largest call the handle takes, capped (JSDR_ACQ_SCRATCH_MB, default 6 GiB): longer calls
+            // go in several launches of acq_chunk frames per input
+            long long cap_mb = 6144;
+            if (const char *e = knob("JSDR_ACQ_SCRATCH_MB")) cap_mb = atoll(e) > 0 ? atoll(e) : cap_mb;
+            long long fmax = h->max_batch / h->nsf;
+            if (fmax < 1) fmax = 1;
+            long long chunk = (cap_mb << 20) / (long long)(per * (size_t)h->nin);
+            if (chunk < 1) chunk = 1;
+            if (chunk > fmax) chunk = fmax;
+            if (const char *e = knob("JSDR_ACQ_CHUNK")) chunk = atoll(e) > 0 && atoll(e) < chunk ? atoll(e) : chunk;
+            if (h->acq_scratch.alloc(per * (size_t)h->nin * (size_t)chunk + 4096) != JSDR_OK) return JSDR_ERR;
+            h->acq_chunk = (int)chunk;
+            int dev = 0, cus = 0;
+            JSDR_HIP_TRY(hipGetDevice(&dev));
+            JSDR_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+            h->num_cu = cus > 0 ? cus : 256;
+        }
+    }
     const int first_out = h->decim - 1 - h->dsCnt;
     const long long g_first = h->n_ds;
     const bool first = h->n_in == 0;
@@ -3398,7 +3443,61 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     }
     const int S = h->nstreams;
     const int *raw = reinterpret_cast<const int *>(raw_dev);
-    if (nds > 0) {
+    if (h->nfftch > 0 && vfresh && nds > 0) {
+        // the VCO factors of the call's outputs, the one table the FFT-acquire front end reads (:515-516)
+        h->h_vco_cs.resize((size_t)nds);
+        for (long long j = 0; j < nds; j++)
+            h->h_vco_cs[(size_t)j] = make_double2(h->h_sincos[h->h_kvco[(size_t)j]], h->h_sincos[256 + h->h_kvco[(size_t)j]]);
+        if (h2d_call(h, h->vco_cs.p, h->h_vco_cs.data(), sizeof(double2) * (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
+    }
+    if (h->nfftch > 0) {
+        // the FFT-acquire channels: one forward phase per input, scan / inverse / edges per channel (bpsk_acq_chan.hip)
+        AcqChanArgs ca;
+        ca.nin = h->nin;
+        ca.nch = h->nch;
+        for (int c = 0; c < h->nch; c++) {
+            if (!h->chan[c].do_fft) continue;
+            ca.chan[ca.nfft] = c;
+            ca.up[ca.nfft] = h->chan[c].do_up;
+            ca.nfft++;
+        }
+        ca.st = h->fft_state.p;
+        FftFrontArgs xa;
+        xa.raw = raw;
+        xa.rawf = nullptr;
+        xa.stride_pairs = stride_i16 / 2;
+        xa.nframes = (int)(L / h->nsf);
+        xa.n = h->nsf;
+        xa.logn = h->logn;
+        xa.ic = ic;
+        xa.qc = qc;
+        xa.do_up = 0;
+        xa.decim = h->decim;
+        xa.first_out = first_out;
+        xa.vco_cs = h->vco_cs.p;
+        xa.tw = h->fft_tw.p;
+        xa.st = h->fft_state.p;
+        xa.dm = h->dm.p;
+        xa.dm_stride = h->dm_stride;
+        xa.nds = nds;
+        xa.ds_taps = h->ds_taps_dev.p;
+        xa.phase_clk = nullptr;
+        AcqmPlan plan;
+        plan.np = h->fm_np;
+        plan.rad = h->fm_rad;
+        plan.tw_off = h->fm_off;
+        plan.wr_off = h->fm_off1;
+        AcqProfCtx pc{h, {nullptr, nullptr, nullptr, nullptr, nullptr}};
+        AcqProf prof;
+        prof.ctx = &pc;
+        prof.mark = acq_prof_mark;
+        if (launch_acq3_chan(xa, ca, h->acq_scratch.p, h->acq_scratch.n, h->acq_chunk, h->num_cu, st, prof, plan, &h->gen_plan) != JSDR_OK)
+            return JSDR_ERR;
+        h->acq_fwd_frames = ca.fwd_frames;
+        h->acq_inv_frames = ca.inv_frames;
+        h->front_name = ca.fwd_name;
+    }
+    if (nds > 0 && h->nfftch < h->nch) {
         ChanFrontArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.raw = raw;
@@ -3406,11 +3505,14 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         fa.ic = ic;
         fa.qc = qc;
         fa.hist = h->hist_in[h->hist_cur].p;
-        for (int c = 0; c < h->nch; c++) {
-            fa.k9[c] = h->chan[c].dev.p;
-            fa.per[c] = h->chan[c].per;
+        for (int c = 0; c < h->nch; c++) {  // the tune-mode channels (all of them, but on a handle with FFT-acquire channels)
+            if (h->chan[c].do_fft) continue;
+            fa.k9[fa.nch] = h->chan[c].dev.p;
+            fa.per[fa.nch] = h->chan[c].per;
+            fa.chan_of[fa.nch] = c;
+            fa.nch++;
         }
-        fa.nch = h->nch;
+        fa.nch_all = h->nch;
         fa.kvco = h->kvco.p;
         fa.sc9 = h->sincos9.p;
         fa.ds_taps = h->ds_taps_dev.p;
@@ -3420,7 +3522,7 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         fa.first_out = first_out;
         fa.decim = h->decim;
         ProfScope ps(h, PK_FRONT, st);
-        h->front_name = "k_chan_front";
+        if (h->nfftch == 0) h->front_name = "k_chan_front";
         if (launch_chan_front(fa, h->nin, st) != JSDR_OK) return JSDR_ERR;
     }
     {
@@ -3761,7 +3863,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
             plan.rad = h->fm_rad;
             plan.tw_off = h->fm_off;
             plan.wr_off = h->fm_off1;
-            AcqProfCtx pc{h, {nullptr, nullptr, nullptr, nullptr}};
+            AcqProfCtx pc{h, {nullptr, nullptr, nullptr, nullptr, nullptr}};
             AcqProf prof;
             prof.ctx = &pc;
             prof.mark = acq_prof_mark;
@@ -4622,8 +4724,9 @@ __global__ void k_snapshot_pack(SnapPack *out, const TailState *st, const int *f
     for (int k = i; k < 512; k += blockDim.x) out->bits[k] = k < nb ? bits_new[k] : (signed char)0;
 }
 
-static void counters_from(const jsdr_bpsk *h, const TailState &t, const int last[2], int cdec, int centreBin, int32_t *out)
+static void counters_from(const jsdr_bpsk *h, const TailState &t, const int last[2], int cdec, int centreBin, int32_t *out, int stream = 0)
 {
+    const bool fft = stream_fft(h, stream);
     out[0] = (int32_t)h->n_in;
     out[1] = (int32_t)h->n_ds;
     out[2] = t.cntBit;
@@ -4633,11 +4736,12 @@ static void counters_from(const jsdr_bpsk *h, const TailState &t, const int last
     out[6] = t.dmCorr;
     out[7] = t.dmMaxCorr;
     out[8] = last[1];
-    out[9] = h->do_fft ? centreBin : 0;
+    out[9] = fft ? centreBin : 0;
 }
 
-static void state_from(const jsdr_bpsk *h, const TailState &t, double avePeakPower, double aveCentreBin, double *out)
+static void state_from(const jsdr_bpsk *h, const TailState &t, double avePeakPower, double aveCentreBin, double *out, int stream = 0)
 {
+    const bool fft = stream_fft(h, stream);
     out[0] = h->tuPhase;
     out[1] = h->vcoPhase;
     // dmBitPhase (:501,:581-584): k steps of +1/9600 from 0.0 within the current bit, replayed exactly
@@ -4647,8 +4751,8 @@ static void state_from(const jsdr_bpsk *h, const TailState &t, double avePeakPow
     out[3] = t.dmEnergyOut;
     out[4] = t.energy1;
     out[5] = t.energy2;
-    out[6] = h->do_fft ? avePeakPower : 0.0;
-    out[7] = h->do_fft ? aveCentreBin : 0.0;
+    out[6] = fft ? avePeakPower : 0.0;
+    out[7] = fft ? aveCentreBin : 0.0;
     for (int i = 0; i < 8; i++) out[8 + i] = t.dmEnergy[i];
     out[16] = t.lastI;
     out[17] = t.lastQ;
@@ -4660,7 +4764,7 @@ static int publish_snapshot(jsdr_bpsk *h)
     hipStream_t ts = (h->overlap && h->tail_stream) ? h->tail_stream : h->last_stream;
     if (!h->snap_fused) {
         hipLaunchKernelGGL(k_snapshot_pack, dim3(1), dim3(256), 0, ts, h->snap_dev.p, h->tail.p, h->fec_last.p, h->cnt_dec.p,
-                           h->nbits.p, h->do_fft ? h->fft_state.p : (const FftFrontState *)nullptr, h->decoded.p,
+                           h->nbits.p, stream_fft(h, 0) ? h->fft_state.p : (const FftFrontState *)nullptr, h->decoded.p,
                            h->bitlog[h->bitlog_cur].p + HIST_BITS);
         JSDR_LAUNCH_CHECK();
     }
@@ -4671,7 +4775,7 @@ static int publish_snapshot(jsdr_bpsk *h)
     if (sync_last(h) != JSDR_OK) return JSDR_ERR;
     JSDR_HIP_TRY(hipStreamSynchronize(ts));
     if (h->snap_fused) {  // what k_snapshot_pack does on the device: no FFT state in tune mode, no bytes beyond the call's bits
-        if (!h->do_fft) {
+        if (!stream_fft(h, 0)) {
             pkp->centreBin = 0;
             pkp->avePeakPower = 0.0;
             pkp->aveCentreBin = 0.0;
@@ -4743,12 +4847,12 @@ int jsdr_bpsk_get_counters(jsdr_bpsk *h, int stream, int32_t out[JSDR_BPSK_NCOUN
     JSDR_HIP_TRY(hipMemcpy(&cdec, h->cnt_dec.p + stream, sizeof(int), hipMemcpyDeviceToHost));
     if (check_overflow(h, stream, "jsdr_bpsk_get_counters") != JSDR_OK) return JSDR_ERR;
     int centreBin = 0;
-    if (h->do_fft) {
+    if (stream_fft(h, stream)) {
         FftFrontState fs;
-        JSDR_HIP_TRY(hipMemcpy(&fs, h->fft_state.p + stream, sizeof(fs), hipMemcpyDeviceToHost));
+        JSDR_HIP_TRY(hipMemcpy(&fs, h->fft_state.p + fft_state_at(h, stream), sizeof(fs), hipMemcpyDeviceToHost));
         centreBin = fs.centreBin;
     }
-    counters_from(h, t, last, cdec, centreBin, out);
+    counters_from(h, t, last, cdec, centreBin, out, stream);
     return JSDR_OK;
 }
 
@@ -4827,13 +4931,13 @@ int jsdr_bpsk_get_state(jsdr_bpsk *h, int stream, double out[18])
     TailState t;
     JSDR_HIP_TRY(hipMemcpy(&t, h->tail.p + stream, sizeof(t), hipMemcpyDeviceToHost));
     double app = 0.0, acb = 0.0;
-    if (h->do_fft) {
+    if (stream_fft(h, stream)) {
         FftFrontState fs;
-        JSDR_HIP_TRY(hipMemcpy(&fs, h->fft_state.p + stream, sizeof(fs), hipMemcpyDeviceToHost));
+        JSDR_HIP_TRY(hipMemcpy(&fs, h->fft_state.p + fft_state_at(h, stream), sizeof(fs), hipMemcpyDeviceToHost));
         app = fs.avePeakPower;
         acb = fs.aveCentreBin;
     }
-    state_from(h, t, app, acb, out);
+    state_from(h, t, app, acb, out, stream);
     if (h->nch > 0) out[0] = h->chan[stream % h->nch].tuPhase;
     return JSDR_OK;
 }
@@ -5004,14 +5108,16 @@ int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who)
 
 // the FFT-acquire buffers of a handle created in the tune mode, allocated and zeroed at its first switch (as jsdr_bpsk_create
 // sets them up for do_fft, and Java's field initialisers, :403-405), and the scratch of the tune -> FFT seam.  All or nothing.
-static int fft_mode_alloc(jsdr_bpsk *h)
+// chan_form (jsdr_bpsk_create_mode_channels): a channel handle has the three-phase front ends only, so every frame that is not one of
+// theirs (2^k of 1024 .. 8192 at a decimation of 4 and more, 9600 / 4800 / 4410) takes the any-frame passes' plan.
+static int fft_mode_alloc(jsdr_bpsk *h, bool chan_form = false)
 {
     const int n = h->nsf;
     const size_t S = (size_t)h->nstreams;
     const long long stride2 = 64 + n / h->decim + 2 + 64;
     if (h->fft_ready && h->fft_state2.p && h->dm2.p) return JSDR_OK;
     const bool pow2 = n >= 1024 && n <= 8192 && (n & (n - 1)) == 0;
-    const bool gen = !(fftm_supported(n) || (h->decim >= 4 && (pow2 || fft2x_supported(n))));
+    const bool gen = chan_form ? !((pow2 && h->decim >= 4) || acqm_supported(n)) : !(fftm_supported(n) || (h->decim >= 4 && (pow2 || fft2x_supported(n))));
     const bool f2x = !gen && !pow2 && fft2x_supported(n);
     DevBuf<FftFrontState> st, st2;
     DevBuf<double2> tw, vcs, ek, dm2;
@@ -5137,6 +5243,12 @@ static int chan_apply(jsdr_bpsk *h, int ch, const double *tuning, const int *do_
         }
         if (do_up) cc.do_up = *do_up;
     }
+    if (do_up && h->nfftch > 0 && h->acq_scratch.p) {
+        // the three-phase scratch is cut for the bands in use ("Track high" on an FFT-acquire channel may change them): allocated
+        // again at the next call
+        h->acq_scratch.release();
+        h->acq_chunk = 0;
+    }
     h->tuning = h->chan[0].tuning;
     h->tuPhaseInc = h->chan[0].tuPhaseInc;
     h->do_up = h->chan[0].do_up;
@@ -5158,7 +5270,11 @@ int jsdr_bpsk_set_mode(jsdr_bpsk *h, int do_fft, int do_up)
 {
     if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_set_mode") != JSDR_OK) return JSDR_ERR;
     if (h->nch > 0) {
-        JSDR_REQUIRE(!do_fft, "jsdr_bpsk_set_mode: a channel handle runs in the tune mode only; the handle is unchanged");
+        if (h->mode_chan)
+            for (int c = 0; c < h->nch; c++)
+                JSDR_REQUIRE((do_fft != 0) == (h->chan[c].do_fft != 0), "jsdr_bpsk_set_mode: channel %d was created in %s; a channel's "
+                             "mode is fixed at creation; the handle is unchanged", c, h->chan[c].do_fft ? "FFT-acquire" : "the tune mode");
+        JSDR_REQUIRE(h->mode_chan || !do_fft, "jsdr_bpsk_set_mode: a channel handle runs in the tune mode only; the handle is unchanged");
         const int up = do_up != 0;
         return chan_apply(h, -1, nullptr, &up, true, "jsdr_bpsk_set_mode");
     }
@@ -5171,7 +5287,11 @@ int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
     if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
     JSDR_REQUIRE(std::isfinite(tuning_hz), "jsdr_bpsk_reconfigure: tuning %g Hz is not finite", tuning_hz);
     if (h->nch > 0) {
-        JSDR_REQUIRE(!do_fft, "jsdr_bpsk_reconfigure: a channel handle runs in the tune mode only; the handle is unchanged");
+        if (h->mode_chan)
+            for (int c = 0; c < h->nch; c++)
+                JSDR_REQUIRE((do_fft != 0) == (h->chan[c].do_fft != 0), "jsdr_bpsk_reconfigure: channel %d was created in %s; a channel's "
+                             "mode is fixed at creation; the handle is unchanged", c, h->chan[c].do_fft ? "FFT-acquire" : "the tune mode");
+        JSDR_REQUIRE(h->mode_chan || !do_fft, "jsdr_bpsk_reconfigure: a channel handle runs in the tune mode only; the handle is unchanged");
         const int up = do_up != 0;
         return chan_apply(h, -1, &tuning_hz, &up, false, "jsdr_bpsk_reconfigure");
     }
@@ -5183,7 +5303,7 @@ int jsdr_bpsk_get_control(jsdr_bpsk *h, double *tuning_hz, int *do_fft, int *do_
 {
     JSDR_REQUIRE(h && tuning_hz && do_fft && do_up, "jsdr_bpsk_get_control: null argument");
     *tuning_hz = h->tuning;
-    *do_fft = h->do_fft;
+    *do_fft = h->nch > 0 ? h->chan[0].do_fft : h->do_fft;  // (a channel handle reports channel 0)
     *do_up = h->do_up;
     return JSDR_OK;
 }
@@ -5239,6 +5359,57 @@ int jsdr_bpsk_create_channels(jsdr_bpsk **out, int rate, int nsamples_per_frame,
     return JSDR_OK;
 }
 
+int jsdr_bpsk_create_mode_channels(jsdr_bpsk **out, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                                   const double *tuning_hz, const int *do_fft, const int *do_up, int64_t max_batch_samples)
+{
+    JSDR_REQUIRE(out, "jsdr_bpsk_create_mode_channels: null handle pointer");
+    *out = nullptr;
+    // every check before any device work
+    JSDR_REQUIRE(nchannels >= 1 && nchannels <= CHAN_MAX, "jsdr_bpsk_create_mode_channels: nchannels %d outside 1 .. %d", nchannels, (int)CHAN_MAX);
+    JSDR_REQUIRE(ninputs >= 1 && (long long)ninputs * nchannels <= 65535, "jsdr_bpsk_create_mode_channels: %d inputs x %d channels", ninputs,
+                 nchannels);
+    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_create_mode_channels: null tuning array");
+    for (int c = 0; c < nchannels; c++)
+        JSDR_REQUIRE(std::isfinite(tuning_hz[c]), "jsdr_bpsk_create_mode_channels: tuning of channel %d (%g Hz) is not finite", c, tuning_hz[c]);
+    JSDR_REQUIRE(rate >= 1 && nsamples_per_frame > 0, "jsdr_bpsk_create_mode_channels: rate %d, frame of %d samples", rate, nsamples_per_frame);
+    int nfft = 0;
+    for (int c = 0; c < nchannels; c++) nfft += (do_fft && do_fft[c]) ? 1 : 0;
+    if (nfft > 0) {
+        // the three-phase front ends' own frames, or any frame the any-frame passes take
+        const int n = nsamples_per_frame, decim = rate / 9600 > 0 ? rate / 9600 : 1;
+        const bool pow2 = n >= 1024 && n <= 8192 && (n & (n - 1)) == 0;
+        JSDR_REQUIRE((pow2 && decim >= 4) || acqm_supported(n) || acqg_supported(n), "jsdr_bpsk_create_mode_channels: an FFT-acquire channel "
+                     "needs a frame of 416 .. 4194304 samples whose prime factors r above 7 keep n r within 2^31 (got %d): below 416 the 204 "
+                     "gathered bins (FUNcubeBPSKDemod.java:458) do not end inside the frame", n);
+    }
+    jsdr_bpsk *h = nullptr;
+    if (jsdr_bpsk_create_channels(&h, rate, nsamples_per_frame, ninputs, nchannels, tuning_hz, do_up, max_batch_samples) != JSDR_OK) return JSDR_ERR;
+    h->mode_chan = true;
+    if (nfft > 0) {
+        // the FFT-acquire buffers as a live switch of an ordinary handle allocates them: state zeroed (Java's field initialisers,
+        // :403-405), twiddles and plan of the frame, the VCO factors' table
+        if (fft_mode_alloc(h, true) != JSDR_OK) {
+            jsdr_bpsk_destroy(h);
+            return JSDR_ERR;
+        }
+        h->fft_state2.release();  // (the tune <-> FFT seam's scratch: a channel's mode never changes)
+        h->dm2.release();
+        for (int c = 0; c < nchannels; c++) h->chan[c].do_fft = do_fft[c] ? 1 : 0;
+        h->nfftch = nfft;
+        h->max_batch = (h->max_batch / nsamples_per_frame) * nsamples_per_frame;  // calls are whole frames
+    }
+    *out = h;
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_acq_last_launch(jsdr_bpsk *h, int64_t *fwd_frames, int64_t *inv_frames)
+{
+    JSDR_REQUIRE(h && fwd_frames && inv_frames, "jsdr_bpsk_acq_last_launch: null argument");
+    *fwd_frames = h->acq_fwd_frames;
+    *inv_frames = h->acq_inv_frames;
+    return JSDR_OK;
+}
+
 int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels)
 {
     JSDR_REQUIRE(h && ninputs && nchannels, "jsdr_bpsk_channel_info: null argument");
@@ -5268,7 +5439,10 @@ int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up)
     }
     JSDR_REQUIRE(channel >= 0 && channel < h->nch, "jsdr_bpsk_set_channel_mode: channel %d out of range (the handle has %d); the handle "
                  "is unchanged", channel, h->nch);
-    JSDR_REQUIRE(!do_fft, "jsdr_bpsk_set_channel_mode: a channel handle runs in the tune mode only; the handle is unchanged");
+    if (h->mode_chan)
+        JSDR_REQUIRE((do_fft != 0) == (h->chan[channel].do_fft != 0), "jsdr_bpsk_set_channel_mode: channel %d was created in %s; a "
+                     "channel's mode is fixed at creation; the handle is unchanged", channel, h->chan[channel].do_fft ? "FFT-acquire" : "the tune mode");
+    JSDR_REQUIRE(h->mode_chan || !do_fft, "jsdr_bpsk_set_channel_mode: a channel handle runs in the tune mode only; the handle is unchanged");
     const int up = do_up != 0;
     return chan_apply(h, channel, nullptr, &up, true, "jsdr_bpsk_set_channel_mode");
 }
@@ -5283,7 +5457,7 @@ int jsdr_bpsk_get_channel_control(jsdr_bpsk *h, int channel, double *tuning_hz, 
     JSDR_REQUIRE(channel >= 0 && channel < h->nch, "jsdr_bpsk_get_channel_control: channel %d out of range (the handle has %d)", channel,
                  h->nch);
     *tuning_hz = h->chan[channel].tuning;
-    *do_fft = 0;
+    *do_fft = h->chan[channel].do_fft;
     *do_up = h->chan[channel].do_up;
     return JSDR_OK;
 }

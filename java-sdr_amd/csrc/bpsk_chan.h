@@ -13,7 +13,9 @@ struct ChanFrontArgs {
     const int2 *hist;                   // [ninputs][32]: the 26 inputs before this call, DC-corrected int16 pair (.x)
     const unsigned short *k9[CHAN_MAX]; // per channel: 9-bit tuner index table (256: pass-through)
     int per[CHAN_MAX];                  // per channel: period of k9 (entry (n + 26) mod per), or 0: k9[26 + n]
-    int nch;
+    int nch;                            // channels this launch takes ...
+    int nch_all;                        // ... of the handle's channels per input: stream = input * nch_all + chan_of[c]
+    int chan_of[CHAN_MAX];              // (a handle whose channels are all in the tune mode: nch_all = nch, chan_of[c] = c)
     const unsigned char *kvco;          // [nds] shared VCO table index
     const double *sc9;                  // cos[0..256], sin[0..256], (1.0, 1.0) at 256
     const double *ds_taps;              // [27]

@@ -90,7 +90,7 @@ __global__ __launch_bounds__(CHAN_THREADS) void k_chan_front(ChanFrontArgs a)
             const int c = c0 + u;
             if (c < a.nch) {
                 const double oi = fi[u] * HOWARD, oq = fq[u] * HOWARD;  // :486
-                a.dm[((long long)in * a.nch + c) * a.dm_stride + 64 + j] = make_double2(oi * vc, oq * vs);  // :515-516
+                a.dm[((long long)in * a.nch_all + a.chan_of[c]) * a.dm_stride + 64 + j] = make_double2(oi * vc, oq * vs);  // :515-516
             }
         }
     }

@@ -217,6 +217,24 @@ void acqg_twiddles(std::vector<double2> &w, int n, AcqgPlan *plan);
 int launch_acqg(const AcqArgs &a, const AcqgPlan &pl, double2 *img, int which, hipStream_t st);
 int launch_acq3(const FftFrontArgs &a, int nstreams, unsigned char *scratch, size_t scratch_bytes, int chunk_frames, int num_cu,
                 hipStream_t st, const AcqProf &prof, const AcqmPlan &plan, const AcqgPlan *gen = nullptr);
+// the channel handle's form (bpsk_acq_chan.hip): the forward phase once per INPUT and frame, scan / inverse / edges once per FFT
+// channel over that channel's streams (one per input), by the same kernels through strided arguments
+enum { ACQ_PART_FWD = 1, ACQ_PART_SCAN = 2, ACQ_PART_INV = 4, ACQ_PART_EDGES = 8, ACQ_PARTS_ALL = 15 };
+void acq3_row_layout(int n, int do_up, int *nsb, int *na);
+int launch_acq3_parts(AcqArgs &a, const FftFrontArgs &fa, int parts, int num_cu, hipStream_t st, const AcqProf &prof, const AcqmPlan &plan,
+                      const AcqgPlan *gen, double2 *img);
+struct AcqChanArgs {
+    int nin = 0, nch = 0;      // inputs, channels per input: stream = input * nch + channel
+    int nfft = 0;              // FFT-acquire channels ...
+    int chan[16] = {0};        // ... which they are ...
+    int up[16] = {0};          // ... and the band each searches (doUp)
+    FftFrontState *st = nullptr;  // [nch][nin]: CHANNEL-major, so that one channel's streams are consecutive
+    long long fwd_frames = 0, inv_frames = 0;  // out: frames transformed forward / inverted by the call
+    const char *fwd_name = "";                 // out: the forward kernel
+};
+size_t acq3c_frame_bytes(int n, int band_mask, bool generic);  // scratch per (input, frame) of one launch
+int launch_acq3_chan(const FftFrontArgs &fa, AcqChanArgs &ca, unsigned char *scratch, size_t scratch_bytes, int chunk_frames, int num_cu,
+                     hipStream_t st, const AcqProf &prof, const AcqmPlan &plan, const AcqgPlan *gen);
 extern int g_acq_last_grid[4];  // workgroups of the last k_acq_fwd / k_acq_inv launch, and how many of each a CU holds
 // frames that are not a power of two (bpsk_fftm.hip): any n with 416 <= n <= 9600 (2^a 3^b 5^c 7^d through the radix passes, any
 // other prime factor through a pass that is the DFT's definition and needs fftm_scratch(n) elements of scratch per stream)
