@@ -1,4 +1,4 @@
-// bpsk_fec.h -- the hook between the demodulator (bpsk.hip) and the FEC decoder (fec.hip).
+// bpsk_fec.h -- the hook between the demodulator (bpsk_handle.hip) and the FEC decoder (fec.hip).
 #pragma once
 #include "common.h"
 

@@ -1,4 +1,4 @@
-// bpsk_fft.h -- interface of the FFT-acquire front end (bpsk_fft.hip) used by the pipeline host code (bpsk.hip)
+// bpsk_fft.h -- interface of the FFT-acquire front end (bpsk_fft.hip) used by the pipeline host code (bpsk_handle.hip)
 #pragma once
 #include "common.h"
 #include <vector>

@@ -21,7 +21,7 @@
 #include <cmath>
 #include <vector>
 
-int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who);  // bpsk.hip: the checks of jsdr_bpsk_set_tuning / _set_mode
+int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who);  // bpsk_handle.hip: the checks of jsdr_bpsk_set_tuning / _set_mode
 
 namespace jsdr {
 
