@@ -19,6 +19,13 @@ OUT = os.path.join(HERE, "libjsdr_hip.so")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-unused-result"]
 SOURCES = {
+    # (the units that compile longest first: the four workers start in this order, and the last one to finish is the build's wall time.
+    #  The tune-mode pipeline is cut by kernel family -- bpsk_front_reg / bpsk_fm / bpsk_front / bpsk_tail -- so that none of them is the
+    #  whole build)
+    "bpsk_front_reg.hip": ["-ffp-contract=off"],
+    "bpsk_fm.hip": ["-ffp-contract=off"],
+    "bpsk_front.hip": ["-ffp-contract=off"],
+    "bpsk_tail.hip": ["-ffp-contract=off"],
     "runtime.hip": [],
     "fft_psd.hip": [],
     "fft_mixed.hip": [],
@@ -31,7 +38,6 @@ SOURCES = {
     "formats.hip": [],
     "demod.hip": ["-ffp-contract=off"],
     "demod_chan.hip": ["-ffp-contract=off"],
-    "bpsk.hip": ["-ffp-contract=off"],
     # (the handle: host code only, but its scheduler steps the reference's phase recurrences in doubles that must round as Java's do)
     "bpsk_handle.hip": ["-ffp-contract=off"],
     "bpsk_fft.hip": ["-ffp-contract=off"],

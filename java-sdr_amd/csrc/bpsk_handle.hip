@@ -1,9 +1,9 @@
 // bpsk_handle.hip -- the jsdr_bpsk handle: the host scheduler, the stages of a call and the C ABI (include/jsdr_hip.h).
 //
-// Host code only: no kernel is defined or launched here.  The tune-mode kernels are in bpsk.hip and are started through the
-// launch_* functions of bpsk_kernels.h; the other kernel families come in through bpsk_fft.h, bpsk_chan.h and bpsk_fec.h.
-// The handle fills their argument structs and calls the launchers, each stage of a call in ONE function that every kind of
-// handle (ordinary, channel, FFT-acquire channel) calls.
+// Host code only: no kernel is defined or launched here.  The tune-mode kernels are in bpsk_front.hip, bpsk_front_reg.hip,
+// bpsk_fm.hip and bpsk_tail.hip and are started through the launch_* functions of bpsk_kernels.h; the other kernel families
+// come in through bpsk_fft.h, bpsk_chan.h and bpsk_fec.h.  The handle fills their argument structs and calls the launchers,
+// each stage of a call in ONE function that every kind of handle (ordinary, channel, FFT-acquire channel) calls.
 //
 // Compiled with -ffp-contract=off like the kernels: the scheduler steps the reference's phase recurrences in host doubles
 // (FUNcubeBPSKDemod.java:384-390, :511-516), and every product and sum must round separately, as Java's do.

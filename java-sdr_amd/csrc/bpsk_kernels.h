@@ -1,6 +1,7 @@
-// bpsk_kernels.h -- the tune-mode pipeline's kernels (bpsk.hip) as the handle (bpsk_handle.hip) sees them: the argument
-// structs that cross the seam, the geometry constants the handle sizes its buffers with, and one launcher per kernel it
-// starts.  The launchers hold each kernel's grid, LDS and template choice (and the knobs that pick between kernels).
+// bpsk_kernels.h -- the tune-mode pipeline's kernels (bpsk_front.hip, bpsk_front_reg.hip, bpsk_fm.hip, bpsk_tail.hip) as the
+// handle (bpsk_handle.hip) sees them: the argument structs that cross the seam, the geometry constants the handle sizes its
+// buffers with, and one launcher per kernel it starts.  The launchers hold each kernel's grid, LDS and template choice (and
+// the knobs that pick between kernels).
 #pragma once
 #include "common.h"
 #include "bpsk_fft.h"
@@ -20,9 +21,8 @@ struct BpskConst {
     double dm_taps[96];   // [65] used, zero beyond (edge steps of the register-blocked loops read past 64)
     signed char sync[72]; // [65] used, +1/-1
 };
-int bpsk_upload_constants(const BpskConst &bc);  // -> __constant__ c_bpsk, read by the front, matched, fm, tail and sync kernels
+int bpsk_upload_constants(const BpskConst &bc);  // -> every unit's __constant__ c_bpsk, read by the front, matched, fm, tail and sync kernels
 
-// per-stream demodulator state that depends on the data (FUNcubeBPSKDemod.java:497-503)
 // per-stream demodulator state that depends on the data (FUNcubeBPSKDemod.java:497-503)
 struct TailState {
     double dmEnergy[8];

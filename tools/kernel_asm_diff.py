@@ -18,7 +18,9 @@ import os
 import re
 import sys
 
-LOCAL = [(re.compile(r"\.LBB\d+_"), ".LBB_"), (re.compile(r"\.Lfunc_(\w+?)\d+"), r".Lfunc_\1"), (re.compile(r"\.Ltmp\d+"), ".Ltmp")]
+LOCAL = [(re.compile(r"\.LBB\d+_"), ".LBB_"), (re.compile(r"\.Lfunc_(\w+?)\d+"), r".Lfunc_\1"), (re.compile(r"\.Ltmp\d+"), ".Ltmp"),
+         # the tune-mode units' copies of the __constant__ tables, jsdr::{front,fm,tail}::c_bpsk: one object, jsdr::c_bpsk, before the cut
+         (re.compile(r"_ZN4jsdr(?:5front|2fm|4tail)6c_bpskE"), "_ZN4jsdr6c_bpskE")]
 
 
 def norm(line):
