@@ -232,7 +232,8 @@ int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
  *     apply to every channel; get_control reports channel 0.
  *   channel_info: an ordinary handle reports nstreams x 1 (and takes channel 0 in the per-channel calls).
  * JSDR_ERR, the handle unchanged: do_fft = 1 in set_mode / set_channel_mode / reconfigure, set_variant(FAST), snapshot_read
- * when nchannels > 1, a channel out of range, a non-finite tuning; float input through batch calls.  Not covered on this
+ * when nchannels > 1, a channel out of range, a non-finite tuning; float input through receive_f32 other than JavaAudio's values (jsdr_bpsk_batch_f32 takes any float,
+ * its stride between INPUTS as batch_i16's).  Not covered on this
  * handle: FFT-acquire channels (jsdr_bpsk_create_mode_channels below has them), the FAST variant, jsdr_group, JNI / Java
  * classes, a per-channel snapshot. */
 int jsdr_bpsk_create_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
@@ -275,13 +276,32 @@ int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
  * multiple of nsamples_per_frame in FFT mode; asynchronous on `stream`.                        */
 int jsdr_bpsk_batch_i16(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stream_stride_i16,
                         int64_t nsamples, int ic, int qc, void *stream);
+/* batched IAudioHandler.receive(float[]): iq_dev[s*stream_stride_f32 + 2t], [.. + 2t+1] = I, Q of sample t of stream s, taken as
+ * the reference takes buf[] (no DC correction, no scaling: x = (double)f).  Otherwise as jsdr_bpsk_batch_i16: asynchronous on
+ * `stream`, the tail, sync and FEC on the side stream, live control between calls as between int16 calls.
+ *   Serves an ordinary handle of any nstreams (the tune mode at any call length, FFT-acquire at whole frames of every frame
+ *   jsdr_bpsk_create accepts) and the handles of jsdr_bpsk_create_channels / jsdr_bpsk_create_mode_channels (the stride is
+ *   between INPUTS).  Results are bit-identical to nstreams one-stream handles of the same configuration, each fed the same
+ *   floats through jsdr_bpsk_receive_f32.  FFT-acquire channels of float input run the forward phase once per band in use
+ *   (the both-band transform is an int16 kernel); jsdr_bpsk_acq_last_launch reports what ran.
+ *   Calls of the two forms may alternate on one handle: float after int16 converts the 26-sample input history (per input on
+ *   a channel handle), int16 after floats that are (float)s/32767f values converts it back, int16 after any other float is
+ *   refused with the handle unchanged.
+ *   jsdr_bpsk_front_kernel: "k_fm_f32", the fused float kernel, where an int16 call would take "k_fm" (a standard decimation, a
+ *   periodic tuner schedule or none, no call that straddles a retune); jsdr_bpsk_set_cu_share / _last_launch and the k_fm and
+ *   k_fm_prep profile slots apply to it.  JSDR_FM=0 (JSDR_KNOBS=1): always the three-kernel path.
+ * JSDR_ERR, the handle unchanged, each checked before any device work: a null handle or pointer, an odd stride, a stride below
+ * 2 nsamples with more than one stream or input, nsamples outside (0, max_batch_samples], a call that is not whole frames
+ * where FFT-acquire needs them, a JSDR_VARIANT_FAST handle (its certification re-reads int16).
+ * Not covered: jsdr_group_*, the FAST variant, JNI and the Java classes (they feed floats through receive_f32). */
+int jsdr_bpsk_batch_f32(jsdr_bpsk *h, const float *iq_dev, int64_t stream_stride_f32, int64_t nsamples, void *stream);
 int jsdr_bpsk_set_cu_share(jsdr_bpsk *h, int wgs_per_cu); /* see jsdr_fft_set_cu_share; applies to the tune-mode front-end kernel */
 /* The library's own answer to "should fft.receive and this demodulator, fed the same batch on two streams, share the CUs?":
  * the shares to pass to jsdr_fft_set_cu_share / jsdr_bpsk_set_cu_share (2 and 1 where the split was measured to pay: the
  * exact variant's tune-mode kernel, 96 kHz, 2048-sample frames, 8192 streams and more per device), 0 and 0 everywhere else.
  * bench.py and jsdr_group_* ask this instead of carrying the rule themselves. */
 int jsdr_bpsk_pair_shares(jsdr_bpsk *h, int *fft_wgs_per_cu, int *bpsk_wgs_per_cu);
-/* diagnostics: tiles x streams of the last tune-mode front-end launch (k_fm) and the workgroups that strode over them */
+/* diagnostics: tiles x streams of the last tune-mode front-end launch (k_fm, k_fm_f32) and the workgroups that strode over them */
 int jsdr_bpsk_last_launch(jsdr_bpsk *h, int64_t *work_items, int64_t *workgroups);
 /* wait until every kernel of the calls made so far has finished (the 9600 Hz tail and the FEC decoder run on
  * an internal side stream so that they overlap the next call's front end; the getters below call this). */

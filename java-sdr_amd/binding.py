@@ -486,6 +486,12 @@ class Bpsk:
         _check(lib().jsdr_bpsk_batch_i16(self.h, _addr(raw_dev), C.c_int64(stride_i16), C.c_int64(nsamples), ic, qc,
                                          C.c_void_p(stream)), "jsdr_bpsk_batch_i16")
 
+    def batch_f32(self, iq_dev, stride_f32, nsamples, stream=None):
+        """float IQ [S][stride_f32], taken as receive(float[]) takes buf[] (any float: no DC correction, no scaling); otherwise
+        as batch_i16"""
+        _check(lib().jsdr_bpsk_batch_f32(self.h, _addr(iq_dev), C.c_int64(stride_f32), C.c_int64(nsamples),
+                                         C.c_void_p(stream)), "jsdr_bpsk_batch_f32")
+
     def is_recovered(self, stream):
         """fast variant: this stream is served by the exact shadow handle (jsdr_bpsk_recover_uncertified replayed it)"""
         v = C.c_int()
@@ -652,6 +658,10 @@ class BpskChannels(Bpsk):
     def batch_i16(self, raw_dev, input_stride_i16, nsamples, ic=0, qc=0, stream=None):
         """input_stride_i16: between INPUTS"""
         super().batch_i16(raw_dev, input_stride_i16, nsamples, ic, qc, stream)
+
+    def batch_f32(self, iq_dev, input_stride_f32, nsamples, stream=None):
+        """input_stride_f32: between INPUTS"""
+        super().batch_f32(iq_dev, input_stride_f32, nsamples, stream)
 
     def set_channel_tuning(self, channel, tuning_hz):
         _check(lib().jsdr_bpsk_set_channel_tuning(self.h, int(channel), C.c_double(tuning_hz)), "jsdr_bpsk_set_channel_tuning")

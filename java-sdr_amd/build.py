@@ -20,10 +20,11 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
           "-Wno-unused-result"]
 SOURCES = {
     # (the units that compile longest first: the four workers start in this order, and the last one to finish is the build's wall time.
-    #  The tune-mode pipeline is cut by kernel family -- bpsk_front_reg / bpsk_fm / bpsk_front / bpsk_tail -- so that none of them is the
+    #  The tune-mode pipeline is cut by kernel family -- bpsk_front_reg / bpsk_fm / bpsk_fm_f32 / bpsk_front / bpsk_tail -- so that none of them is the
     #  whole build)
     "bpsk_front_reg.hip": ["-ffp-contract=off"],
     "bpsk_fm.hip": ["-ffp-contract=off"],
+    "bpsk_fm_f32.hip": ["-ffp-contract=off"],
     "bpsk_front.hip": ["-ffp-contract=off"],
     "bpsk_tail.hip": ["-ffp-contract=off"],
     "runtime.hip": [],

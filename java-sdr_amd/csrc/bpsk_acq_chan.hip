@@ -310,11 +310,13 @@ int launch_acq3_chan(const FftFrontArgs &fa, AcqChanArgs &ca, unsigned char *scr
     const bool generic = gen != nullptr && gen->on;
     const int n = fa.n;
     JSDR_REQUIRE(generic || acq3_supported(n), "bpsk channels: no FFT-acquire front end for frames of %d samples", n);
-    JSDR_REQUIRE(ca.nfft >= 1 && ca.nfft <= 16 && ca.nin >= 1 && fa.raw && !fa.rawf, "bpsk channels: internal: bad FFT-acquire channel set");
+    JSDR_REQUIRE(ca.nfft >= 1 && ca.nfft <= 16 && ca.nin >= 1 && (fa.raw != nullptr) != (fa.rawf != nullptr), "bpsk channels: internal: bad FFT-acquire channel set");
     int mask = 0;
     for (int k = 0; k < ca.nfft; k++) mask |= ca.up[k] ? 2 : 1;
     const bool pow2 = !generic && !acqm_supported(n);
-    const bool both = mask == 3 && pow2;  // one transform serves both bands
+    // one transform serves both bands -- of int16 input: k_acqc_fwd has no float form, float input (jsdr_bpsk_batch_f32) takes
+    // k_acq_fwd's once per band in use
+    const bool both = mask == 3 && pow2 && !fa.rawf;
     if (chunk_frames < 1) chunk_frames = 1;
     const size_t nf = (size_t)ca.nin * (size_t)chunk_frames;
     JSDR_REQUIRE(nf * acq3c_frame_bytes(n, mask, generic) + 4096 <= scratch_bytes, "bpsk channels: FFT-acquire scratch too small (%zu frames)", nf);
@@ -343,7 +345,7 @@ int launch_acq3_chan(const FftFrontArgs &fa, AcqChanArgs &ca, unsigned char *scr
     }
     AcqArgs a;
     a.raw = fa.raw;
-    a.rawf = nullptr;
+    a.rawf = fa.rawf;
     a.stride_pairs = fa.stride_pairs;
     a.ic = fa.ic;
     a.qc = fa.qc;

@@ -7,10 +7,10 @@ namespace jsdr {
 enum { CHAN_MAX = 16 };
 
 struct ChanFrontArgs {
-    const int *raw;                     // int16 pairs as dwords, [ninputs][stride_pairs]
+    const int *raw;                     // int16 pairs as dwords, [ninputs][stride_pairs]; k_chan_front<.., F32IN>: float2 samples
     long long stride_pairs;             // between inputs
     int ic, qc;
-    const int2 *hist;                   // [ninputs][32]: the 26 inputs before this call, DC-corrected int16 pair (.x)
+    const int2 *hist;                   // [ninputs][32]: the 26 inputs before this call, DC-corrected int16 pair (.x) or float2 bits
     const unsigned short *k9[CHAN_MAX]; // per channel: 9-bit tuner index table (256: pass-through)
     int per[CHAN_MAX];                  // per channel: period of k9 (entry (n + 26) mod per), or 0: k9[26 + n]
     int nch;                            // channels this launch takes ...
@@ -27,6 +27,6 @@ struct ChanFrontArgs {
     int nout;                           // outputs per workgroup (set by the launcher)
 };
 
-int launch_chan_front(const ChanFrontArgs &a, int ninputs, hipStream_t st);
+int launch_chan_front(const ChanFrontArgs &a, int ninputs, bool f32in, hipStream_t st);
 
 }  // namespace jsdr

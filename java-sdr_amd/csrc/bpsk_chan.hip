@@ -3,7 +3,7 @@
 //
 // One workgroup = up to 256 consecutive decimated outputs of ONE input.  The raw samples their 27-tap windows cover are
 // read from memory once, DC-corrected and converted int16 -> float (JavaAudio's rule) once, and parked in LDS as float2
-// (exact: (double)f is what the reference multiplies).  Then every thread owns one output and walks its window newest ->
+// (exact: (double)f is what the reference multiplies); float input (F32IN, jsdr_bpsk_batch_f32) IS that image and is parked as read.  Then every thread owns one output and walks its window newest ->
 // oldest (FUNcubeBPSKDemod.java:479-483) for every channel of the input, CG channels at a time with their accumulator pairs
 // in registers, so one LDS read of a sample serves CG channels.  Per channel and sample the tuner factor (:388-390,
 // component-wise) comes from a 9-bit index into cos[0..256] / sin[0..256] whose entry 256 is (1.0, 1.0): a sample the
@@ -19,7 +19,7 @@ namespace jsdr {
 
 enum { CHAN_THREADS = 256, CHAN_CG = 4 };
 
-template <int CG>
+template <int CG, bool F32IN = false>
 __global__ __launch_bounds__(CHAN_THREADS) void k_chan_front(ChanFrontArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -38,6 +38,15 @@ __global__ __launch_bounds__(CHAN_THREADS) void k_chan_front(ChanFrontArgs a)
     const int2 *hist = a.hist + (long long)in * 32;
     for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
         const long long n = n_lo + e;  // < L: the newest sample of the last output is at most L - 1
+        if constexpr (F32IN) {
+            if (n >= 0) {
+                x[e] = reinterpret_cast<const float2 *>(a.raw)[(long long)in * a.stride_pairs + n];
+            } else {
+                const int2 h = hist[26 + n];  // the float pair's bits (k_hist_in)
+                x[e] = make_float2(__int_as_float(h.x), __int_as_float(h.y));
+            }
+            continue;
+        }
         int w;
         if (n >= 0) {
             w = raw[n];
@@ -96,7 +105,7 @@ __global__ __launch_bounds__(CHAN_THREADS) void k_chan_front(ChanFrontArgs a)
     }
 }
 
-int launch_chan_front(const ChanFrontArgs &a_in, int ninputs, hipStream_t st)
+int launch_chan_front(const ChanFrontArgs &a_in, int ninputs, bool f32in, hipStream_t st)
 {
     ChanFrontArgs a = a_in;
     // outputs per workgroup: 256, fewer where a tile's samples would not fit 64 KB of LDS (decimations above 31)
@@ -110,8 +119,13 @@ int launch_chan_front(const ChanFrontArgs &a_in, int ninputs, hipStream_t st)
     a.nout = (int)nout;
     const size_t lds = (514 + 28) * sizeof(double) + ((size_t)(nout - 1) * a.decim + 27) * sizeof(float2);
     const long long gx = (a.nds + nout - 1) / nout;
-    JSDR_LDS_ATTR(k_chan_front<CHAN_CG>, lds);
-    hipLaunchKernelGGL(k_chan_front<CHAN_CG>, dim3((unsigned)gx, (unsigned)ninputs), dim3(CHAN_THREADS), lds, st, a);
+    if (f32in) {
+        JSDR_LDS_ATTR((k_chan_front<CHAN_CG, true>), lds);
+        hipLaunchKernelGGL((k_chan_front<CHAN_CG, true>), dim3((unsigned)gx, (unsigned)ninputs), dim3(CHAN_THREADS), lds, st, a);
+    } else {
+        JSDR_LDS_ATTR((k_chan_front<CHAN_CG, false>), lds);
+        hipLaunchKernelGGL((k_chan_front<CHAN_CG, false>), dim3((unsigned)gx, (unsigned)ninputs), dim3(CHAN_THREADS), lds, st, a);
+    }
     JSDR_LAUNCH_CHECK();
     return JSDR_OK;
 }

@@ -121,6 +121,9 @@ struct jsdr_bpsk {
     DevBuf<int> amax;              // fast variant: [S] running maximum of |int16 sample| (float bits)
     DevBuf<SnapPack> snap_dev;     // receive(): the packed results of the call, fetched in one copy (k_snapshot_pack)
     DevBuf<int> fm_edges;          // k_fm: [S][4 * FM_EDGE] the stream around sample 0 and around the last sample (k_fm_edges)
+    DevBuf<float2> fm_edges_f32;   // k_fm_f32: the same images as float pairs (k_fm_prep_f32); allocated by the first jsdr_bpsk_batch_f32
+    bool f32_batch = false;        // the call in progress is a jsdr_bpsk_batch_f32: float input may take the fused kernel (receive_f32's
+                                   // frames keep the three-kernel path)
     DevBuf<double2> dm, y[2];  // y is double-buffered: the tail of call k overlaps the front end of call k+1
     int y_cur = 0;
     // fused front end + matched filter (k_fm): the 64-sample halo lives in its own double buffer, the tuner table is
@@ -813,6 +816,30 @@ static int run_hist_in(jsdr_bpsk *h, const HistArgs &ha, hipStream_t st)
     return JSDR_OK;
 }
 
+// The 26-sample input history is kept in the form of the input that wrote it.  A call of the other form gets it converted
+// (k_hist_convert): int16 -> float always exists; float -> int16 exists exactly when every float is some (float)s/32767f, and a
+// call that finds another float is refused.  The conversion is made on a COPY in the idle history buffer, which becomes the
+// current one only when it holds: a refused call leaves the handle as it was.  rows: streams, or inputs of a channel handle.
+static int hist_form(jsdr_bpsk *h, bool want_float, int rows, hipStream_t st)
+{
+    if (h->n_in > 0 && want_float != h->hist_is_float) {
+        int2 *cur = h->hist_in[h->hist_cur].p, *idle = h->hist_in[h->hist_cur ^ 1].p;
+        JSDR_HIP_TRY(hipMemcpyAsync(idle, cur, sizeof(int2) * 32 * (size_t)rows, hipMemcpyDeviceToDevice, st));
+        JSDR_HIP_TRY(hipMemsetAsync(h->hist_bad.p, 0, sizeof(int), st));
+        if (launch_hist_convert(idle, rows, want_float ? 1 : 0, h->hist_bad.p, st) != JSDR_OK) return JSDR_ERR;
+        if (!want_float) {
+            int bad = 0;
+            JSDR_HIP_TRY(hipMemcpyAsync(&bad, h->hist_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
+            JSDR_HIP_TRY(hipStreamSynchronize(st));
+            JSDR_REQUIRE(!bad, "bpsk: int16 input after float frames whose samples are not (float)s/32767f values: the input "
+                         "history cannot be carried over");
+        }
+        h->hist_cur ^= 1;
+    }
+    h->hist_is_float = want_float;
+    return JSDR_OK;
+}
+
 // first block boundary of the matched filter's tiling (slot 0 <=> g == 64 mod 65) at or before g_first; may be "negative" for g < 64
 static long long first_block(long long g_first)
 {
@@ -1002,7 +1029,7 @@ static long long chan_vco(jsdr_bpsk *h, long long L, bool *fresh)
 static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, long long stride_i16, long long L, int ic,
                     int qc, hipStream_t st)
 {
-    JSDR_REQUIRE(raw_dev && !rawf_dev, "bpsk channels: the channel handle takes int16 input");
+    JSDR_REQUIRE((raw_dev != nullptr) != (rawf_dev != nullptr), "bpsk channels: null input");
     JSDR_REQUIRE(L > 0 && L <= h->max_batch, "bpsk: nsamples=%lld outside (0, max_batch_samples=%lld]", L, h->max_batch);
     JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nin == 1 || stride_i16 >= 2 * L),
                  "bpsk channels: input stride %lld too small for %lld samples", stride_i16, L);
@@ -1015,6 +1042,12 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
             if (h->chan[c].do_fft) mask |= h->chan[c].do_up ? 2 : 1;
         // (per INPUT and frame)
         if (acq_scratch_ensure(h, acq3c_frame_bytes(h->nsf, mask, h->gen_plan.on), (size_t)h->nin, 4096) != JSDR_OK) return JSDR_ERR;
+    }
+    // the inputs' 26-sample history in the form of this call's input (only the tune-mode channels read it)
+    if (h->nfftch < h->nch) {
+        if (hist_form(h, rawf_dev != nullptr, h->nin, st) != JSDR_OK) return JSDR_ERR;
+    } else {
+        h->hist_is_float = rawf_dev != nullptr;
     }
     const int first_out = h->decim - 1 - h->dsCnt;
     const long long g_first = h->n_ds;
@@ -1035,6 +1068,7 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         h->rx_frame_bytes = 0;
     }
     const int *raw = reinterpret_cast<const int *>(raw_dev);
+    const float2 *rawf = reinterpret_cast<const float2 *>(rawf_dev);
     const long long stride_pairs = stride_i16 / 2;
     if (h->nfftch > 0 && vfresh && nds > 0)
         if (send_vco_cs(h, nds, st) != JSDR_OK) return JSDR_ERR;
@@ -1050,7 +1084,7 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
             ca.nfft++;
         }
         ca.st = h->fft_state.p;
-        FftFrontArgs xa = fft_front_args(h, raw, nullptr, stride_pairs, L, ic, qc, first_out, nds);
+        FftFrontArgs xa = fft_front_args(h, raw, rawf, stride_pairs, L, ic, qc, first_out, nds);
         xa.do_up = 0;  // (each channel's band is in ca.up)
         AcqLaunchCtx lc;
         acq_launch_ctx(h, lc);
@@ -1063,7 +1097,7 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     if (nds > 0 && h->nfftch < h->nch) {
         ChanFrontArgs fa;
         memset(&fa, 0, sizeof(fa));
-        fa.raw = raw;
+        fa.raw = rawf ? reinterpret_cast<const int *>(rawf) : raw;
         fa.stride_pairs = stride_pairs;
         fa.ic = ic;
         fa.qc = qc;
@@ -1086,9 +1120,9 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         fa.decim = h->decim;
         ProfScope ps(h, PK_FRONT, st);
         if (h->nfftch == 0) h->front_name = "k_chan_front";
-        if (launch_chan_front(fa, h->nin, st) != JSDR_OK) return JSDR_ERR;
+        if (launch_chan_front(fa, h->nin, rawf != nullptr, st) != JSDR_OK) return JSDR_ERR;
     }
-    if (run_hist_in(h, hist_args(h, raw, nullptr, stride_pairs, L, ic, qc, h->nin), st) != JSDR_OK) return JSDR_ERR;  // per input
+    if (run_hist_in(h, hist_args(h, raw, rawf, stride_pairs, L, ic, qc, h->nin), st) != JSDR_OK) return JSDR_ERR;  // per input
     const int yb = h->y_cur;
     if (wait_tail(h, yb, st) != JSDR_OK) return JSDR_ERR;
     if (nds > 0 && run_matched(h, yb, nds, g_first, st) != JSDR_OK) return JSDR_ERR;
@@ -1110,6 +1144,12 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     JSDR_REQUIRE(h->variant == 0 || raw_dev, "bpsk: the fast variant takes int16 input (its certification pass re-reads the raw samples)");
     JSDR_REQUIRE(h->seam != SEAM_TO_TUNE || L >= 26, "bpsk: the first tune-mode call after FFT-acquire frames needs at least 26 samples "
                  "(the input history is rebuilt from them)");
+    // the fused float kernel's edge images (4 KB a stream), at the first float batch: what can fail for want of memory fails
+    // before anything of the handle has moved on
+    if (rawf_dev && h->f32_batch && h->use_fm && !h->fm_edges_f32.p && (h->decim == 4 || h->decim == 5 || h->decim == 10 || h->decim == 20))
+        if (h->fm_edges_f32.alloc((size_t)h->nstreams * 4 * FM_EDGE) != JSDR_OK) return JSDR_ERR;
+    // the previous call may have come through the other input form (before the schedule moves on: the conversion can refuse)
+    if (!h->do_fft && h->seam != SEAM_TO_TUNE && hist_form(h, rawf_dev != nullptr, h->nstreams, st) != JSDR_OK) return JSDR_ERR;
     const int first_out = h->decim - 1 - h->dsCnt;
     const long long g_first = h->n_ds;
     unsigned char kh0[26], mh0[26];  // the tuner indices / mix flags of the 26 samples before the call (build_schedule moves them on)
@@ -1127,28 +1167,13 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         split = h->mix < 0 || h->seam == SEAM_TO_TUNE;
         for (int i = 0; i < 26 && !split; i++) split = h->h_mhist[i] != (unsigned char)f0;
     }
-    if (!h->do_fft) {
-        const bool want_float = rawf_dev != nullptr;
-        if (h->n_in > 0 && want_float != h->hist_is_float && h->seam != SEAM_TO_TUNE) {  // the previous call came through the other input form
-            JSDR_HIP_TRY(hipMemsetAsync(h->hist_bad.p, 0, sizeof(int), st));
-            if (launch_hist_convert(h->hist_in[h->hist_cur].p, h->nstreams, want_float ? 1 : 0, h->hist_bad.p, st) != JSDR_OK) return JSDR_ERR;
-            if (!want_float) {
-                int bad = 0;
-                JSDR_HIP_TRY(hipMemcpyAsync(&bad, h->hist_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
-                JSDR_HIP_TRY(hipStreamSynchronize(st));
-                JSDR_REQUIRE(!bad, "bpsk: int16 input after float frames whose samples are not (float)s/32767f values: the input "
-                             "history cannot be carried over");
-            }
-        }
-        h->hist_is_float = want_float;
-    }
-    // fused path (k_fm): int16 input, a tuner schedule that is periodic with a period dividing the lane span (or
-    // no tuner at all), 32-bit sample indices
+    // fused path (k_fm; k_fm_f32 for the float batches of jsdr_bpsk_batch_f32): a tuner schedule that is periodic with a
+    // period dividing the lane span (or no tuner at all), 32-bit sample indices
     const bool std_decim = h->decim == 4 || h->decim == 5 || h->decim == 10 || h->decim == 20;  // the specialised front ends
     const int fm_rd = h->decim == 4 ? 20 : h->decim * 4;  // D * R of the k_fm instantiation
     const bool per_ok = !h->do_fft && !split && h->mix == 1 && h->c_tper > 0 && fm_rd % h->c_tper == 0;
-    const bool fm_ok = h->use_fm && std_decim && !h->do_fft && !split && raw_dev && !rawf_dev && nds > 0 && L <= 0x3fffffffLL &&
-                       (h->mix == 0 || per_ok);
+    const bool fm_ok = h->use_fm && std_decim && !h->do_fft && !split && nds > 0 && L <= 0x3fffffffLL &&
+                       ((raw_dev && !rawf_dev) || (rawf_dev && h->f32_batch && h->variant == 0 && h->fm_edges_f32.p)) && (h->mix == 0 || per_ok);
     const int kshift = 0;
     const bool fresh = !h->cache_valid;
     if (fresh) h->ktu_uploaded = false;
@@ -1363,7 +1388,19 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         ma.first_out = first_out;
         ma.amax = h->amax.p;
         ma.grid_limit = h->share_wgs_per_cu * h->num_cu;  // (jsdr_bpsk_set_cu_share has asked for the CU count)
-        {
+        if (rawf_dev) {
+            EdgeF32Args ea;
+            ea.rawf = fa.rawf;
+            ea.stride_pairs = fa.stride_pairs;
+            ea.nsamples = (int)L;
+            ea.hist = fa.hist;
+            ea.edges = h->fm_edges_f32.p;
+            ea.nstreams = S;
+            const HistArgs ha = hist_args(h, nullptr, fa.rawf, fa.stride_pairs, L, 0, 0, S);
+            ProfScope psh(h, PK_PREP, st);
+            if (launch_fm_prep_f32(ea, ha, st) != JSDR_OK) return JSDR_ERR;
+            hist_done = true;
+        } else {
             EdgeArgs ea;
             ea.raw = fa.raw;
             ea.stride_pairs = fa.stride_pairs;
@@ -1381,9 +1418,18 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
             hist_done = true;
         }
         ProfScope ps(h, PK_FM, st);
+        if (rawf_dev) {
+            FmF32Args mf;
+            mf.a = ma;
+            mf.rawf = fa.rawf;
+            mf.edges = h->fm_edges_f32.p;
+            h->front_name = "k_fm_f32";
+            if (launch_fm_f32(mf, h->decim, h->mix != 0, S, st, &h->last_fm_items, &h->last_fm_grid) != JSDR_OK) return JSDR_ERR;
+        } else {
         h->front_name = "k_fm";
         if (launch_fm(ma, h->decim, h->mix != 0, (ic != 0) || (qc != 0), h->variant != 0, S, st, &h->last_fm_items, &h->last_fm_grid) != JSDR_OK)
             return JSDR_ERR;
+        }
         h->dmh_cur ^= 1;
     } else if (nds > 0) {
         ProfScope ps(h, PK_FRONT, st);
@@ -1717,6 +1763,7 @@ int jsdr_bpsk_destroy(jsdr_bpsk *h)
     h->hist_bad.release();
     h->amax.release();
     h->fm_edges.release();
+    h->fm_edges_f32.release();
     h->snap_dev.release();
     h->dmh[0].release();
     h->dmh[1].release();
@@ -1840,6 +1887,17 @@ int jsdr_bpsk_batch_i16(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stream_str
         if (bpsk_run(h->shadow, h->shadow_in.p, nullptr, 2 * h->max_batch, nsamples, ic, qc, as_stream(stream)) != JSDR_OK) return JSDR_ERR;
     }
     return JSDR_OK;
+}
+
+// batched IAudioHandler.receive(float[]): bpsk_run with the float input; its refusals are bpsk_run's / chan_run's checks, which come
+// before any device work.
+int jsdr_bpsk_batch_f32(jsdr_bpsk *h, const float *iq_dev, int64_t stream_stride_f32, int64_t nsamples, void *stream)
+{
+    JSDR_REQUIRE(h && iq_dev, "jsdr_bpsk_batch_f32: null argument");
+    h->f32_batch = true;
+    const int rc = bpsk_run(h, nullptr, iq_dev, stream_stride_f32, nsamples, 0, 0, as_stream(stream));
+    h->f32_batch = false;
+    return rc;
 }
 
 // Fast variant: the streams the calls so far left uncertified are REPLAYED from the handle's first call on an internal exact

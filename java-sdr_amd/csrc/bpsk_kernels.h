@@ -127,6 +127,22 @@ struct ScatterArgs {
     int bytes[2];
 };
 
+// k_fm_f32 (bpsk_fm_f32.hip): k_fm's arguments with the float input and the float edge images (a.raw, a.edges, a.ic, a.qc and
+// a.amax are unused)
+struct FmF32Args {
+    FmArgs a;
+    const float2 *rawf;         // the float frames of IAudioHandler.receive, [S][stride]
+    const float2 *edges;        // [S][4 * FM_EDGE]: k_fm_prep_f32's images
+};
+struct EdgeF32Args {
+    const float2 *rawf;
+    long long stride_pairs;
+    int nsamples;
+    const int2 *hist;           // [S][32]: the 26 inputs before this call, float pairs' bits
+    float2 *edges;
+    int nstreams;
+};
+
 struct TailArgs {
     const double2 *y;
     long long y_stride;
@@ -183,6 +199,8 @@ int launch_dm_history(double2 *dm, long long dm_stride, long long nds, int nstre
 int launch_fm_prep(const EdgeArgs &ea, const HistArgs &ha, const ScatterArgs &sc, hipStream_t st);
 // *items, *grid: the work items (tiles x streams) of the launch and the workgroups that stride over them
 int launch_fm(const FmArgs &a, int decim, bool mix, bool dc, bool fast, int nstreams, hipStream_t st, long long *items, long long *grid);
+int launch_fm_prep_f32(const EdgeF32Args &ea, const HistArgs &ha, hipStream_t st);
+int launch_fm_f32(const FmF32Args &a, int decim, bool mix, int nstreams, hipStream_t st, long long *items, long long *grid);
 const char *launch_tail(const TailArgs &ta, bool cert, hipStream_t st);
 bool sync_t_applies(int max_bits);  // the transposed-image sync kernel takes a log of that many new bits (JSDR_SYNC_T=0: never)
 int launch_sync_t(const SyncArgs &sa, const SyncFinArgs &sf, int nstreams, hipStream_t st);

@@ -1157,7 +1157,7 @@ namespace jsdr {
 // every unit's copy of the tables (bpsk_units.h)
 int bpsk_upload_constants(const BpskConst &bc)
 {
-    if (bpsk_front_upload_constants(bc) != JSDR_OK || bpsk_fm_upload_constants(bc) != JSDR_OK) return JSDR_ERR;
+    if (bpsk_front_upload_constants(bc) != JSDR_OK || bpsk_fm_upload_constants(bc) != JSDR_OK || bpsk_fm_f32_upload_constants(bc) != JSDR_OK) return JSDR_ERR;
     JSDR_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(c_bpsk), &bc, sizeof(bc)));
     return JSDR_OK;
 }

@@ -1,5 +1,5 @@
 // bpsk_units.h -- what the tune-mode pipeline's translation units (bpsk_front.hip, bpsk_front_reg.hip, bpsk_fm.hip,
-// bpsk_tail.hip) share beyond bpsk_kernels.h.  Internal to those four: the handle sees bpsk_kernels.h only.
+// bpsk_fm_f32.hip, bpsk_tail.hip) share beyond bpsk_kernels.h.  Internal to those five: the handle sees bpsk_kernels.h only.
 //
 // The build has no relocatable device code, so a __constant__ object cannot be shared between units: each unit whose kernels
 // read the tables holds its own copy, `namespace <unit> { __constant__ BpskConst c_bpsk; }` -- the whole struct, so a field
@@ -40,6 +40,7 @@ static int launched()
 // bpsk_tail.hip and call these (hidden: the library exports what it exported as one unit)
 __attribute__((visibility("hidden"))) int bpsk_front_upload_constants(const BpskConst &bc);
 __attribute__((visibility("hidden"))) int bpsk_fm_upload_constants(const BpskConst &bc);
+__attribute__((visibility("hidden"))) int bpsk_fm_f32_upload_constants(const BpskConst &bc);
 __attribute__((visibility("hidden"))) void bpsk_fm_clocks_report();  // JSDR_X_CLK
 
 // bpsk_front_reg.hip's launcher as bpsk_front.hip's launch_front calls it (instantiated there for the four rates)
