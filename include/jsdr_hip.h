@@ -234,8 +234,8 @@ int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
  * JSDR_ERR, the handle unchanged: do_fft = 1 in set_mode / set_channel_mode / reconfigure, set_variant(FAST), snapshot_read
  * when nchannels > 1, a channel out of range, a non-finite tuning; float input through receive_f32 other than JavaAudio's values (jsdr_bpsk_batch_f32 takes any float,
  * its stride between INPUTS as batch_i16's).  Not covered on this
- * handle: FFT-acquire channels (jsdr_bpsk_create_mode_channels below has them), the FAST variant, jsdr_group, JNI / Java
- * classes, a per-channel snapshot. */
+ * handle: FFT-acquire channels (jsdr_bpsk_create_mode_channels below has them; jsdr_bpsk_create_live_channels switches a
+ * channel between the modes live), the FAST variant, jsdr_group, JNI / Java classes, a per-channel snapshot. */
 int jsdr_bpsk_create_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
                               const double *tuning_hz, const int *do_up, int64_t max_batch_samples);
 /* Channel handle whose channels are each in the tune mode or in FFT-acquire ("FFT/Tune", FUNcubeBPSKDemod.java:180-186),
@@ -260,9 +260,50 @@ int jsdr_bpsk_create_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, i
  *     reconfigure take a do_fft that changes no channel's mode (so none at all on a handle with both kinds).
  * JSDR_ERR, the handle unchanged: a change of a channel's do_fft by any route, a call that is not whole frames,
  * set_variant(FAST), snapshot_read when nchannels > 1, a channel out of range, a non-finite tuning -- all checked before
- * any device work.  Not covered: switching a channel between the modes live, the FAST variant, jsdr_group, JNI / Java
- * classes, a per-channel snapshot. */
+ * any device work.  Not covered on this handle: switching a channel between the modes live (jsdr_bpsk_create_live_channels
+ * below has it), the FAST variant, jsdr_group, JNI / Java classes, a per-channel snapshot. */
 int jsdr_bpsk_create_mode_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                                   const double *tuning_hz, const int *do_fft, const int *do_up, int64_t max_batch_samples);
+/* Channel handle whose channels switch between the tune mode and FFT-acquire LIVE: every "FUNcube<idx>" tab's own "FFT/Tune"
+ * button (FUNcubeBPSKDemod.actionPerformed, :165-190), which works while audio runs.  Arguments, stream numbering
+ * (i * nchannels + c), getters, pack_slots, the slot layout, receive_*, batch_i16 / batch_f32 and the per-channel calls are
+ * jsdr_bpsk_create_mode_channels'; do_fft[c] / do_up[c] are the INITIAL modes.  Handles from the two older creators behave
+ * exactly as before, every refusal and message included.  What differs here:
+ *   The frame must be one FFT-acquire takes (416 samples and more), whatever the initial modes.
+ *   Everything a switch needs per channel and stream is allocated and zeroed at creation, for every channel (the FFT state
+ *     rows, the seam's copies, the tuner state of channels that start in FFT-acquire): a switch allocates nothing per stream.
+ *     The per-input three-phase scratch is cut for the bands in use; an action that changes them ("FFT/Tune", "Track high")
+ *     cuts it again, and is refused with the handle unchanged if that cannot be had.
+ *   set_channel_mode(c, do_fft, do_up) with a do_fft other than the channel's current one is that tab's "FFT/Tune" action:
+ *     doFFT changes, tuPhaseInc is recomputed, dmMaxCorr = 0 on that channel's streams, nothing else is reset and no other
+ *     channel is touched.  While a channel acquires its tuPhase stands still and carries on from there when it returns to
+ *     the tune mode.  set_mode / reconfigure apply to every channel, each switching or not by its own current mode.  The action
+ *     takes effect from the next call, whose streams of that channel carry the seam, on every input: the down-sampler history
+ *     crosses it exactly, in both directions (tune -> FFT-acquire: the tune path's I and Q columns; FFT-acquire -> tune: the
+ *     FFT path's doubles).  Several channels may carry a seam in one call, in different directions.  A switch that is switched
+ *     back before any call cancels the seam; each action still zeroes dmMaxCorr.
+ *   A call is whole frames whenever at least one channel is in FFT-acquire for it (a channel that just switched to it
+ *     included); a call in which a channel carries the FFT-acquire -> tune seam needs at least 26 samples.
+ *   Results: stream (i, c) is bit-identical to an ordinary handle created with channel c's initial (tuning, do_fft, do_up),
+ *     fed input i in the same calls and given jsdr_bpsk_set_mode / jsdr_bpsk_set_tuning at the same points -- bits, FEC rc /
+ *     bit index / bytes, the ten counters, the 18 state doubles and the (fi, fq) trace, through both seams, int16 and float input.
+ *   A call that carries no seam launches exactly what a jsdr_bpsk_create_mode_channels handle of the current configuration
+ *     launches; jsdr_bpsk_front_kernel and jsdr_bpsk_acq_last_launch mean what they mean there.  On a seam call
+ *     jsdr_bpsk_acq_last_launch counts the same frames as a steady call of the new configuration: the tune -> FFT-acquire seam
+ *     re-runs no frame (it forms the Q rail of the few outputs that reach into the tune path's history from the Q column, in
+ *     one small kernel behind the channel's edges), and the FFT-acquire -> tune seam is a tune-mode front end
+ *     (jsdr_bpsk_front_kernel: "k_front_split" when no other front end ran in the call).
+ *   After "Track high" on a channel that has run FFT-acquire frames in the other band, that channel's frames go through the
+ *     ordinary handle's one-kernel front end until a frame's peak has moved its centre bin into the new band (the bins around
+ *     the carried one are not in the three-phase rows of one band); such a call waits for that kernel, and
+ *     jsdr_bpsk_acq_last_launch counts the three-phase launches alone (a tune -> FFT-acquire seam in such a call runs the
+ *     channel's first frame twice, as the ordinary handle's does).  Frames only the any-frame passes take keep the
+ *     three-phase launches and their rows.
+ * JSDR_ERR, the handle and its pending seams unchanged, each checked before any device work: a frame FFT-acquire cannot take,
+ * a call that is not whole frames where it must be, fewer than 26 samples with a pending FFT-acquire -> tune seam,
+ * set_variant(FAST), snapshot_read when nchannels > 1, a channel out of range, a non-finite tuning.  Not covered:
+ * jsdr_group_*, the FAST variant, JNI / Java classes, a per-channel snapshot, switching on handles of the two older creators. */
+int jsdr_bpsk_create_live_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
                                    const double *tuning_hz, const int *do_fft, const int *do_up, int64_t max_batch_samples);
 int jsdr_bpsk_acq_last_launch(jsdr_bpsk *h, int64_t *fwd_frames, int64_t *inv_frames);
 int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels);

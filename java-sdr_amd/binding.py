@@ -620,9 +620,11 @@ class BpskChannels(Bpsk):
     """`ninputs` inputs x len(tunings) independently tuned FUNcubeBPSKDemod instances (jsdr.java:479-483's nfcs tabs fed the
     same audio).  Channel c of input i is stream i * nchannels + c; every getter takes (input, channel)."""
 
-    def __init__(self, rate, blen, tunings, do_up=None, ninputs=1, max_batch_samples=None, size=4, do_fft=None):
+    def __init__(self, rate, blen, tunings, do_up=None, ninputs=1, max_batch_samples=None, size=4, do_fft=None, live=False):
         """do_fft (per channel, fixed at creation): the channels that run FFT-acquire, each searching the band its do_up names
-        (jsdr_bpsk_create_mode_channels); None: jsdr_bpsk_create_channels, every channel in the tune mode"""
+        (jsdr_bpsk_create_mode_channels); None: jsdr_bpsk_create_channels, every channel in the tune mode.
+        live=True: jsdr_bpsk_create_live_channels -- do_fft (None: all 0) gives the initial modes, and set_channel_mode /
+        set_mode / reconfigure switch a channel between the modes between calls"""
         tunings = [float(t) for t in tunings]
         self.samples = blen // size
         self.ninputs = ninputs
@@ -632,6 +634,12 @@ class BpskChannels(Bpsk):
         self.h = C.c_void_p()
         tu = (C.c_double * max(self.nchannels, 1))(*tunings)
         up = None if do_up is None else (C.c_int * max(self.nchannels, 1))(*[int(v) for v in do_up])
+        if live:
+            ff = None if do_fft is None else (C.c_int * max(self.nchannels, 1))(*[int(v) for v in do_fft])
+            _check(lib().jsdr_bpsk_create_live_channels(C.byref(self.h), rate, self.samples, ninputs, self.nchannels,
+                                                        tu if tunings else None, ff, up, C.c_int64(self.max_batch)),
+                   "jsdr_bpsk_create_live_channels")
+            return
         if do_fft is not None:
             ff = (C.c_int * max(self.nchannels, 1))(*[int(v) for v in do_fft])
             _check(lib().jsdr_bpsk_create_mode_channels(C.byref(self.h), rate, self.samples, ninputs, self.nchannels,

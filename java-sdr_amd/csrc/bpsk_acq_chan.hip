@@ -12,6 +12,9 @@
 //                    dm_stride, a row stride of nch * dm_stride and the FFT state kept channel-major, stream index s of such a launch
 //                    IS input s -- the kernels read their input's rows under their channel's band and write their stream's dm row,
 //                    centre bins, edges and state.  Per-stream work is the ordinary handle's, instruction for instruction.
+//   the seam        a live channel handle (jsdr_bpsk_create_live_channels), a channel's first call after tune -> FFT-acquire:
+//                    k_acq_edges_seam below, behind that channel's k_acq_edges in the call's first launch, forms the Q rail of the
+//                    outputs whose windows reach into the tune path's history from its Q column.
 // A both-band row holds the bins in natural order, so every channel gathers from it as a lower-band stream does (offset c - 102):
 // the upper band's centre bins end at n/2 - 75, inside the row.
 //
@@ -276,6 +279,34 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acqc_fwd(AcqcFwdArgs ca
     }
 }
 
+// ============================================================================================================= the seam's edges
+// jsdr_bpsk_create_live_channels, the first call of a channel after it switched tune -> FFT-acquire.  dsBuf then holds the tune
+// path's last 26 samples, distinct I and Q columns, and the first outputs of the call's first frame -- those whose 27-tap windows
+// reach back into it, at most 26 / D + 1 -- are RxDownSample(re, re) over (I column | frame) on the I rail and (Q column | frame) on
+// the Q rail (:461-463, :479-492).  The channel's launches have run with the I column in FftFrontState::hist (k_chan_seam_hist),
+// so every fi is right and k_acq_edges has formed those outputs' Q rail from the I column too; this kernel forms it again from the
+// Q column: k_acq_edges' window loop over the same 26 head samples of frame 0 (still in the launch's scratch: it runs behind the
+// channel's k_acq_edges of the call's FIRST launch) and qcol in the history's place, written to .y alone.  One block per stream
+// of the channel (= input), one thread per output.
+__global__ __launch_bounds__(64) void k_acq_edges_seam(AcqArgs a, const double *qcol, int J)
+{
+    const int s = blockIdx.x, j = threadIdx.x;
+    const int e = (int)a.first_out + a.decim * j;  // the sample of frame 0 whose arrival completes output j
+    if (j >= J || e >= 26 || e >= a.n || j >= (int)a.nds) return;
+    const double HOWARD = 0.9 * 32768.0;
+    const double *head = a.edges + (long long)s * a.F * 52;  // frame 0 of the launch is frame 0 of the call (a.f0 == 0)
+    const double *prev = qcol + (long long)s * 26;
+    double fq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 27; k++) {  // newest first (:479-483)
+        const int i = e - k;
+        const double x = i >= 0 ? head[i] : prev[26 + i];
+        fq += x * ds_tap(k);
+    }
+    const double ov = fq * HOWARD;
+    a.dm[(long long)s * a.dm_stride + 64 + j].y = ov * a.vco_cs[j].y;
+}
+
 // ============================================================================================================= host
 size_t acq3c_frame_bytes(int n, int band_mask, bool generic)
 {
@@ -430,6 +461,11 @@ int launch_acq3_chan(const FftFrontArgs &fa, AcqChanArgs &ca, unsigned char *scr
                     return JSDR_ERR;
             }
             ca.inv_frames += (long long)a.S * a.F;
+            if (f0 == 0 && ca.seam_q[k] != nullptr && ca.seam_J > 0) {
+                // the channel's first call after tune -> FFT-acquire: the Q rail of the outputs that reach into the tune path's history
+                hipLaunchKernelGGL(k_acq_edges_seam, dim3((unsigned)a.S), dim3(64), 0, st, a, ca.seam_q[k], ca.seam_J);
+                JSDR_LAUNCH_CHECK();
+            }
         }
     }
     return JSDR_OK;

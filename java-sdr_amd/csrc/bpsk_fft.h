@@ -229,6 +229,10 @@ struct AcqChanArgs {
     int chan[16] = {0};        // ... which they are ...
     int up[16] = {0};          // ... and the band each searches (doUp)
     FftFrontState *st = nullptr;  // [nch][nin]: CHANNEL-major, so that one channel's streams are consecutive
+    // a live channel handle's call in which FFT channel k carries the tune -> FFT-acquire seam: the Q column of the tune path's
+    // history, [nin][26] (k_chan_seam_hist), and the outputs of the call's first frame whose windows reach into it (k_acq_edges_seam)
+    const double *seam_q[16] = {nullptr};
+    int seam_J = 0;
     long long fwd_frames = 0, inv_frames = 0;  // out: frames transformed forward / inverted by the call
     const char *fwd_name = "";                 // out: the forward kernel
 };

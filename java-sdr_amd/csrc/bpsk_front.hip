@@ -5,6 +5,7 @@
 //   k_front_any   : any decimation;  k_front_split: a call that straddles the tuner's sign test (after a retune)
 //   k_hist_in, k_hist_convert : the 26-sample input history between calls
 //   k_seam_hist, k_seam_q     : jsdr_bpsk_set_mode, tune -> FFT-acquire
+//   k_chan_seam_hist          : the same seam on one channel of a live channel handle (jsdr_bpsk_create_live_channels)
 // and their launchers (bpsk_kernels.h).
 //
 // One of the four units of the tune-mode pipeline, which is cut by kernel family so that an edit to one family recompiles
@@ -392,6 +393,33 @@ __global__ __launch_bounds__(64) void k_seam_q(double2 *dm, long long dm_stride,
     if (j < J) dm[(long long)s * dm_stride + 64 + j].y = dm2[(long long)s * dm2_stride + 64 + j].y;
 }
 
+// jsdr_bpsk_create_live_channels, tune -> FFT-acquire on ONE channel: k_seam_hist on the channel geometry.  One block per INPUT:
+// the input's raw 26-sample history (kept per input on every call) mixed with that channel's 26 history indices exactly as
+// k_chan_front mixes them -- 9-bit indices into sc9, whose entry 256 is (1.0, 1.0): x * 1.0 == x, the pass-through of :395 -- the
+// I column into the channel's rows of the FFT state (channel-major: st is the channel's first row), the Q column into the copy
+// k_acq_edges_seam reads.  avePeakPower, aveCentreBin and centreBin stay as the channel's last FFT-acquire frame left them.
+__global__ __launch_bounds__(32) void k_chan_seam_hist(const int2 *hist, int is_float, const double *sc9, ChanSeamHist sh,
+                                                       FftFrontState *st, double *qcol)
+{
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (t < 26) {
+        const int2 hv = hist[(long long)i * 32 + t];
+        double di, dq;
+        if (is_float) {
+            di = (double)__int_as_float(hv.x);
+            dq = (double)__int_as_float(hv.y);
+        } else {
+            di = (double)i16_to_float_java((int)(short)(hv.x & 0xffff));
+            dq = (double)i16_to_float_java(hv.x >> 16);
+        }
+        const int k = sh.k9[t];
+        di = di * sc9[k];
+        dq = dq * sc9[257 + k];
+        st[i].hist[t] = di;
+        qcol[(long long)i * 26 + t] = dq;
+    }
+}
+
 // keep the 26 most recent inputs (DC-corrected int16 pair, or the float pair) for the next call
 __global__ void k_hist_in(HistArgs a)
 {
@@ -521,6 +549,13 @@ int launch_seam_hist(const int2 *hist, int is_float, const double *sincos, const
 int launch_seam_q(double2 *dm, long long dm_stride, const double2 *dm2, long long dm2_stride, int J, int nstreams, hipStream_t st)
 {
     hipLaunchKernelGGL(k_seam_q, dim3((unsigned)nstreams), dim3(64), 0, st, dm, dm_stride, dm2, dm2_stride, J);
+    return launched();
+}
+
+int launch_chan_seam_hist(const int2 *hist, int is_float, const double *sc9, const ChanSeamHist &sh, FftFrontState *st, double *qcol,
+                          int ninputs, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_chan_seam_hist, dim3((unsigned)ninputs), dim3(32), 0, stream, hist, is_float, sc9, sh, st, qcol);
     return launched();
 }
 

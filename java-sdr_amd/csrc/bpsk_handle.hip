@@ -58,7 +58,11 @@ struct Schedule {
 struct BpskChan {
     double tuning = 0.0, tuPhase = 0.0, tuPhaseInc = 0.0;
     int do_up = 0;
-    int do_fft = 0;                  // jsdr_bpsk_create_mode_channels: the channel runs FFT-acquire (fixed at creation)
+    int do_fft = 0;                  // jsdr_bpsk_create_mode_channels: the channel runs FFT-acquire (fixed at creation; a live
+                                     // channel handle's "FFT/Tune" action changes it)
+    int seam = 0;                    // live channel handle: the channel's first call after a switch is still to come (SEAM_*)
+    int cb_band = -1;                // ... the band (doUp) its FFT state's centreBin was last settled in, -1: no FFT-acquire frame yet
+    std::vector<unsigned short> k9x; // ... its FFT -> tune call's table for k_front_split: [26 + L], the history passed through
     unsigned short khist[26] = {0};  // indices of the 26 samples before the next call
     // the schedule last computed for this channel, keyed by the state it started from
     bool valid = false;
@@ -239,6 +243,11 @@ struct jsdr_bpsk {
     bool mode_chan = false;
     int nfftch = 0;
     long long acq_fwd_frames = 0, acq_inv_frames = 0;  // jsdr_bpsk_acq_last_launch
+    // jsdr_bpsk_create_live_channels: a channel's mode changes live.  fft_state has every channel's rows from creation on, seam_q
+    // the Q columns of the tune -> FFT seam ([nch][nin][26], beside fft_state's I columns); acq_mask: the bands acq_scratch is cut for
+    bool live_chan = false;
+    DevBuf<double> seam_q;
+    int acq_mask = 0;
 };
 
 // whether a stream runs FFT-acquire (state doubles 6 / 7 and counter centreBin are live), and where its FftFrontState sits
@@ -1024,6 +1033,100 @@ static long long chan_vco(jsdr_bpsk *h, long long L, bool *fresh)
     return (long long)h->h_kvco.size();
 }
 
+// the bands the FFT-acquire channels search (bit 0: lower, bit 1: upper): what the three-phase scratch is cut for
+static int chan_band_mask(const jsdr_bpsk *h)
+{
+    int mask = 0;
+    for (int c = 0; c < h->nch; c++)
+        if (h->chan[c].do_fft) mask |= h->chan[c].do_up ? 2 : 1;
+    return mask;
+}
+
+// A live channel handle, "Track high" on a channel that has run FFT-acquire frames in the other band: until a frame's peak moves
+// it (:447-450) the channel's centreBin is the other band's (clamped to this band's end, :444-445), and the 204 bins around it
+// (:458) are not all in the rows the three-phase forward kernels keep of ONE band -- [0, n/4 + 28), or [0, 204) and
+// [n/4 - 26, n/2 + 28): they hold what the rule can produce in that band.  Such a channel's frames go through the ordinary
+// handle's one-kernel front end, which has the whole spectrum in LDS, over the channel's streams (one an input, rows strided as
+// the per-channel launches stride them), and the call then waits for it and reads the centre bins: once every input's gathers
+// inside the band's rows the channel is back in the three-phase launches.  Frames that only the any-frame passes take have no
+// such kernel: they stay in the three-phase launches.
+enum FftFront { FRONT_POW2, FRONT_FFTM, FRONT_FFT2X, FRONT_GEN, FRONT_NONE };
+static FftFront fft_front_kind(int n, int decim, bool chan_form, int force_gen);
+
+static bool chan_cb_foreign(const jsdr_bpsk *h, int c)
+{
+    return h->live_chan && h->chan[c].cb_band >= 0 && h->chan[c].cb_band != (h->chan[c].do_up ? 1 : 0);
+}
+
+static bool chan_fused_ok(const jsdr_bpsk *h)
+{
+    return !h->gen_plan.on && fft_front_kind(h->nsf, h->decim, false, -1) == fft_front_kind(h->nsf, h->decim, true, -1);
+}
+
+static int chan_fused_front(jsdr_bpsk *h, const FftFrontArgs &xa, int c, bool names_call, bool hist_float, hipStream_t st)
+{
+    BpskChan &cc = h->chan[c];
+    const int S = h->nin, n = h->nsf;
+    FftFrontArgs x1 = xa;
+    x1.do_up = cc.do_up;
+    x1.st = h->fft_state.p + (size_t)c * (size_t)S;
+    x1.dm = h->dm.p + (long long)c * h->dm_stride;
+    x1.dm_stride = h->dm_stride * h->nch;
+    x1.phase_clk = nullptr;
+    auto front = [&](const FftFrontArgs &x) {
+        return h->fft_2x ? launch_front_fft2x(x, h->fm_np, h->fm_rad, h->fm_off, h->fm_off1, h->fft2x_ek.p, h->fft2x_r0.p, S, st)
+                         : (h->fft_mixed ? launch_front_fftm(x, h->fm_np, h->fm_rad, h->fm_off, h->fm_off1, h->fft2x_ek.p, S, st)
+                                         : launch_front_fft(x, S, st));
+    };
+    const bool seam = cc.seam == SEAM_TO_FFT;
+    if (seam) {
+        // the call also carries the channel's tune -> FFT-acquire seam: the ordinary handle's way -- the I column into the channel's
+        // state rows, a copy of those rows with the Q column (fft_state2's first rows), and below frame 0 once more from the copy
+        // into dm2's rows, whose Q rail k_seam_q takes for the outputs that reach back
+        ChanSeamHist sh;
+        memcpy(sh.k9, cc.khist, sizeof(sh.k9));
+        double *qcol = h->seam_q.p + (size_t)c * (size_t)S * 26;
+        if (launch_chan_seam_hist(h->hist_in[h->hist_cur].p, hist_float ? 1 : 0, h->sincos9.p, sh, x1.st, qcol, S, st) != JSDR_OK) return JSDR_ERR;
+        JSDR_HIP_TRY(hipMemcpyAsync(h->fft_state2.p, x1.st, sizeof(FftFrontState) * (size_t)S, hipMemcpyDeviceToDevice, st));
+        unsigned char *hist2 = reinterpret_cast<unsigned char *>(h->fft_state2.p) + offsetof(FftFrontState, hist);
+        JSDR_HIP_TRY(hipMemcpy2DAsync(hist2, sizeof(FftFrontState), qcol, sizeof(double) * 26, sizeof(double) * 26, (size_t)S,
+                                      hipMemcpyDeviceToDevice, st));
+    }
+    {
+        ProfScope ps(h, PK_FRONT, st);
+        const char *name = h->fft_2x ? "k_front_fft2x" : (h->fft_mixed ? (fftm_pairs(x1.n, x1.nframes) ? "k_front_fftm2" : "k_front_fftm") : "k_front_fft");
+        if (names_call) h->front_name = name;  // (no three-phase launch ran in the call)
+        if (front(x1) != JSDR_OK) return JSDR_ERR;
+        if (seam) {
+            const int D = h->decim, fo = (int)x1.first_out;
+            const long long nds1 = fo < n ? (long long)((n - 1 - fo) / D + 1) : 0;  // outputs of frame 0
+            long long J = fo <= 25 ? (long long)((25 - fo) / D + 1) : 0;          // outputs whose windows reach back
+            if (J > nds1) J = nds1;
+            if (J > x1.nds) J = x1.nds;
+            if (J > 0) {
+                FftFrontArgs x2 = x1;
+                x2.nframes = 1;
+                x2.st = h->fft_state2.p;
+                x2.dm = h->dm2.p;
+                x2.dm_stride = h->dm2_stride;
+                x2.nds = nds1;
+                if (front(x2) != JSDR_OK) return JSDR_ERR;
+                if (launch_seam_q(x1.dm, x1.dm_stride, h->dm2.p, h->dm2_stride, (int)J, S, st) != JSDR_OK) return JSDR_ERR;
+            }
+        }
+    }
+    JSDR_HIP_TRY(hipStreamSynchronize(st));
+    std::vector<FftFrontState> fs((size_t)S);
+    JSDR_HIP_TRY(hipMemcpy(fs.data(), x1.st, sizeof(FftFrontState) * (size_t)S, hipMemcpyDeviceToHost));
+    bool settled = true;
+    for (int i = 0; i < S; i++) {
+        const int b = fs[(size_t)i].centreBin;
+        settled = settled && (cc.do_up ? (b == 102 || (b >= n / 4 + 76 && b <= n / 2 - 74)) : (b >= 102 && b <= n / 4 - 74));
+    }
+    if (settled) cc.cb_band = cc.do_up ? 1 : 0;
+    return JSDR_OK;
+}
+
 // A call of a channel handle: every channel of every input through k_chan_front, then the per-stream matched filter, tail,
 // sync and FEC exactly as bpsk_run launches them for an ordinary handle of ninputs x nchannels streams.
 static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, long long stride_i16, long long L, int ic,
@@ -1035,20 +1138,34 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
                  "bpsk channels: input stride %lld too small for %lld samples", stride_i16, L);
     JSDR_REQUIRE(h->nfftch == 0 || (L % h->nsf) == 0, "bpsk channels: a handle with FFT-acquire channels needs whole frames (%lld %% %d != 0); "
                  "the handle is unchanged", L, h->nsf);
+    // a live channel handle (jsdr_bpsk_create_live_channels): the channels whose first call after a switch this is
+    int nto_tune = 0;  // (FFT-acquire -> tune; the others, tune -> FFT-acquire, are among the nfftch channels)
+    for (int c = 0; c < h->nch; c++) nto_tune += h->chan[c].seam == SEAM_TO_TUNE ? 1 : 0;
+    JSDR_REQUIRE(nto_tune == 0 || L >= 26, "bpsk channels: a channel's first tune-mode call after FFT-acquire frames needs at least 26 samples "
+                 "(the input history is rebuilt from them); the handle is unchanged");
+    if (h->nfftch > 0 && h->live_chan && h->acq_scratch.p && h->acq_mask != chan_band_mask(h)) {  // (cut for other bands: an action's
+        h->acq_scratch.release();                                                                  //  re-cut did not come about)
+        h->acq_chunk = 0;
+    }
     if (h->nfftch > 0 && !h->acq_scratch.p) {
         // the one step of the call that can fail for want of memory comes before anything of the handle has moved on
-        int mask = 0;
-        for (int c = 0; c < h->nch; c++)
-            if (h->chan[c].do_fft) mask |= h->chan[c].do_up ? 2 : 1;
+        const int mask = chan_band_mask(h);
         // (per INPUT and frame)
         if (acq_scratch_ensure(h, acq3c_frame_bytes(h->nsf, mask, h->gen_plan.on), (size_t)h->nin, 4096) != JSDR_OK) return JSDR_ERR;
+        h->acq_mask = mask;
     }
-    // the inputs' 26-sample history in the form of this call's input (only the tune-mode channels read it)
-    if (h->nfftch < h->nch) {
+    // the inputs' 26-sample history in the form of this call's input (only the tune-mode channels read it; a channel on its first
+    // tune call after FFT-acquire frames reads the FFT path's doubles instead).  A channel that switched tune -> FFT-acquire reads
+    // it once more, below, in the form it has: converted with the others' or, when no channel is left to convert it for, the form
+    // of the call that wrote it
+    const bool hist_was_float = h->hist_is_float;
+    const bool hist_read = h->nch - h->nfftch - nto_tune > 0;
+    if (hist_read) {
         if (hist_form(h, rawf_dev != nullptr, h->nin, st) != JSDR_OK) return JSDR_ERR;
     } else {
         h->hist_is_float = rawf_dev != nullptr;
     }
+    const bool seam_hist_float = hist_read ? h->hist_is_float : hist_was_float;
     const int first_out = h->decim - 1 - h->dsCnt;
     const long long g_first = h->n_ds;
     const bool first = h->n_in == 0;
@@ -1059,10 +1176,20 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     chan_schedules(h, L, first, fresh);
     if (vfresh && nds > 0)
         if (h2d_call(h, h->kvco.p, h->h_kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
-    for (int c = 0; c < h->nch; c++)
-        if (fresh[c])
-            if (h2d_call(h, h->chan[c].dev.p, h->chan[c].tab.data(), sizeof(unsigned short) * h->chan[c].tab.size(), st) != JSDR_OK)
-                return JSDR_ERR;
+    for (int c = 0; c < h->nch; c++) {
+        BpskChan &cc = h->chan[c];
+        if (cc.seam == SEAM_TO_TUNE) {
+            // k_front_split's table in the channel's device slot: the schedule's index of every sample of the call, 256 (pass-through)
+            // for the 26 history samples -- they are the FFT path's unmixed doubles.  The slot no longer holds cc.tab: see below
+            cc.k9x.resize((size_t)L + 26);
+            for (int i = 0; i < 26; i++) cc.k9x[(size_t)i] = 256;
+            for (long long n = 0; n < L; n++)
+                cc.k9x[(size_t)(26 + n)] = cc.per > 0 ? cc.tab[(size_t)((n + 26) % cc.per)] : cc.tab[(size_t)(26 + n)];
+            if (h2d_call(h, cc.dev.p, cc.k9x.data(), sizeof(unsigned short) * cc.k9x.size(), st) != JSDR_OK) return JSDR_ERR;
+        } else if (fresh[c]) {
+            if (h2d_call(h, cc.dev.p, cc.tab.data(), sizeof(unsigned short) * cc.tab.size(), st) != JSDR_OK) return JSDR_ERR;
+        }
+    }
     if (h->rx_frame_bytes) {  // receive(): the frame waits at the pinned arena's head
         JSDR_HIP_TRY(hipMemcpyAsync(h->stage_raw.p, h->pin, h->rx_frame_bytes, hipMemcpyHostToDevice, st));
         h->rx_frame_bytes = 0;
@@ -1077,10 +1204,33 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         AcqChanArgs ca;
         ca.nin = h->nin;
         ca.nch = h->nch;
+        int fused[CHAN_MAX], nfused = 0;
         for (int c = 0; c < h->nch; c++) {
             if (!h->chan[c].do_fft) continue;
+            if (chan_cb_foreign(h, c) && chan_fused_ok(h)) {
+                fused[nfused++] = c;  // (below: the centre bin it carries may gather outside its band's three-phase rows)
+                continue;
+            }
             ca.chan[ca.nfft] = c;
             ca.up[ca.nfft] = h->chan[c].do_up;
+            if (h->chan[c].seam == SEAM_TO_FFT) {
+                // the channel's first FFT-acquire call after the tune mode: dsBuf's I column into its FFT state rows, the Q column
+                // beside them (k_chan_seam_hist); the Q rail of the outputs that reach into it comes from k_acq_edges_seam, behind
+                // the channel's own edges in the call's first launch
+                ChanSeamHist sh;
+                memcpy(sh.k9, h->chan[c].khist, sizeof(sh.k9));
+                double *qcol = h->seam_q.p + (size_t)c * (size_t)h->nin * 26;
+                if (launch_chan_seam_hist(h->hist_in[h->hist_cur].p, seam_hist_float ? 1 : 0, h->sincos9.p, sh,
+                                          h->fft_state.p + (size_t)c * (size_t)h->nin, qcol, h->nin, st) != JSDR_OK)
+                    return JSDR_ERR;
+                const int D = h->decim;
+                const long long nds1 = first_out < h->nsf ? (long long)((h->nsf - 1 - first_out) / D + 1) : 0;  // outputs of frame 0
+                long long J = first_out <= 25 ? (long long)((25 - first_out) / D + 1) : 0;  // outputs whose windows reach back
+                if (J > nds1) J = nds1;
+                if (J > nds) J = nds;
+                ca.seam_q[ca.nfft] = qcol;
+                ca.seam_J = (int)J;
+            }
             ca.nfft++;
         }
         ca.st = h->fft_state.p;
@@ -1088,13 +1238,19 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         xa.do_up = 0;  // (each channel's band is in ca.up)
         AcqLaunchCtx lc;
         acq_launch_ctx(h, lc);
-        if (launch_acq3_chan(xa, ca, h->acq_scratch.p, h->acq_scratch.n, h->acq_chunk, device_cus(h), st, lc.prof, lc.plan, &h->gen_plan) != JSDR_OK)
+        if (ca.nfft > 0 &&
+            launch_acq3_chan(xa, ca, h->acq_scratch.p, h->acq_scratch.n, h->acq_chunk, device_cus(h), st, lc.prof, lc.plan, &h->gen_plan) != JSDR_OK)
             return JSDR_ERR;
         h->acq_fwd_frames = ca.fwd_frames;
         h->acq_inv_frames = ca.inv_frames;
         h->front_name = ca.fwd_name;
+        for (int k = 0; k < ca.nfft; k++)
+            if (!chan_cb_foreign(h, ca.chan[k])) h->chan[ca.chan[k]].cb_band = ca.up[k] ? 1 : 0;
+        for (int k = 0; k < nfused; k++)
+            if (chan_fused_front(h, xa, fused[k], ca.nfft == 0 && k == 0, seam_hist_float, st) != JSDR_OK) return JSDR_ERR;
     }
-    if (nds > 0 && h->nfftch < h->nch) {
+    if (h->live_chan && h->nfftch == 0) h->acq_fwd_frames = h->acq_inv_frames = 0;  // (what a handle without FFT-acquire channels reports)
+    if (nds > 0 && h->nch - h->nfftch - nto_tune > 0) {
         ChanFrontArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.raw = rawf ? reinterpret_cast<const int *>(rawf) : raw;
@@ -1103,7 +1259,7 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         fa.qc = qc;
         fa.hist = h->hist_in[h->hist_cur].p;
         for (int c = 0; c < h->nch; c++) {  // the tune-mode channels (all of them, but on a handle with FFT-acquire channels)
-            if (h->chan[c].do_fft) continue;
+            if (h->chan[c].do_fft || h->chan[c].seam == SEAM_TO_TUNE) continue;
             fa.k9[fa.nch] = h->chan[c].dev.p;
             fa.per[fa.nch] = h->chan[c].per;
             fa.chan_of[fa.nch] = c;
@@ -1122,6 +1278,40 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         if (h->nfftch == 0) h->front_name = "k_chan_front";
         if (launch_chan_front(fa, h->nin, rawf != nullptr, st) != JSDR_OK) return JSDR_ERR;
     }
+    for (int c = 0; c < h->nch && nto_tune > 0; c++) {
+        BpskChan &cc = h->chan[c];
+        if (cc.seam != SEAM_TO_TUNE) continue;
+        // the channel's first tune call after FFT-acquire frames: k_front_split over its streams (one per input), the double history
+        // of its FFT state rows (I == Q, unmixed) in the raw one's place, its dm rows addressed as the per-channel FFT launches
+        // address them
+        if (nds > 0) {
+            FrontArgs fs;
+            fs.raw = raw;
+            fs.rawf = rawf;
+            fs.stride_pairs = stride_pairs;
+            fs.nsamples = L;
+            fs.ic = ic;
+            fs.qc = qc;
+            fs.mix = 1;
+            fs.ktu = nullptr;
+            fs.kvco = h->kvco.p;
+            fs.sincos = h->sincos.p;
+            fs.hist = h->hist_in[h->hist_cur].p;
+            fs.dm = h->dm.p + (long long)c * h->dm_stride;
+            fs.dm_stride = h->dm_stride * h->nch;
+            fs.ds_dbg = nullptr;
+            fs.nds = nds;
+            fs.first_out = first_out;
+            fs.tcs = nullptr;
+            fs.tper = 0;
+            ProfScope ps(h, PK_FRONT, st);
+            if (h->nfftch == 0 && h->nch == nto_tune) h->front_name = "k_front_split";
+            if (launch_front_split(fs, cc.dev.p, h->sincos9.p, h->decim, h->fft_state.p + (size_t)c * (size_t)h->nin, h->nin, st) != JSDR_OK)
+                return JSDR_ERR;
+        }
+        cc.valid = false;  // (its device slot holds this call's table, not the cached schedule's)
+    }
+    for (int c = 0; c < h->nch; c++) h->chan[c].seam = SEAM_NONE;  // every pending seam has been carried
     if (run_hist_in(h, hist_args(h, raw, rawf, stride_pairs, L, ic, qc, h->nin), st) != JSDR_OK) return JSDR_ERR;  // per input
     const int yb = h->y_cur;
     if (wait_tail(h, yb, st) != JSDR_OK) return JSDR_ERR;
@@ -1470,7 +1660,6 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
 // chan_form (jsdr_bpsk_create_mode_channels): a channel handle has the three-phase front ends only, so every frame that is
 // not one of theirs (2^k of 1024 .. 8192 at a decimation of 4 and more, 9600 / 4800 / 4410) takes the any-frame passes' plan.
 // force_gen (jsdr_bpsk_create under JSDR_ACQG, tests): 1 the any-frame passes for a frame the LDS kernels take, 0 never them.
-enum FftFront { FRONT_POW2, FRONT_FFTM, FRONT_FFT2X, FRONT_GEN, FRONT_NONE };
 static FftFront fft_front_kind(int n, int decim, bool chan_form, int force_gen = -1)
 {
     const bool pow2 = n >= 1024 && n <= 8192 && (n & (n - 1)) == 0;
@@ -1811,6 +2000,7 @@ int jsdr_bpsk_destroy(jsdr_bpsk *h)
     h->sincos9.release();
     h->fft_state2.release();
     h->dm2.release();
+    h->seam_q.release();
     bpsk_debug_clocks_report();
     if (h->phase_clk.p) {
         static const char *const names_p2[8] = {"load+scatter", "forward FFT", "|X|", "boxcar+argmax", "centre-bin rule",
@@ -2515,11 +2705,36 @@ static int chan_mode_check(jsdr_bpsk *h, int ch, int do_fft, const char *who)
     return JSDR_OK;
 }
 
-static int chan_apply(jsdr_bpsk *h, int ch, const double *tuning, const int *do_up, bool zero_maxcorr, const char *who)
+// do_fft (a live channel handle only, jsdr_bpsk_create_live_channels): the "FFT/Tune" action (:180-186) on the channels it changes
+static int chan_apply(jsdr_bpsk *h, int ch, const double *tuning, const int *do_up, bool zero_maxcorr, const char *who,
+                      const int *do_fft = nullptr)
 {
     JSDR_REQUIRE(ch >= -1 && ch < h->nch, "%s: channel %d out of range (the handle has %d); the handle is unchanged", who, ch, h->nch);
     JSDR_REQUIRE(!tuning || std::isfinite(*tuning), "%s: tuning %g Hz is not finite; the handle is unchanged", who, tuning ? *tuning : 0.0);
     if (sync_last(h) != JSDR_OK) return JSDR_ERR;
+    if (h->live_chan && h->acq_scratch.p) {
+        // the three-phase scratch is cut for the bands in use, which "FFT/Tune" and "Track high" may change: re-cut now, before
+        // anything of the handle has changed -- if that cannot be had the action is refused
+        int mask = 0;
+        for (int c = 0; c < h->nch; c++) {
+            const bool acted = ch < 0 || c == ch;
+            const int f = (acted && do_fft) ? *do_fft : h->chan[c].do_fft;
+            const int u = (acted && do_up) ? *do_up : h->chan[c].do_up;
+            if (f) mask |= u ? 2 : 1;
+        }
+        if (mask != h->acq_mask) {
+            h->acq_scratch.release();  // (never both: the scratch is the handle's largest buffer)
+            h->acq_chunk = 0;
+            if (mask != 0) {
+                if (acq_scratch_ensure(h, acq3c_frame_bytes(h->nsf, mask, h->gen_plan.on), (size_t)h->nin, 4096) != JSDR_OK) {
+                    set_error("%s: the FFT-acquire scratch could not be cut again for the bands in use; the handle is unchanged (its next "
+                              "call allocates the scratch anew)", who);
+                    return JSDR_ERR;
+                }
+                h->acq_mask = mask;
+            }
+        }
+    }
     if (zero_maxcorr) {
         hipStream_t st = h->last_stream;
         if (launch_reset_maxcorr_chan(h->tail.p, h->nin, h->nch, ch, st) != JSDR_OK) return JSDR_ERR;
@@ -2533,8 +2748,19 @@ static int chan_apply(jsdr_bpsk *h, int ch, const double *tuning, const int *do_
             cc.tuPhaseInc = 2.0 * JPI * *tuning / (double)h->rate;  // :189
         }
         if (do_up) cc.do_up = *do_up;
+        if (do_fft && (*do_fft != 0) != (cc.do_fft != 0)) {
+            // the channel's first call in the new mode carries the seam; a switch back before any call cancels it.  tuPhase stands
+            // still while the channel acquires and carries on from there
+            const int want = *do_fft ? SEAM_TO_FFT : SEAM_TO_TUNE;
+            cc.seam = cc.seam != SEAM_NONE ? SEAM_NONE : want;
+            cc.do_fft = *do_fft ? 1 : 0;
+        }
     }
-    if (do_up && h->nfftch > 0 && h->acq_scratch.p) {
+    if (do_fft) {
+        h->nfftch = 0;
+        for (int c = 0; c < h->nch; c++) h->nfftch += h->chan[c].do_fft ? 1 : 0;
+    }
+    if (!h->live_chan && do_up && h->nfftch > 0 && h->acq_scratch.p) {
         // the three-phase scratch is cut for the bands in use ("Track high" on an FFT-acquire channel may change them): allocated
         // again at the next call
         h->acq_scratch.release();
@@ -2561,9 +2787,9 @@ int jsdr_bpsk_set_mode(jsdr_bpsk *h, int do_fft, int do_up)
 {
     if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_set_mode") != JSDR_OK) return JSDR_ERR;
     if (h->nch > 0) {
-        if (chan_mode_check(h, -1, do_fft, "jsdr_bpsk_set_mode") != JSDR_OK) return JSDR_ERR;
-        const int up = do_up != 0;
-        return chan_apply(h, -1, nullptr, &up, true, "jsdr_bpsk_set_mode");
+        if (!h->live_chan && chan_mode_check(h, -1, do_fft, "jsdr_bpsk_set_mode") != JSDR_OK) return JSDR_ERR;
+        const int up = do_up != 0, fft = do_fft != 0;
+        return chan_apply(h, -1, nullptr, &up, true, "jsdr_bpsk_set_mode", h->live_chan ? &fft : nullptr);
     }
     if (do_fft && !h->do_fft && fft_mode_alloc(h, fft_front_kind(h->nsf, h->decim, false), true) != JSDR_OK) return JSDR_ERR;
     return live_apply(h, h->tuning, do_fft != 0, do_up != 0, true);
@@ -2574,9 +2800,9 @@ int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
     if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
     JSDR_REQUIRE(std::isfinite(tuning_hz), "jsdr_bpsk_reconfigure: tuning %g Hz is not finite", tuning_hz);
     if (h->nch > 0) {
-        if (chan_mode_check(h, -1, do_fft, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
-        const int up = do_up != 0;
-        return chan_apply(h, -1, &tuning_hz, &up, false, "jsdr_bpsk_reconfigure");
+        if (!h->live_chan && chan_mode_check(h, -1, do_fft, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
+        const int up = do_up != 0, fft = do_fft != 0;
+        return chan_apply(h, -1, &tuning_hz, &up, false, "jsdr_bpsk_reconfigure", h->live_chan ? &fft : nullptr);
     }
     if (do_fft && !h->do_fft && fft_mode_alloc(h, fft_front_kind(h->nsf, h->decim, false), true) != JSDR_OK) return JSDR_ERR;
     return live_apply(h, tuning_hz, do_fft != 0, do_up != 0, false);
@@ -2670,6 +2896,42 @@ int jsdr_bpsk_create_mode_channels(jsdr_bpsk **out, int rate, int nsamples_per_f
     return JSDR_OK;
 }
 
+int jsdr_bpsk_create_live_channels(jsdr_bpsk **out, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                                   const double *tuning_hz, const int *do_fft, const int *do_up, int64_t max_batch_samples)
+{
+    JSDR_REQUIRE(out, "jsdr_bpsk_create_live_channels: null handle pointer");
+    *out = nullptr;
+    // every check before any device work
+    JSDR_REQUIRE(nchannels >= 1 && nchannels <= CHAN_MAX, "jsdr_bpsk_create_live_channels: nchannels %d outside 1 .. %d", nchannels, (int)CHAN_MAX);
+    JSDR_REQUIRE(ninputs >= 1 && (long long)ninputs * nchannels <= 65535, "jsdr_bpsk_create_live_channels: %d inputs x %d channels", ninputs,
+                 nchannels);
+    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_create_live_channels: null tuning array");
+    for (int c = 0; c < nchannels; c++)
+        JSDR_REQUIRE(std::isfinite(tuning_hz[c]), "jsdr_bpsk_create_live_channels: tuning of channel %d (%g Hz) is not finite", c, tuning_hz[c]);
+    JSDR_REQUIRE(rate >= 1 && nsamples_per_frame > 0, "jsdr_bpsk_create_live_channels: rate %d, frame of %d samples", rate, nsamples_per_frame);
+    // any channel may come to acquire: the frame must be one FFT-acquire takes, whatever the initial modes
+    const FftFront front = fft_front_kind(nsamples_per_frame, rate / 9600 > 0 ? rate / 9600 : 1, true);
+    if (front == FRONT_NONE) return fft_frame_refused("jsdr_bpsk_create_live_channels: a channel that may switch to FFT-acquire", nsamples_per_frame);
+    jsdr_bpsk *h = nullptr;
+    if (jsdr_bpsk_create_channels(&h, rate, nsamples_per_frame, ninputs, nchannels, tuning_hz, do_up, max_batch_samples) != JSDR_OK) return JSDR_ERR;
+    h->mode_chan = true;
+    h->live_chan = true;
+    // everything a switch needs per channel and stream, for EVERY channel, now: the FFT state rows (zeroed: Java's field
+    // initialisers) with the front end's tables, and the seam's Q columns.  (The tuner's host state and device slot of a channel
+    // that starts in FFT-acquire are jsdr_bpsk_create_channels'.)
+    if (fft_mode_alloc(h, front, true) != JSDR_OK || h->seam_q.alloc((size_t)h->nstreams * 26) != JSDR_OK || h->seam_q.zero() != JSDR_OK ||
+        hipDeviceSynchronize() != hipSuccess) {
+        jsdr_bpsk_destroy(h);
+        return JSDR_ERR;
+    }
+    for (int c = 0; c < nchannels; c++) {
+        h->chan[c].do_fft = (do_fft && do_fft[c]) ? 1 : 0;
+        h->nfftch += h->chan[c].do_fft;
+    }
+    *out = h;
+    return JSDR_OK;
+}
+
 int jsdr_bpsk_acq_last_launch(jsdr_bpsk *h, int64_t *fwd_frames, int64_t *inv_frames)
 {
     JSDR_REQUIRE(h && fwd_frames && inv_frames, "jsdr_bpsk_acq_last_launch: null argument");
@@ -2707,9 +2969,9 @@ int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up)
     }
     JSDR_REQUIRE(channel >= 0 && channel < h->nch, "jsdr_bpsk_set_channel_mode: channel %d out of range (the handle has %d); the handle "
                  "is unchanged", channel, h->nch);
-    if (chan_mode_check(h, channel, do_fft, "jsdr_bpsk_set_channel_mode") != JSDR_OK) return JSDR_ERR;
-    const int up = do_up != 0;
-    return chan_apply(h, channel, nullptr, &up, true, "jsdr_bpsk_set_channel_mode");
+    if (!h->live_chan && chan_mode_check(h, channel, do_fft, "jsdr_bpsk_set_channel_mode") != JSDR_OK) return JSDR_ERR;
+    const int up = do_up != 0, fft = do_fft != 0;
+    return chan_apply(h, channel, nullptr, &up, true, "jsdr_bpsk_set_channel_mode", h->live_chan ? &fft : nullptr);
 }
 
 int jsdr_bpsk_get_channel_control(jsdr_bpsk *h, int channel, double *tuning_hz, int *do_fft, int *do_up)

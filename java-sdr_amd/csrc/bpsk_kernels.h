@@ -67,6 +67,12 @@ struct SeamHist {
     unsigned char mhist[26];  // 1: mixed, 0: passed through
 };
 
+// jsdr_bpsk_create_live_channels, tune -> FFT-acquire on one channel (k_chan_seam_hist): that channel's 9-bit tuner indices of the
+// 26 samples before the call (256: passed through)
+struct ChanSeamHist {
+    unsigned short k9[26];
+};
+
 // k_hist_in: keep the 26 most recent inputs (DC-corrected int16 pair, or the float pair) for the next call
 struct HistArgs {
     const int *raw;
@@ -192,6 +198,9 @@ int launch_front_split(const FrontArgs &fa, const unsigned short *ktu9, const do
 int launch_seam_hist(const int2 *hist, int is_float, const double *sincos, const SeamHist &sh, FftFrontState *st, FftFrontState *st2,
                      int nstreams, hipStream_t stream);
 int launch_seam_q(double2 *dm, long long dm_stride, const double2 *dm2, long long dm2_stride, int J, int nstreams, hipStream_t st);
+// st, qcol: the channel's first row of the channel-major FFT state, and of the Q columns' copy ([ninputs][26])
+int launch_chan_seam_hist(const int2 *hist, int is_float, const double *sc9, const ChanSeamHist &sh, FftFrontState *st, double *qcol,
+                          int ninputs, hipStream_t stream);
 int launch_hist_in(const HistArgs &ha, hipStream_t st);
 int launch_hist_convert(int2 *hist, int nstreams, int to_float, int *bad, hipStream_t st);
 int launch_matched(const MatchedArgs &ma, int nstreams, hipStream_t st);
