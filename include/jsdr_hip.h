@@ -305,6 +305,42 @@ int jsdr_bpsk_create_mode_channels(jsdr_bpsk **h, int rate, int nsamples_per_fra
  * jsdr_group_*, the FAST variant, JNI / Java classes, a per-channel snapshot, switching on handles of the two older creators. */
 int jsdr_bpsk_create_live_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
                                    const double *tuning_hz, const int *do_fft, const int *do_up, int64_t max_batch_samples);
+/* Tuned handle: nstreams lock-step demodulators in the tune mode (doBufferTune, FUNcubeBPSKDemod.java:366-397), EVERY STREAM WITH
+ * ITS OWN TUNING -- each FUNcubeBPSKDemod's own bpsk-tuning and its own "Freq: +10Hz / -10Hz" actions (:173-190, :195-196), for
+ * signals that sit at different offsets and drift with Doppler.  Stream s is a demodulator created with tuning_hz[s]; all streams
+ * advance together through jsdr_bpsk_batch_i16 / jsdr_bpsk_batch_f32.  Strides, ragged call lengths, the getters, pack_slots, the
+ * slot layout and the profile calls are an ordinary handle's.  Handles from every other creator behave exactly as before.
+ *   Result: stream s is bit-identical to a one-stream handle of jsdr_bpsk_create made with (int) of its tuning, given
+ *     jsdr_bpsk_set_tuning(tuning_hz[s]) before its first sample, fed the same calls, and given jsdr_bpsk_set_tuning wherever
+ *     stream s got jsdr_bpsk_set_stream_tuning: the bits of every call, FEC rc / bit index / bytes, the ten counters, the 18 state
+ *     doubles (double 0, tuPhase, is the stream's own) and the (fi, fq) trace.
+ *   The tuner recurrence (:384-390) is walked per stream on the device, once a call ("k_tuner_walk" in the profile); the front end
+ *     is "k_front_pst" (jsdr_bpsk_front_kernel), behind it the three-kernel path.  The walk keeps tuPhase as it stands before
+ *     every 64th sample of the call: 1/8 byte per sample and stream of max_batch_samples, beside the handle's other buffers.
+ *   set_stream_tuning / set_stream_tunings (streams first .. first + count - 1): actionPerformed's tuning change (:174-189) on
+ *     those streams only -- tuning, tuPhaseInc = 2 pi tuning / rate, dmMaxCorr = 0 (also when the value is the current one);
+ *     tuPhase, all histories, the bit clock, the FEC register and the counters carry on; the other streams are not touched.  The
+ *     change takes effect from the next call; the last 26 samples keep the factors they were mixed with (the pass-through of
+ *     :395 included).  The bulk form checks every value before it applies any.
+ *   Whole-handle controls: set_tuning applies to every stream; get_control reports stream 0; set_mode(0, do_up) and
+ *     reconfigure(t, 0, do_up) store do_up (no effect in the tune mode) and treat dmMaxCorr as they do on an ordinary handle.
+ *   Tunings: any finite value below `rate`.  <= 0 follows :388-396 per stream: samples pass unmixed once that stream's
+ *     tuPhase <= 0, and 0 freezes tuPhase.  A tuning >= rate is refused: tuPhaseInc >= 2 pi, the single subtraction of :385 no
+ *     longer bounds tuPhase and the table index leaves the range in which host and device agree.
+ * JSDR_ERR, the handle unchanged, each checked before any device work: a null handle or pointer, a non-finite tuning or one
+ * >= rate, a stream or range out of bounds, do_fft = 1 by any route (set_mode, reconfigure), set_variant(FAST), receive_i16 /
+ * receive_f32 (the 1-stream form of jsdr_bpsk_create), the three per-stream calls on a handle of any other creator, and the
+ * per-channel calls (set_channel_tuning, set_channel_mode, get_channel_control) on a tuned handle.
+ * Not covered on this handle: FFT-acquire, the FAST variant, jsdr_group_*, receive_*, JNI / Java classes. */
+int jsdr_bpsk_create_tuned(jsdr_bpsk **h, int rate, int nsamples_per_frame, int nstreams,
+                           const double *tuning_hz /*[nstreams]*/, int64_t max_batch_samples);
+int jsdr_bpsk_set_stream_tuning(jsdr_bpsk *h, int stream, double tuning_hz);
+int jsdr_bpsk_set_stream_tunings(jsdr_bpsk *h, int first, int count, const double *tuning_hz);
+int jsdr_bpsk_get_stream_tuning(jsdr_bpsk *h, int stream, double *tuning_hz);
+/* host only, no device: the tuner recurrence exactly as the device walks it (CPU tests): n samples from tuPhase tu0 at tuPhaseInc
+ * tu_inc -- k9_out[i]: the table index of sample i, 0 .. 255, or 256 where the sample passes through unmixed; *tu_end: tuPhase
+ * after the last one (may be NULL) */
+int jsdr_bpsk_tuner_walk_host(double tu0, double tu_inc, int64_t n, uint16_t *k9_out, double *tu_end);
 int jsdr_bpsk_acq_last_launch(jsdr_bpsk *h, int64_t *fwd_frames, int64_t *inv_frames);
 int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels);
 int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz);

@@ -616,6 +616,45 @@ class Bpsk:
             pass
 
 
+class BpskTuned(Bpsk):
+    """len(tunings) lock-step FUNcubeBPSKDemod instances in the tune mode, every stream with its own tuning
+    (jsdr_bpsk_create_tuned): stream s is a demodulator created with tunings[s]; batches, getters and slots as Bpsk's."""
+
+    def __init__(self, rate, blen, tunings, max_batch_samples=None, size=4):
+        tunings = [float(t) for t in tunings]
+        self.samples = blen // size
+        self.nstreams = len(tunings)
+        self.max_batch = max_batch_samples or self.samples
+        self.h = C.c_void_p()
+        tu = (C.c_double * max(self.nstreams, 1))(*tunings)
+        _check(lib().jsdr_bpsk_create_tuned(C.byref(self.h), rate, self.samples, self.nstreams, tu if tunings else None,
+                                            C.c_int64(self.max_batch)), "jsdr_bpsk_create_tuned")
+
+    # actionPerformed's tuning change (:174-189) on those streams only, between calls
+    def set_stream_tuning(self, stream, tuning_hz):
+        _check(lib().jsdr_bpsk_set_stream_tuning(self.h, int(stream), C.c_double(tuning_hz)), "jsdr_bpsk_set_stream_tuning")
+
+    def set_stream_tunings(self, first, tunings):
+        tunings = [float(t) for t in tunings]
+        tu = (C.c_double * max(len(tunings), 1))(*tunings)
+        _check(lib().jsdr_bpsk_set_stream_tunings(self.h, int(first), len(tunings), tu), "jsdr_bpsk_set_stream_tunings")
+
+    def stream_tuning(self, stream):
+        t = C.c_double()
+        _check(lib().jsdr_bpsk_get_stream_tuning(self.h, int(stream), C.byref(t)), "jsdr_bpsk_get_stream_tuning")
+        return t.value
+
+
+def tuner_walk_host(tu0, inc, n):
+    """the tuner recurrence as the tuned handle's kernels walk it, on the host (no device): n samples from tuPhase tu0 at
+    tuPhaseInc inc -> (9-bit table index per sample, 256: passed through; tuPhase at the end)"""
+    k9 = np.empty(max(int(n), 1), np.uint16)
+    end = C.c_double()
+    _check(lib().jsdr_bpsk_tuner_walk_host(C.c_double(tu0), C.c_double(inc), C.c_int64(int(n)), _addr(k9), C.byref(end)),
+           "jsdr_bpsk_tuner_walk_host")
+    return k9[:int(n)], end.value
+
+
 class BpskChannels(Bpsk):
     """`ninputs` inputs x len(tunings) independently tuned FUNcubeBPSKDemod instances (jsdr.java:479-483's nfcs tabs fed the
     same audio).  Channel c of input i is stream i * nchannels + c; every getter takes (input, channel)."""

@@ -49,6 +49,7 @@ SOURCES = {
     "bpsk_fftm.hip": ["-ffp-contract=off"],
     "bpsk_acqg.hip": ["-ffp-contract=off"],
     "bpsk_chan.hip": ["-ffp-contract=off"],
+    "bpsk_pst.hip": ["-ffp-contract=off"],
     "group.hip": [],
 }
 

@@ -11,6 +11,8 @@
 #include "bpsk_fec.h"
 #include "bpsk_fft.h"
 #include "bpsk_chan.h"
+#include "bpsk_pst.h"
+#include "bpsk_tuner.h"
 #include <math.h>
 #include <cmath>
 #include <atomic>
@@ -248,6 +250,17 @@ struct jsdr_bpsk {
     bool live_chan = false;
     DevBuf<double> seam_q;
     int acq_mask = 0;
+    // tuned handle (jsdr_bpsk_create_tuned): every stream its own tuner, walked on the device once a call (bpsk_pst.hip).  The
+    // handle's own tuPhase / tuPhaseInc stay 0: build_schedule's shared parts (decimation counter, VCO schedule) are all the
+    // call takes from it
+    bool pst = false;
+    std::vector<double> pst_tuning;    // [S] each stream's tuning (the device holds its tuPhaseInc)
+    DevBuf<double> pst_tu, pst_inc;    // [S] tuPhase, tuPhaseInc
+    DevBuf<double> pst_ckpt;           // [S][pst_ckpt_stride] k_tuner_walk's checkpoints of the call
+    long long pst_ckpt_stride = 0;
+    DevBuf<unsigned short> pst_kh[2];  // [S][32] the 9-bit indices of the 26 samples before the next call, double-buffered like hist_in
+    int pst_kh_cur = 0;
+    DevBuf<int> pst_ids;               // [S] the streams an action zeroes dmMaxCorr in (k_reset_maxcorr_list)
 };
 
 // whether a stream runs FFT-acquire (state doubles 6 / 7 and counter centreBin are live), and where its FftFrontState sits
@@ -261,10 +274,10 @@ static size_t fft_state_at(const jsdr_bpsk *h, int stream)
 }
 
 enum { PK_FRONT = 0, PK_HIST, PK_MATCHED, PK_DMHIST, PK_TAIL, PK_SYNC, PK_SYNCFIN, PK_FEC, PK_FM, PK_SYNCT, PK_PREP,
-       PK_ACQ_FWD, PK_ACQ_SCAN, PK_ACQ_INV, PK_ACQ_EDGES, PK_ACQC_FWD, PK_COUNT };
+       PK_ACQ_FWD, PK_ACQ_SCAN, PK_ACQ_INV, PK_ACQ_EDGES, PK_ACQC_FWD, PK_TWALK, PK_COUNT };
 static const char *const kProfNames[PK_COUNT] = {"k_front", "k_hist_in", "k_matched", "k_dm_history", "k_tail", "k_sync",
                                                  "k_sync_fin", "k_fec_bpsk", "k_fm", "k_sync_t", "k_fm_prep",
-                                                 "k_acq_fwd", "k_acq_scan", "k_acq_inv", "k_acq_edges", "k_acqc_fwd"};
+                                                 "k_acq_fwd", "k_acq_scan", "k_acq_inv", "k_acq_edges", "k_acqc_fwd", "k_tuner_walk"};
 
 static hipEvent_t prof_event(jsdr_bpsk *h)
 {
@@ -1321,11 +1334,87 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     return JSDR_OK;
 }
 
+// ------------------------------------------------------------------------------------------- tuned handles
+// A call of a tuned handle (jsdr_bpsk_create_tuned): every stream's tuner walked on the device (k_tuner_walk), the front end fed
+// from the walk's checkpoints (k_front_pst), then the three-kernel path's k_hist_in, k_matched, k_dm_history and the side
+// section, as bpsk_run launches them.  build_schedule provides the parts every stream shares -- the decimation counter, the VCO
+// schedule, the outputs of the call; the handle's own tuner stands at 0 and its tables are not sent.
+static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, long long stride_i16, long long L, int ic, int qc,
+                   hipStream_t st)
+{
+    JSDR_REQUIRE(raw_dev || rawf_dev, "bpsk: null input");
+    JSDR_REQUIRE(L > 0 && L <= h->max_batch, "bpsk: nsamples=%lld outside (0, max_batch_samples=%lld]", L, h->max_batch);
+    JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nstreams == 1 || stride_i16 >= 2 * L),
+                 "bpsk: stream stride %lld too small for %lld samples", stride_i16, L);
+    // the previous call may have come through the other input form (before anything moves on: the conversion can refuse)
+    if (hist_form(h, rawf_dev != nullptr, h->nstreams, st) != JSDR_OK) return JSDR_ERR;
+    const int S = h->nstreams;
+    const int first_out = h->decim - 1 - h->dsCnt;
+    const long long g_first = h->n_ds;
+    const long long nds = build_schedule(h, L);
+    JSDR_REQUIRE(nds <= h->max_ds, "bpsk: internal: %lld decimated samples exceed capacity %lld", nds, h->max_ds);
+    if (!h->cache_valid) {
+        h->tab_cur ^= 1;  // (double-buffered as bpsk_run's)
+        if (nds > 0)
+            if (h2d_call(h, h->kvco.p + (size_t)h->tab_cur * (size_t)h->max_ds, h->h_kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
+        h->cache_valid = true;
+    }
+    unsigned char *kvco_p = h->kvco.p + (size_t)h->tab_cur * (size_t)h->max_ds;
+    double2 *tcs_p = h->tcs.p + (size_t)h->tab_cur * (256 + FM_TABLE_SLACK);
+    const int *raw = reinterpret_cast<const int *>(raw_dev);
+    const float2 *rawf = reinterpret_cast<const float2 *>(rawf_dev);
+    const long long stride_pairs = stride_i16 / 2;
+    {
+        TunerWalkArgs wa;
+        wa.tu = h->pst_tu.p;
+        wa.inc = h->pst_inc.p;
+        wa.ckpt = h->pst_ckpt.p;
+        wa.ckpt_stride = h->pst_ckpt_stride;
+        wa.nsamples = L;
+        wa.kh_old = h->pst_kh[h->pst_kh_cur].p;
+        wa.kh_new = h->pst_kh[h->pst_kh_cur ^ 1].p;
+        wa.nstreams = S;
+        ProfScope ps(h, PK_TWALK, st);
+        if (launch_tuner_walk(wa, st) != JSDR_OK) return JSDR_ERR;
+    }
+    if (nds > 0) {
+        PstFrontArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.raw = rawf ? reinterpret_cast<const int *>(rawf) : raw;
+        fa.stride_pairs = stride_pairs;
+        fa.ic = ic;
+        fa.qc = qc;
+        fa.hist = h->hist_in[h->hist_cur].p;
+        fa.inc = h->pst_inc.p;
+        fa.ckpt = h->pst_ckpt.p;
+        fa.ckpt_stride = h->pst_ckpt_stride;
+        fa.kh_old = h->pst_kh[h->pst_kh_cur].p;
+        fa.kvco = kvco_p;
+        fa.sc9 = h->sincos9.p;
+        fa.ds_taps = h->ds_taps_dev.p;
+        fa.dm = h->dm.p;
+        fa.dm_stride = h->dm_stride;
+        fa.nds = nds;
+        fa.first_out = first_out;
+        fa.decim = h->decim;
+        ProfScope ps(h, PK_FRONT, st);
+        h->front_name = "k_front_pst";
+        if (launch_front_pst(fa, S, rawf != nullptr, st) != JSDR_OK) return JSDR_ERR;
+    }
+    h->pst_kh_cur ^= 1;
+    if (run_hist_in(h, hist_args(h, raw, rawf, stride_pairs, L, ic, qc, S), st) != JSDR_OK) return JSDR_ERR;
+    const int yb = h->y_cur;
+    if (wait_tail(h, yb, st) != JSDR_OK) return JSDR_ERR;
+    if (nds > 0 && run_matched(h, yb, nds, g_first, st) != JSDR_OK) return JSDR_ERR;
+    return finish_call(h, yb, L, nds, g_first, first_out, ic, qc, raw, stride_pairs, kvco_p, tcs_p, st);
+}
+
 static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, long long stride_i16, long long L,
                     int ic, int qc, hipStream_t st)
 {
     JSDR_REQUIRE(h, "bpsk: null handle");
     if (h->nch > 0) return chan_run(h, raw_dev, rawf_dev, stride_i16, L, ic, qc, st);
+    if (h->pst) return pst_run(h, raw_dev, rawf_dev, stride_i16, L, ic, qc, st);
     JSDR_REQUIRE(raw_dev || rawf_dev, "bpsk: null input");
     JSDR_REQUIRE(L > 0 && L <= h->max_batch, "bpsk: nsamples=%lld outside (0, max_batch_samples=%lld]", L, h->max_batch);
     JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nstreams == 1 || stride_i16 >= 2 * L),
@@ -2001,6 +2090,12 @@ int jsdr_bpsk_destroy(jsdr_bpsk *h)
     h->fft_state2.release();
     h->dm2.release();
     h->seam_q.release();
+    h->pst_tu.release();
+    h->pst_inc.release();
+    h->pst_ckpt.release();
+    h->pst_kh[0].release();
+    h->pst_kh[1].release();
+    h->pst_ids.release();
     bpsk_debug_clocks_report();
     if (h->phase_clk.p) {
         static const char *const names_p2[8] = {"load+scatter", "forward FFT", "|X|", "boxcar+argmax", "centre-bin rule",
@@ -2181,6 +2276,8 @@ int jsdr_bpsk_last_launch(jsdr_bpsk *h, int64_t *work_items, int64_t *workgroups
 int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
 {
     JSDR_REQUIRE(h && raw_host, "jsdr_bpsk_receive_i16: null argument");
+    JSDR_REQUIRE(!h->pst, "jsdr_bpsk_receive_i16: a tuned handle (jsdr_bpsk_create_tuned) takes batches only; receive() is the 1-stream "
+                 "form of jsdr_bpsk_create");
     JSDR_REQUIRE(h->nstreams == 1 || (h->nch > 0 && h->nin == 1),
                  "jsdr_bpsk_receive_i16: handle has %d streams; receive() is the 1-stream form (or a 1-input channel handle)",
                  h->nstreams);
@@ -2207,6 +2304,8 @@ int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
 int jsdr_bpsk_receive_f32(jsdr_bpsk *h, const float *iq_host)
 {
     JSDR_REQUIRE(h && iq_host, "jsdr_bpsk_receive_f32: null argument");
+    JSDR_REQUIRE(!h->pst, "jsdr_bpsk_receive_f32: a tuned handle (jsdr_bpsk_create_tuned) takes batches only; receive() is the 1-stream "
+                 "form of jsdr_bpsk_create");
     if (h->nch > 0) {
         // a channel handle takes what IAudioHandler delivers, (float)s / 32767f values (JavaAudio.java:281-288), through the
         // int16 kernels; any other float frame is refused
@@ -2493,6 +2592,7 @@ int jsdr_bpsk_get_state(jsdr_bpsk *h, int stream, double out[18])
     }
     state_from(h, t, app, acb, out, stream);
     if (h->nch > 0) out[0] = h->chan[stream % h->nch].tuPhase;
+    if (h->pst) JSDR_HIP_TRY(hipMemcpy(&out[0], h->pst_tu.p + stream, sizeof(double), hipMemcpyDeviceToHost));
     return JSDR_OK;
 }
 
@@ -2629,6 +2729,7 @@ int jsdr_bpsk_set_variant(jsdr_bpsk *h, int variant)
     JSDR_REQUIRE(h, "jsdr_bpsk_set_variant: null handle");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || variant == JSDR_VARIANT_FAST, "jsdr_bpsk_set_variant: unknown variant %d", variant);
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || h->nch == 0, "jsdr_bpsk_set_variant: a channel handle has no fast variant");
+    JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->pst, "jsdr_bpsk_set_variant: a tuned handle has no fast variant");
     JSDR_REQUIRE(h->n_in == 0, "jsdr_bpsk_set_variant: the variant is fixed once samples have been received");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->do_fft, "jsdr_bpsk_set_variant: the fast variant covers the tune mode only");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->retuned, "jsdr_bpsk_set_variant: the fast variant has no live control, and this handle was retuned");
@@ -2649,6 +2750,7 @@ int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who)
     JSDR_REQUIRE(h, "%s: null handle", who);
     JSDR_REQUIRE(h->variant == JSDR_VARIANT_EXACT,
                  "%s: the fast variant has no live control (jsdr_bpsk_recover_uncertified replays from creation)", who);
+    JSDR_REQUIRE(!(h->pst && do_fft > 0), "%s: a tuned handle (jsdr_bpsk_create_tuned) runs in the tune mode only; the handle is unchanged", who);
     if (do_fft > 0 && !h->do_fft) {
         JSDR_REQUIRE(fft_front_kind(h->nsf, h->decim, false) != FRONT_NONE, "%s: FFT-acquire mode cannot take this handle's frame size (%d "
                      "samples: it needs 416 .. 4194304 samples whose prime factors r above 7 keep n r within 2^31); the handle is unchanged",
@@ -2773,11 +2875,47 @@ static int chan_apply(jsdr_bpsk *h, int ch, const double *tuning, const int *do_
     return JSDR_OK;
 }
 
+// A tuned handle (jsdr_bpsk_create_tuned): the tunings it takes.  At tuning >= rate tuPhaseInc >= 2 pi: the single subtraction of
+// :385 no longer bounds tuPhase, and (int) of the table index leaves the range in which the host's and the device's casts agree.
+static int pst_tuning_check(const jsdr_bpsk *h, const double *tunings, int count, int first, const char *who)
+{
+    for (int i = 0; i < count; i++)
+        JSDR_REQUIRE(std::isfinite(tunings[i]) && tunings[i] < (double)h->rate, "%s: tuning %g Hz of stream %d is not a finite value below "
+                     "the rate (%d Hz); the handle is unchanged", who, tunings[i], first + i, h->rate);
+    return JSDR_OK;
+}
+
+// actionPerformed's tuning change (:177-190) on the streams first .. first + count - 1 of a tuned handle, after the handle's
+// pending work: tuning, tuPhaseInc = 2 pi tuning / rate (:189) and, for an action, dmMaxCorr = 0 (:190) in those streams.  Their
+// tuPhase, the indices their last 26 samples were mixed with and every other piece of state carry on; the other streams are not
+// touched.  tunings: one value a stream, or null: `one` for all of them.  Every value has been checked by the caller.
+static int pst_apply(jsdr_bpsk *h, int first, int count, const double *tunings, double one, bool zero_maxcorr)
+{
+    if (sync_last(h) != JSDR_OK) return JSDR_ERR;
+    std::vector<double> inc((size_t)count);
+    for (int i = 0; i < count; i++) inc[(size_t)i] = 2.0 * JPI * (tunings ? tunings[i] : one) / (double)h->rate;  // :189
+    if (zero_maxcorr) {
+        std::vector<int> ids((size_t)count);
+        for (int i = 0; i < count; i++) ids[(size_t)i] = first + i;
+        hipStream_t st = h->last_stream;
+        JSDR_HIP_TRY(hipMemcpy(h->pst_ids.p, ids.data(), sizeof(int) * (size_t)count, hipMemcpyHostToDevice));
+        if (launch_reset_maxcorr_list(h->tail.p, h->pst_ids.p, count, st) != JSDR_OK) return JSDR_ERR;  // one launch, whatever the count
+        JSDR_HIP_TRY(hipStreamSynchronize(st));
+    }
+    JSDR_HIP_TRY(hipMemcpy(h->pst_inc.p + first, inc.data(), sizeof(double) * (size_t)count, hipMemcpyHostToDevice));
+    for (int i = 0; i < count; i++) h->pst_tuning[(size_t)(first + i)] = tunings ? tunings[i] : one;
+    return JSDR_OK;
+}
+
 extern "C" {
 
 int jsdr_bpsk_set_tuning(jsdr_bpsk *h, double tuning_hz)
 {
     if (bpsk_live_check(h, -1, "jsdr_bpsk_set_tuning") != JSDR_OK) return JSDR_ERR;
+    if (h->pst) {  // every stream
+        if (pst_tuning_check(h, &tuning_hz, 1, 0, "jsdr_bpsk_set_tuning") != JSDR_OK) return JSDR_ERR;
+        return pst_apply(h, 0, h->nstreams, nullptr, tuning_hz, true);
+    }
     JSDR_REQUIRE(std::isfinite(tuning_hz), "jsdr_bpsk_set_tuning: tuning %g Hz is not finite", tuning_hz);
     if (h->nch > 0) return chan_apply(h, -1, &tuning_hz, nullptr, true, "jsdr_bpsk_set_tuning");
     return live_apply(h, tuning_hz, h->do_fft, h->do_up, true);
@@ -2798,6 +2936,12 @@ int jsdr_bpsk_set_mode(jsdr_bpsk *h, int do_fft, int do_up)
 int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
 {
     if (bpsk_live_check(h, do_fft != 0, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
+    if (h->pst) {  // setup() on every stream: the tuning, doUp stored, dmMaxCorr kept
+        if (pst_tuning_check(h, &tuning_hz, 1, 0, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
+        if (pst_apply(h, 0, h->nstreams, nullptr, tuning_hz, false) != JSDR_OK) return JSDR_ERR;
+        h->do_up = do_up != 0;
+        return JSDR_OK;
+    }
     JSDR_REQUIRE(std::isfinite(tuning_hz), "jsdr_bpsk_reconfigure: tuning %g Hz is not finite", tuning_hz);
     if (h->nch > 0) {
         if (!h->live_chan && chan_mode_check(h, -1, do_fft, "jsdr_bpsk_reconfigure") != JSDR_OK) return JSDR_ERR;
@@ -2811,7 +2955,7 @@ int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
 int jsdr_bpsk_get_control(jsdr_bpsk *h, double *tuning_hz, int *do_fft, int *do_up)
 {
     JSDR_REQUIRE(h && tuning_hz && do_fft && do_up, "jsdr_bpsk_get_control: null argument");
-    *tuning_hz = h->tuning;
+    *tuning_hz = h->pst ? h->pst_tuning[0] : h->tuning;    // (a tuned handle reports stream 0)
     *do_fft = h->nch > 0 ? h->chan[0].do_fft : h->do_fft;  // (a channel handle reports channel 0)
     *do_up = h->do_up;
     return JSDR_OK;
@@ -2951,6 +3095,7 @@ int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels)
 int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz)
 {
     JSDR_REQUIRE(h, "jsdr_bpsk_set_channel_tuning: null handle");
+    JSDR_REQUIRE(!h->pst, "jsdr_bpsk_set_channel_tuning: a tuned handle has streams, not channels (jsdr_bpsk_set_stream_tuning); the handle is unchanged");
     if (h->nch == 0) {  // an ordinary handle is one channel
         JSDR_REQUIRE(channel == 0, "jsdr_bpsk_set_channel_tuning: channel %d out of range (the handle has 1)", channel);
         return jsdr_bpsk_set_tuning(h, tuning_hz);
@@ -2963,6 +3108,7 @@ int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz)
 int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up)
 {
     JSDR_REQUIRE(h, "jsdr_bpsk_set_channel_mode: null handle");
+    JSDR_REQUIRE(!h->pst, "jsdr_bpsk_set_channel_mode: a tuned handle has streams, not channels (jsdr_bpsk_set_mode); the handle is unchanged");
     if (h->nch == 0) {
         JSDR_REQUIRE(channel == 0, "jsdr_bpsk_set_channel_mode: channel %d out of range (the handle has 1)", channel);
         return jsdr_bpsk_set_mode(h, do_fft, do_up);
@@ -2977,6 +3123,7 @@ int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up)
 int jsdr_bpsk_get_channel_control(jsdr_bpsk *h, int channel, double *tuning_hz, int *do_fft, int *do_up)
 {
     JSDR_REQUIRE(h && tuning_hz && do_fft && do_up, "jsdr_bpsk_get_channel_control: null argument");
+    JSDR_REQUIRE(!h->pst, "jsdr_bpsk_get_channel_control: a tuned handle has streams, not channels (jsdr_bpsk_get_stream_tuning)");
     if (h->nch == 0) {
         JSDR_REQUIRE(channel == 0, "jsdr_bpsk_get_channel_control: channel %d out of range (the handle has 1)", channel);
         return jsdr_bpsk_get_control(h, tuning_hz, do_fft, do_up);
@@ -2986,6 +3133,88 @@ int jsdr_bpsk_get_channel_control(jsdr_bpsk *h, int channel, double *tuning_hz, 
     *tuning_hz = h->chan[channel].tuning;
     *do_fft = h->chan[channel].do_fft;
     *do_up = h->chan[channel].do_up;
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_create_tuned(jsdr_bpsk **out, int rate, int nsamples_per_frame, int nstreams, const double *tuning_hz,
+                           int64_t max_batch_samples)
+{
+    JSDR_REQUIRE(out, "jsdr_bpsk_create_tuned: null handle pointer");
+    *out = nullptr;
+    // every check before any device work
+    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_create_tuned: null tuning array");
+    JSDR_REQUIRE(rate >= 1 && nsamples_per_frame > 0 && nstreams > 0 && nstreams <= 65535, "jsdr_bpsk_create_tuned: bad geometry (rate %d, "
+                 "frame of %d samples, %d streams)", rate, nsamples_per_frame, nstreams);
+    for (int s = 0; s < nstreams; s++)
+        JSDR_REQUIRE(std::isfinite(tuning_hz[s]) && tuning_hz[s] < (double)rate, "jsdr_bpsk_create_tuned: tuning %g Hz of stream %d is not a "
+                     "finite value below the rate (%d Hz)", tuning_hz[s], s, rate);
+    jsdr_bpsk *h = nullptr;
+    if (jsdr_bpsk_create(&h, rate, nsamples_per_frame, 0, 0, 0, nstreams, max_batch_samples) != JSDR_OK) return JSDR_ERR;
+    h->pst = true;
+    h->use_fm = false;
+    const size_t S = (size_t)nstreams;
+    h->pst_tuning.assign(tuning_hz, tuning_hz + nstreams);
+    std::vector<double> inc(S);
+    for (size_t s = 0; s < S; s++) inc[s] = 2.0 * JPI * tuning_hz[s] / (double)rate;  // :196
+    h->pst_ckpt_stride = h->max_batch / PST_C + 1;
+    const bool ok = sincos9_ensure(h) == JSDR_OK && h->pst_tu.alloc(S) == JSDR_OK && h->pst_inc.alloc(S) == JSDR_OK &&
+                    h->pst_ckpt.alloc(S * (size_t)h->pst_ckpt_stride) == JSDR_OK && h->pst_kh[0].alloc(S * 32) == JSDR_OK &&
+                    h->pst_kh[1].alloc(S * 32) == JSDR_OK && h->pst_ids.alloc(S) == JSDR_OK && h->pst_tu.zero() == JSDR_OK &&
+                    h->pst_kh[0].zero() == JSDR_OK && h->pst_kh[1].zero() == JSDR_OK &&
+                    hipMemcpy(h->pst_inc.p, inc.data(), sizeof(double) * S, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        set_error("jsdr_bpsk_create_tuned: device allocation failed (%d streams of %lld samples)", nstreams, (long long)h->max_batch);
+        jsdr_bpsk_destroy(h);
+        return JSDR_ERR;
+    }
+    *out = h;
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_set_stream_tunings(jsdr_bpsk *h, int first, int count, const double *tuning_hz)
+{
+    if (bpsk_live_check(h, -1, "jsdr_bpsk_set_stream_tunings") != JSDR_OK) return JSDR_ERR;
+    JSDR_REQUIRE(h->pst, "jsdr_bpsk_set_stream_tunings: the handle was not made by jsdr_bpsk_create_tuned (its streams share one tuning: "
+                 "jsdr_bpsk_set_tuning); the handle is unchanged");
+    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_set_stream_tunings: null tuning array");
+    JSDR_REQUIRE(first >= 0 && count >= 1 && first < h->nstreams && count <= h->nstreams - first, "jsdr_bpsk_set_stream_tunings: streams %d .. "
+                 "%lld out of range (the handle has %d); the handle is unchanged", first, (long long)first + count - 1, h->nstreams);
+    if (pst_tuning_check(h, tuning_hz, count, first, "jsdr_bpsk_set_stream_tunings") != JSDR_OK) return JSDR_ERR;  // every value before any is applied
+    return pst_apply(h, first, count, tuning_hz, 0.0, true);
+}
+
+int jsdr_bpsk_set_stream_tuning(jsdr_bpsk *h, int stream, double tuning_hz)
+{
+    if (bpsk_live_check(h, -1, "jsdr_bpsk_set_stream_tuning") != JSDR_OK) return JSDR_ERR;
+    JSDR_REQUIRE(h->pst, "jsdr_bpsk_set_stream_tuning: the handle was not made by jsdr_bpsk_create_tuned (its streams share one tuning: "
+                 "jsdr_bpsk_set_tuning); the handle is unchanged");
+    JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_set_stream_tuning: stream %d out of range (the handle has %d); the handle "
+                 "is unchanged", stream, h->nstreams);
+    if (pst_tuning_check(h, &tuning_hz, 1, stream, "jsdr_bpsk_set_stream_tuning") != JSDR_OK) return JSDR_ERR;
+    return pst_apply(h, stream, 1, &tuning_hz, 0.0, true);
+}
+
+int jsdr_bpsk_get_stream_tuning(jsdr_bpsk *h, int stream, double *tuning_hz)
+{
+    JSDR_REQUIRE(h && tuning_hz, "jsdr_bpsk_get_stream_tuning: null argument");
+    JSDR_REQUIRE(h->pst, "jsdr_bpsk_get_stream_tuning: the handle was not made by jsdr_bpsk_create_tuned (jsdr_bpsk_get_control reports its "
+                 "one tuning)");
+    JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_stream_tuning: stream %d out of range (the handle has %d)", stream,
+                 h->nstreams);
+    *tuning_hz = h->pst_tuning[(size_t)stream];
+    return JSDR_OK;
+}
+
+// host only, no device: the tuner recurrence exactly as k_tuner_walk and k_front_pst walk it (bpsk_tuner.h) -- n samples from
+// tuPhase tu0 at tuPhaseInc tu_inc: the 9-bit table index of every sample (256: passed through) and tuPhase at the end
+int jsdr_bpsk_tuner_walk_host(double tu0, double tu_inc, int64_t n, uint16_t *k9_out, double *tu_end)
+{
+    JSDR_REQUIRE(n >= 0 && (k9_out || n == 0), "jsdr_bpsk_tuner_walk_host: %lld samples, index buffer %s", (long long)n, k9_out ? "given" : "null");
+    double tu = tu0;
+    for (int64_t i = 0; i < n; i++) k9_out[i] = (uint16_t)tuner_step(tu, tu_inc);
+    if (tu_end) *tu_end = tu;
     return JSDR_OK;
 }
 

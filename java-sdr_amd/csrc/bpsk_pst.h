@@ -1,0 +1,49 @@
+// bpsk_pst.h -- the front end of a tuned handle (jsdr_bpsk_create_tuned: every stream its own tuning), bpsk_pst.hip, as
+// bpsk_handle.hip starts it.
+#pragma once
+#include "common.h"
+#include "bpsk_kernels.h"
+
+namespace jsdr {
+
+// samples between two checkpoints of the walk: 8 bytes per PST_C samples and stream is what the tuner costs in memory
+// (1/8 byte a sample, against 4 of the int16 input)
+enum { PST_C = 64 };
+
+struct TunerWalkArgs {
+    double *tu;                    // [S] tuPhase: read at the start, the call's end value written back
+    const double *inc;             // [S] tuPhaseInc
+    double *ckpt;                  // [S][ckpt_stride]: tuPhase as it stands BEFORE sample c * PST_C of the call
+    long long ckpt_stride;
+    long long nsamples;            // L
+    const unsigned short *kh_old;  // [S][32]: the 9-bit indices of the 26 samples before the call
+    unsigned short *kh_new;        // [S][32]: ... of the 26 samples before the next one
+    int nstreams;
+};
+
+struct PstFrontArgs {
+    const int *raw;                // int16 pairs as dwords, [S][stride_pairs]; k_front_pst<true>: float2 samples
+    long long stride_pairs;
+    int ic, qc;
+    const int2 *hist;              // [S][32]: the 26 inputs before the call (k_hist_in)
+    const double *inc;             // [S]
+    const double *ckpt;            // [S][ckpt_stride], k_tuner_walk's
+    long long ckpt_stride;
+    const unsigned short *kh_old;  // [S][32]
+    const unsigned char *kvco;     // [nds] shared VCO table index
+    const double *sc9;             // cos[0..256], sin[0..256], (1.0, 1.0) at 256
+    const double *ds_taps;         // [27]
+    double2 *dm;                   // [S][dm_stride]: 64 history + nds VCO-mixed samples
+    long long dm_stride;
+    long long nds;
+    int first_out;                 // input index whose arrival completes output 0
+    int decim;
+    int nout;                      // outputs per workgroup (set by the launcher)
+};
+
+int launch_tuner_walk(const TunerWalkArgs &a, hipStream_t st);
+int launch_front_pst(const PstFrontArgs &a, int nstreams, bool f32in, hipStream_t st);
+// dmMaxCorr = 0 (:190) in the n streams ids[] names
+int launch_reset_maxcorr_list(TailState *st, const int *ids, int n, hipStream_t stream);
+
+}  // namespace jsdr

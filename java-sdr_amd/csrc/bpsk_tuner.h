@@ -1,0 +1,39 @@
+// bpsk_tuner.h -- the tuner recurrence of FUNcubeBPSKDemod.doBufferTune (:384-390), stated once for the host walk
+// (jsdr_bpsk_tuner_walk_host) and the two kernels of a tuned handle (bpsk_pst.hip: k_tuner_walk, k_front_pst).
+//
+// The operations are chan_compute's (bpsk_handle.hip), in its order: the phase moves on and wraps with ONE subtraction, and the
+// table index is the product tu * 256.0 divided by 2 pi -- multiplied, then divided, never multiplied by a reciprocal -- and
+// truncated.  Every unit that includes this is compiled with -ffp-contract=off: each operation rounds by itself, as Java's do,
+// and the device's FP64 add, multiply and divide are IEEE's, so host and device produce the same doubles and the same indices.
+// The index is 9 bits wide: 0 .. 255 are the reference's sin / cos tables, 256 is the sample the reference passes through
+// unmixed (tuPhase <= 0, :388 / :395) -- entry 256 of the kernels' table is (1.0, 1.0).
+#pragma once
+#include "common.h"
+
+namespace jsdr {
+
+constexpr double TUNER_PI = 3.14159265358979323846;  // (bpsk_handle.hip's JPI)
+
+// tuPhase += tuPhaseInc; if (tuPhase > 2 pi) tuPhase -= 2 pi   (:384-385)
+__host__ __device__ inline void tuner_advance(double &tu, double inc)
+{
+    const double two_pi = 2.0 * TUNER_PI;
+    tu += inc;
+    if (tu > two_pi) tu -= two_pi;
+}
+
+// the table index of a sample mixed at phase tu (:388-390), 256 where it passes through (:395)
+__host__ __device__ inline int tuner_k9(double tu)
+{
+    const double two_pi = 2.0 * TUNER_PI;
+    return tu > 0.0 ? (int)(tu * (double)256 / two_pi) % 256 : 256;
+}
+
+// one sample: the phase moves on, then gives the sample's index
+__host__ __device__ inline int tuner_step(double &tu, double inc)
+{
+    tuner_advance(tu, inc);
+    return tuner_k9(tu);
+}
+
+}  // namespace jsdr
