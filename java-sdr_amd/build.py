@@ -39,8 +39,10 @@ SOURCES = {
     "formats.hip": [],
     "demod.hip": ["-ffp-contract=off"],
     "demod_chan.hip": ["-ffp-contract=off"],
-    # (the handle: host code only, but its scheduler steps the reference's phase recurrences in doubles that must round as Java's do)
+    # (the handle: host code only, but tuPhaseInc and its sin / cos tables are doubles that must round as Java's do)
     "bpsk_handle.hip": ["-ffp-contract=off"],
+    # (the host scheduler: host code only, it steps the reference's phase recurrences in doubles that must round as Java's do)
+    "bpsk_sched.hip": ["-ffp-contract=off"],
     "bpsk_fft.hip": ["-ffp-contract=off"],
     # (no atomic optimiser: it turns the one-lane ticket atomicAdd into atomic + s_waitcnt vmcnt(0) + v_readfirstlane on the spot,
     #  i.e. a round trip to memory at the top of a frame for a value that is wanted a pass later)

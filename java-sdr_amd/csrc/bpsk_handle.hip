@@ -1,18 +1,22 @@
-// bpsk_handle.hip -- the jsdr_bpsk handle: the host scheduler, the stages of a call and the C ABI (include/jsdr_hip.h).
+// bpsk_handle.hip -- the jsdr_bpsk handle: the stages of a call and the C ABI (include/jsdr_hip.h).
 //
 // Host code only: no kernel is defined or launched here.  The tune-mode kernels are in bpsk_front.hip, bpsk_front_reg.hip,
 // bpsk_fm.hip and bpsk_tail.hip and are started through the launch_* functions of bpsk_kernels.h; the other kernel families
 // come in through bpsk_fft.h, bpsk_chan.h and bpsk_fec.h.  The handle fills their argument structs and calls the launchers,
 // each stage of a call in ONE function that every kind of handle (ordinary, channel, FFT-acquire channel) calls.
 //
-// Compiled with -ffp-contract=off like the kernels: the scheduler steps the reference's phase recurrences in host doubles
-// (FUNcubeBPSKDemod.java:384-390, :511-516), and every product and sum must round separately, as Java's do.
+// The input-independent schedule of a call (tuPhase, vcoPhase, dsCnt stepped in host doubles; the period search; the keys that
+// say which call a schedule serves) is bpsk_sched.hip's.  The handle holds schedules, decides when one is computed -- on the
+// calling thread, or a call ahead on a worker -- and keeps their device copies.
+//
+// Compiled with -ffp-contract=off like the kernels and the scheduler: tuPhaseInc (bpsk_tuner.h) and the sin / cos tables are
+// computed here in host doubles, and every product and sum must round separately, as Java's do.
 #include "bpsk_kernels.h"
 #include "bpsk_fec.h"
 #include "bpsk_fft.h"
 #include "bpsk_chan.h"
 #include "bpsk_pst.h"
-#include "bpsk_tuner.h"
+#include "bpsk_sched.h"
 #include <math.h>
 #include <cmath>
 #include <atomic>
@@ -38,22 +42,7 @@ static const float h_dm_half[33] = {
 using namespace jsdr;
 
 // =============================================================================================== host
-// the input-independent schedule of one call: tuner / VCO table indices per sample (FUNcubeBPSKDemod.java:384-390, :511-516)
-struct Schedule {
-    bool valid = false;
-    double tu0 = 0, vco0 = 0;  // phase state at the start of the call ...
-    int ds0 = 0;
-    long long L = -1;
-    bool first = false;        // ... which is the first of the stream (history samples are zeros)
-    unsigned char khist0[26] = {0};
-    double tu1 = 0, vco1 = 0;  // state at its end
-    int ds1 = 0, mix = 1, tper = 0;
-    int f0 = 1;                // sample 0 of the call is mixed (tuPhase > 0) ...
-    long long n0 = 0;          // ... and so is every sample before n0, none from it on (n0 = L: no crossing)
-    long long nds = 0;
-    std::vector<unsigned char> ktu, kvco;
-    std::vector<double2> tcs;
-};
+static_assert((int)SCHED_TABLE_SLACK == (int)FM_TABLE_SLACK, "the scheduler's periodic table carries what k_fm reads past one period");
 
 // one channel of a channel handle (jsdr_bpsk_create_channels): its tuner (FUNcubeBPSKDemod.java:381-390, :196) and the
 // cache of its last schedule.  The table is of 9-bit indices (256: the sample passed through unmixed, :395).
@@ -66,17 +55,8 @@ struct BpskChan {
     int cb_band = -1;                // ... the band (doUp) its FFT state's centreBin was last settled in, -1: no FFT-acquire frame yet
     std::vector<unsigned short> k9x; // ... its FFT -> tune call's table for k_front_split: [26 + L], the history passed through
     unsigned short khist[26] = {0};  // indices of the 26 samples before the next call
-    // the schedule last computed for this channel, keyed by the state it started from
-    bool valid = false;
-    double k_tu0 = 0.0, k_inc = 0.0;
-    long long k_L = -1;
-    bool k_first = false;
-    unsigned short k_hist0[26] = {0};
-    double tu1 = 0.0;                 // tuPhase at its end
-    unsigned short khist1[26] = {0};  // the indices of its last 26 samples
-    int per = 0;                      // > 0: tab holds one period (entry (n + 26) mod per); 0: tab holds 26 + L entries
-    std::vector<unsigned short> tab;
-    DevBuf<unsigned short> dev;       // the device copy of tab
+    ChanSchedule sched;              // the schedule last computed for this channel, keyed by the state it started from
+    DevBuf<unsigned short> dev;      // the device copy of sched.tab
 };
 
 struct SideJob;
@@ -90,32 +70,24 @@ struct jsdr_bpsk {
     double tuPhase = 0.0, tuPhaseInc = 0.0, vcoPhase = 0.0;
     int dsCnt = 0;
     long long n_in = 0, n_ds = 0;  // samples consumed / demodulated since creation (cntRaw, cntDS)
-    // one-entry schedule cache
-    bool cache_valid = false;
-    double c_tu0 = 0, c_vco0 = 0, c_tu1 = 0, c_vco1 = 0;
-    int c_ds0 = 0, c_ds1 = 0;
-    long long c_L = -1, c_nds = 0;
-    std::vector<unsigned char> h_ktu;  // [26 history + L]
+    // the schedule of the current call (a one-entry cache: a call from the same state takes it as it is) and the next call's,
+    // stepped on `worker` while the GPU runs the current one
+    Schedule cur, prefetch;
+    bool tables_on_device = false;     // the device copy of cur's tables (kvco, tcs; vco_cs) is the current one
     unsigned char h_khist[26] = {0};   // tuner indices of the 26 samples before the next call
-    unsigned char c_khist[26] = {0};
-    int mix = 1, c_mix = 1;
-    // live control (jsdr_bpsk_set_tuning): which side of the sign test (:388) each sample fell on
-    int c_f0 = 1;
-    long long c_n0 = 0;
-    bool retuned = false;
+    bool retuned = false;              // a live-control call has run (the fast variant's replay from creation would not see it)
     // live mode switches (jsdr_bpsk_set_mode): the FFT-acquire buffers exist (at create, or from the first switch on), the
     // first call after a switch still to come, and the second run's scratch of a tune -> FFT switch
     bool fft_ready = false;
     int seam = 0;
     DevBuf<FftFrontState> fft_state2;
     DevBuf<double2> dm2;
-    long long dm2_stride = 0;              // a live-control call has run (the fast variant's replay from creation would not see it)
+    long long dm2_stride = 0;
     unsigned char h_mhist[26] = {0};   // 1: the 26 samples before the next call were mixed, 0: passed through
     DevBuf<unsigned short> ktu9;       // k_front_split: [26 + L] 9-bit tuner index (256: pass-through)
     DevBuf<double> sincos9;            // cos[0..256], sin[0..256] with (1.0, 1.0) at 256
     std::vector<unsigned short> h_ktu9;
     int c_kshift = -1;
-    std::vector<unsigned char> h_kvco;
     // device
     DevBuf<double> sincos;
     DevBuf<unsigned char> ktu;
@@ -149,10 +121,7 @@ struct jsdr_bpsk {
     const char *front_name = "k_front";  // the front-end kernel the last call launched
     const char *tail_name = "k_tail";    // ... the tail kernel (k_tail / k_tail8) ...
     const char *fec_name = "k_fec_bpsk"; // ... and the FEC form (one wave per block, or the batch form's kernels)
-    int c_tper = 0;                // period of the cached tuner schedule (0: not periodic with a period <= 256)
-    bool ktu_uploaded = false;     // the device copy of the per-sample tuner index table matches the cached schedule
-    std::vector<double2> h_tcs;
-    Schedule prefetch;             // the next call's schedule, stepped on `worker` while the GPU runs the current call
+    bool ktu_uploaded = false;     // the device copy of the per-sample tuner index table matches cur's
     std::thread worker;
     bool prefetch_on = true;       // JSDR_SCHED_PREFETCH=0: always on the calling thread
     long long sched_sync = 0, sched_prefetched = 0;  // schedules computed on the calling thread / taken from the worker
@@ -236,10 +205,7 @@ struct jsdr_bpsk {
     // channel handle (jsdr_bpsk_create_channels): nch > 0 channels per input, stream = input * nch + channel
     int nch = 0, nin = 0;
     BpskChan *chan = nullptr;
-    bool vco_valid = false;          // the shared VCO schedule of the last call, keyed by (vcoPhase, dsCnt, L) at its start
-    double v_vco0 = 0.0, v_vco1 = 0.0;
-    int v_ds0 = 0, v_ds1 = 0;
-    long long v_L = -1;
+    VcoSchedule vco;                 // the VCO schedule of the last call, shared by every channel and input
     // jsdr_bpsk_create_mode_channels: every channel in the tune mode or in FFT-acquire, fixed at creation.  nfftch of them run
     // FFT-acquire (bpsk_acq_chan.hip); fft_state is then CHANNEL-major, [nch][nin]
     bool mode_chan = false;
@@ -331,171 +297,68 @@ static void acq_prof_mark(void *ctx, int phase, bool begin, hipStream_t st)
     }
 }
 
-static const double JPI = 3.14159265358979323846;
 enum { SEAM_NONE = 0, SEAM_TO_FFT = 1, SEAM_TO_TUNE = 2 };
 
-// FUNcubeBPSKDemod.java:384-390 / :511-516 -- advance the phase accumulators exactly as the reference does and record
-// the table index each sample will use.  Input independent: a function of the phase state at the start of the call,
-// the call's length and the configuration.  The recurrences round state-dependently (tuPhase += inc; wrap at 2 pi;
-// truncate tuPhase*256/(2 pi)), so they are stepped one sample at a time in double, mul THEN div -- on the host: a
-// single GPU lane needs ~35 cycles per link of this dependent FP64 chain (17 ms per 2^20 samples, against ~4 ms on a
-// host core), and the links cannot be spread over lanes.  What keeps it off the critical path instead: the state
-// repeats exactly for periodic configurations (cache hit, nothing computed), and for the others the schedule of the
-// NEXT call is computed on a worker thread while the GPU works on this one (compute_schedule + the prefetch below).
-static void compute_schedule(Schedule &sc, bool do_fft, double tuPhaseInc, int decim, const double *sincos)
+// what a call of L samples from the handle's present state needs of its schedule
+static ScheduleKey schedule_request(const jsdr_bpsk *h, long long L, bool first)
 {
-    const double two_pi = 2.0 * JPI;
-    const double vinc = 2.0 * JPI * 1200.0 / (double)9600;  // VCO_PHASE_INC (:88)
-    const long long L = sc.L;
-    sc.ktu.resize((size_t)L + 26);
-    memcpy(sc.ktu.data(), sc.khist0, 26);
-    sc.kvco.clear();
-    sc.kvco.reserve((size_t)(L / decim + 2));
-    double tu = sc.tu0, vco = sc.vco0;
-    int cnt = sc.ds0;
-    long long nmix = 0;
-    unsigned char *kt = sc.ktu.data() + 26;
-    for (long long n = 0; n < L; n++) {
-        int k = 0;
-        if (!do_fft) {  // doBufferFFT never runs the tuner (:406-464)
-            tu += tuPhaseInc;
-            if (tu > two_pi) tu -= two_pi;
-            if (tu > 0.0) {  // :388
-                k = (int)(tu * (double)256 / two_pi) % 256;
-                nmix++;
-            }
-        }
-        kt[n] = (unsigned char)k;
-        if (++cnt >= decim) {
-            cnt = 0;
-            vco += vinc;
-            if (vco > two_pi) vco -= two_pi;
-            sc.kvco.push_back((unsigned char)((int)(vco * (double)256 / two_pi) % 256));
-        }
-    }
-    // tuPhase > 0 holds for every sample (tuning > 0) or for none (tuning <= 0): one flag per call
-    sc.mix = (nmix == L) ? 1 : (nmix == 0 ? 0 : -1);
-    sc.f0 = sc.mix == 0 ? 0 : 1;
-    sc.n0 = L;
-    if (sc.mix < 0) {
-        // tuPhase crossed 0 inside the call (a retune, jsdr_bpsk_set_tuning): once <= 0 it is monotone, so there is exactly
-        // one crossing.  Stepped again the same way to find it (calls after a retune only).
-        double t = sc.tu0;
-        for (long long n = 0; n < L; n++) {
-            t += tuPhaseInc;
-            if (t > two_pi) t -= two_pi;
-            const int m = t > 0.0 ? 1 : 0;
-            if (n == 0) sc.f0 = m;
-            else if (m != sc.f0) {
-                sc.n0 = n;
-                break;
-            }
-        }
-    }
-    sc.tu1 = tu;
-    sc.vco1 = vco;
-    sc.ds1 = cnt;
-    sc.nds = (long long)sc.kvco.size();
-    // Is the tuner index periodic in the sample number?  (An exact 8-cycle at 12 kHz / 96 kHz.)  Candidate from the
-    // head of the table, then verified over EVERY sample of the call, history included -- at the start of a stream
-    // the 26 history samples are zeros, whose table entry does not matter.
-    sc.tper = 0;
-    if (!do_fft && sc.mix == 1) {
-        const unsigned char *k = sc.ktu.data() + (sc.first ? 26 : 0);
-        const long long len = L + (sc.first ? 0 : 26);
-        const long long head = len < 1024 ? len : 1024;
-        for (int p = 1; p <= 256 && p < len; p++) {
-            if (memcmp(k, k + p, (size_t)(head - p)) != 0) continue;
-            if (memcmp(k, k + p, (size_t)(len - p)) == 0) {
-                sc.tper = p;
-                // unwrapped table: entry e <-> samples n with (n + 26) mod p == e mod p
-                const long long off = (sc.first ? 26 : 0);  // k[i] is the index of sample n = i + off - 26
-                sc.tcs.resize((size_t)p + FM_TABLE_SLACK);
-                for (int e = 0; e < p + FM_TABLE_SLACK; e++) {
-                    const int i = (int)(((e - off) % p + p) % p);  // smallest i >= 0 with (i + off) mod p == e mod p
-                    const int kk = k[i];
-                    sc.tcs[(size_t)e] = make_double2(sincos[kk], sincos[256 + kk]);
-                }
-            }
-            break;
-        }
-    }
-    sc.valid = true;
+    ScheduleKey k;
+    k.tu0 = h->tuPhase;
+    k.inc = h->tuPhaseInc;
+    k.vco0 = h->vcoPhase;
+    k.ds0 = h->dsCnt;
+    k.decim = h->decim;
+    k.L = L;
+    k.do_fft = h->do_fft != 0;
+    k.first = first;
+    memcpy(k.khist0, h->h_khist, sizeof(k.khist0));
+    return k;
 }
 
-static bool schedule_matches(const Schedule &sc, double tu, double vco, int ds, const unsigned char *khist, long long L, bool first)
+// the handle's state moves to the end of the call h->cur describes
+static void schedule_advance(jsdr_bpsk *h)
 {
-    return sc.valid && sc.L == L && sc.tu0 == tu && sc.vco0 == vco && sc.ds0 == ds && sc.first == first &&
-           memcmp(sc.khist0, khist, 26) == 0;
+    h->tuPhase = h->cur.tu1;
+    h->vcoPhase = h->cur.vco1;
+    h->dsCnt = h->cur.ds1;
+    memcpy(h->h_khist, h->cur.ktu.data() + h->cur.key.L, 26);
 }
 
-static void schedule_key(Schedule &sc, double tu, double vco, int ds, const unsigned char *khist, long long L, bool first)
-{
-    sc.valid = false;
-    sc.tu0 = tu;
-    sc.vco0 = vco;
-    sc.ds0 = ds;
-    sc.L = L;
-    sc.first = first;
-    memcpy(sc.khist0, khist, 26);
-}
-
-// Returns the number of decimated outputs of a call of L samples and leaves its schedule in the handle.
+// Returns the number of decimated outputs of a call of L samples and leaves its schedule in h->cur.
 static long long build_schedule(jsdr_bpsk *h, long long L)
 {
-    if (h->cache_valid && h->c_L == L && h->c_tu0 == h->tuPhase && h->c_vco0 == h->vcoPhase && h->c_ds0 == h->dsCnt &&
-        memcmp(h->c_khist, h->h_khist, 26) == 0) {
-        h->tuPhase = h->c_tu1;
-        h->vcoPhase = h->c_vco1;
-        h->dsCnt = h->c_ds1;
-        h->mix = h->c_mix;
-        memcpy(h->h_khist, h->h_ktu.data() + L, 26);
-        return h->c_nds;
+    const bool first = h->n_in == 0;
+    const ScheduleKey want = schedule_request(h, L, first);
+    // (a schedule computed for a stream's first call also serves a later call from the same state)
+    if (h->tables_on_device && h->cur.valid && h->cur.key.same_call(want)) {
+        schedule_advance(h);
+        return h->cur.nds;
     }
     if (h->worker.joinable()) h->worker.join();
     Schedule &pf = h->prefetch;
-    const bool first = h->n_in == 0;
-    if (!schedule_matches(pf, h->tuPhase, h->vcoPhase, h->dsCnt, h->h_khist, L, first)) {
-        schedule_key(pf, h->tuPhase, h->vcoPhase, h->dsCnt, h->h_khist, L, first);
-        compute_schedule(pf, h->do_fft != 0, h->tuPhaseInc, h->decim, h->h_sincos.data());
+    if (!schedule_matches(pf, want)) {
+        schedule_key(pf, want);
+        compute_schedule(pf, h->h_sincos.data());
         h->sched_sync++;
     } else {
         h->sched_prefetched++;
     }
-    // adopt it (the vectors change hands: the outgoing ones become the worker's scratch)
-    h->c_tu0 = pf.tu0;
-    h->c_vco0 = pf.vco0;
-    h->c_ds0 = pf.ds0;
-    memcpy(h->c_khist, pf.khist0, 26);
-    h->h_ktu.swap(pf.ktu);
-    h->h_kvco.swap(pf.kvco);
-    if (pf.tper > 0) h->h_tcs.swap(pf.tcs);
-    h->c_tper = pf.tper;
-    h->mix = h->c_mix = pf.mix;
-    h->c_f0 = pf.f0;
-    h->c_n0 = pf.n0;
-    h->tuPhase = h->c_tu1 = pf.tu1;
-    h->vcoPhase = h->c_vco1 = pf.vco1;
-    h->dsCnt = h->c_ds1 = pf.ds1;
-    h->c_L = L;
-    h->c_nds = pf.nds;
-    memcpy(h->h_khist, h->h_ktu.data() + L, 26);
-    h->cache_valid = false;  // device copy refreshed by the caller
+    // adopt it (the structs change places: the outgoing vectors become the worker's scratch)
+    std::swap(h->cur, pf);
     pf.valid = false;
-    // the next call, assuming the same length: nothing to do if the state has come back to where this call started (the
-    // cache will hit), otherwise step it on the worker thread while the GPU runs this call
-    const bool comes_back = h->c_tu1 == h->c_tu0 && h->c_vco1 == h->c_vco0 && h->c_ds1 == h->c_ds0 &&
-                            memcmp(h->h_khist, h->c_khist, 26) == 0;
-    if (!comes_back && h->prefetch_on && L >= 65536) {  // (a short call's schedule costs less than starting a thread)
-        schedule_key(pf, h->tuPhase, h->vcoPhase, h->dsCnt, h->h_khist, L, false);
-        const bool do_fft = h->do_fft != 0;
-        const double inc = h->tuPhaseInc;
-        const int decim = h->decim;
+    h->tables_on_device = false;  // refreshed by the caller
+    const ScheduleKey from = h->cur.key;
+    schedule_advance(h);
+    // the next call, assuming the same length: nothing to do if the state has come back to where this call started (h->cur
+    // will serve it), otherwise step it on the worker thread while the GPU runs this call
+    const ScheduleKey next = schedule_request(h, L, false);
+    if (!next.same_call(from) && h->prefetch_on && L >= 65536) {  // (a short call's schedule costs less than starting a thread)
+        schedule_key(pf, next);
         const double *sincos = h->h_sincos.data();
         Schedule *dst = &pf;
-        h->worker = std::thread([dst, do_fft, inc, decim, sincos] { compute_schedule(*dst, do_fft, inc, decim, sincos); });
+        h->worker = std::thread([dst, sincos] { compute_schedule(*dst, sincos); });
     }
-    return h->c_nds;
+    return h->cur.nds;
 }
 
 // the bit clock (:581-584) must be the regular one the tail kernel assumes
@@ -587,8 +450,8 @@ static int run_side(jsdr_bpsk *h, const SideJob &j)
         ta.qc = j.qc;
         ta.decim = h->decim;
         ta.first_out = j.first_out;
-        ta.mix = h->mix;
-        ta.tper = (h->mix == 1) ? h->c_tper : 0;
+        ta.mix = h->cur.mix;
+        ta.tper = (h->cur.mix == 1) ? h->cur.tper : 0;
         ta.tcs = j.tcs_p;
         ta.kvco = j.kvco_p;
         ta.sincos = h->sincos.p;
@@ -764,8 +627,8 @@ static void acq_launch_ctx(jsdr_bpsk *h, AcqLaunchCtx &c)
 // the VCO factors of the call's outputs, the one table the FFT-acquire front ends read (:515-516)
 static void fill_vco_cs(const jsdr_bpsk *h, double2 *dst, long long nds)
 {
-    for (long long j = 0; j < nds; j++)
-        dst[j] = make_double2(h->h_sincos[h->h_kvco[(size_t)j]], h->h_sincos[256 + h->h_kvco[(size_t)j]]);
+    const std::vector<unsigned char> &kvco = h->nch > 0 ? h->vco.kvco : h->cur.kvco;  // (a channel handle keeps the VCO's alone)
+    for (long long j = 0; j < nds; j++) dst[j] = make_double2(h->h_sincos[kvco[(size_t)j]], h->h_sincos[256 + kvco[(size_t)j]]);
 }
 
 // ... through the handle's own table (the call's ordinary copy)
@@ -919,131 +782,37 @@ static int finish_call(jsdr_bpsk *h, int yb, long long L, long long nds, long lo
 }
 
 // ------------------------------------------------------------------------------------------- channel handles
-// The tuner schedule of one channel for a call of L samples from the state in its key (k_tu0, k_inc, k_hist0, first):
-// compute_schedule's tuner recurrence, step for step, with the sign test (:388) folded into the index (256: pass-through).
-// Then the shortest period p <= 256 that holds over every sample of the call (and the 26 history samples, except at the
-// stream's start, where they are zeros and their factor does not matter) -- one period is all the device needs.
-static void chan_compute(BpskChan &c, long long L, bool first)
-{
-    const double two_pi = 2.0 * JPI;
-    std::vector<unsigned short> full((size_t)L + 26);
-    memcpy(full.data(), c.k_hist0, sizeof(c.k_hist0));
-    double tu = c.k_tu0;
-    const double inc = c.k_inc;
-    unsigned short *kt = full.data() + 26;
-    for (long long n = 0; n < L; n++) {
-        tu += inc;
-        if (tu > two_pi) tu -= two_pi;
-        kt[n] = tu > 0.0 ? (unsigned short)((int)(tu * (double)256 / two_pi) % 256) : (unsigned short)256;
-    }
-    c.tu1 = tu;
-    memcpy(c.khist1, full.data() + L, sizeof(c.khist1));
-    const long long off = first ? 26 : 0;
-    const long long len = L + 26 - off;
-    const unsigned short *k = full.data() + off;
-    c.per = 0;
-    for (int p = 1; p <= 256 && p < len; p++) {
-        bool same = true;
-        for (long long i = 0; i + p < len && same; i++) same = k[i] == k[i + p];
-        if (!same) continue;
-        c.per = p;
-        c.tab.resize((size_t)p);
-        for (int e = 0; e < p; e++) c.tab[(size_t)e] = k[(((e - off) % p) + p) % p];  // the entry of the samples n + 26 == e mod p
-        break;
-    }
-    if (c.per == 0) c.tab.swap(full);
-    c.k_L = L;
-    c.k_first = first;
-    c.valid = true;
-}
-
-static bool chan_key_equal(const BpskChan &a, const BpskChan &b)
-{
-    return a.k_tu0 == b.k_tu0 && a.k_inc == b.k_inc && a.k_L == b.k_L && a.k_first == b.k_first &&
-           memcmp(a.k_hist0, b.k_hist0, sizeof(a.k_hist0)) == 0;
-}
-
-// Every channel's schedule for a call of L samples: a channel whose state has come back to where its cached schedule
-// started takes that one (a periodic tuning with a call length of whole periods: nothing to build after its first calls);
-// channels with equal keys share one computation; the rest are built in parallel, one thread per schedule (at most 16, the
-// most channels a handle has), for calls long enough to pay for the threads.  *fresh[c]: the device copy must be sent.
+// Every channel's tuner schedule for a call of L samples (bpsk_sched.hip: kept where the state has come back, shared between
+// equal keys, built in parallel), and the channels' state moved to the call's end.  *fresh[c]: the device copy must be sent.
 static void chan_schedules(jsdr_bpsk *h, long long L, bool first, bool *fresh)
 {
-    std::vector<int> lead;
-    std::vector<int> follow(h->nch, -1);
+    ChanSchedule *sched[CHAN_MAX];
+    ChanKey want[CHAN_MAX];
     for (int c = 0; c < h->nch; c++) {
         BpskChan &ch = h->chan[c];
-        fresh[c] = false;
-        if (ch.do_fft) continue;  // doBufferFFT never runs the tuner (:406-464): tuPhase stands still
-        if (ch.valid && ch.k_L == L && ch.k_first == first && ch.k_tu0 == ch.tuPhase && ch.k_inc == ch.tuPhaseInc &&
-            memcmp(ch.k_hist0, ch.khist, sizeof(ch.khist)) == 0)
-            continue;
-        ch.k_tu0 = ch.tuPhase;
-        ch.k_inc = ch.tuPhaseInc;
-        ch.k_L = L;
-        ch.k_first = first;
-        memcpy(ch.k_hist0, ch.khist, sizeof(ch.khist));
-        fresh[c] = true;
-        for (int l : lead)
-            if (chan_key_equal(h->chan[l], ch)) follow[c] = l;
-        if (follow[c] < 0) lead.push_back(c);
+        sched[c] = ch.do_fft ? nullptr : &ch.sched;  // doBufferFFT never runs the tuner (:406-464): tuPhase stands still
+        want[c].tu0 = ch.tuPhase;
+        want[c].inc = ch.tuPhaseInc;
+        want[c].L = L;
+        want[c].first = first;
+        memcpy(want[c].hist0, ch.khist, sizeof(ch.khist));
     }
-    if (lead.size() >= 2 && L >= 65536) {
-        std::vector<std::thread> pool;
-        for (int l : lead) pool.emplace_back([h, l, L, first] { chan_compute(h->chan[l], L, first); });
-        for (auto &t : pool) t.join();
-    } else {
-        for (int l : lead) chan_compute(h->chan[l], L, first);
-    }
-    h->sched_sync += (long long)lead.size();
-    for (int c = 0; c < h->nch; c++) {
-        if (follow[c] < 0) continue;
-        const BpskChan &src = h->chan[follow[c]];
-        BpskChan &ch = h->chan[c];
-        ch.tu1 = src.tu1;
-        memcpy(ch.khist1, src.khist1, sizeof(ch.khist1));
-        ch.per = src.per;
-        ch.tab = src.tab;
-        ch.valid = true;
-    }
+    h->sched_sync += chan_schedules(sched, want, h->nch, fresh);
     for (int c = 0; c < h->nch; c++) {
         BpskChan &ch = h->chan[c];
         if (ch.do_fft) continue;
-        ch.tuPhase = ch.tu1;
-        memcpy(ch.khist, ch.khist1, sizeof(ch.khist));
+        ch.tuPhase = ch.sched.tu1;
+        memcpy(ch.khist, ch.sched.khist1, sizeof(ch.khist));
     }
 }
 
-// The shared VCO schedule (:511-516): the same for every channel and input.  Left in h->h_kvco; returns the outputs of the call.
+// The shared VCO schedule (:511-516): the same for every channel and input.  Left in h->vco; returns the outputs of the call.
 static long long chan_vco(jsdr_bpsk *h, long long L, bool *fresh)
 {
-    *fresh = false;
-    if (!(h->vco_valid && h->v_L == L && h->v_vco0 == h->vcoPhase && h->v_ds0 == h->dsCnt)) {
-        const double two_pi = 2.0 * JPI;
-        const double vinc = 2.0 * JPI * 1200.0 / (double)9600;  // VCO_PHASE_INC (:88)
-        h->h_kvco.clear();
-        h->h_kvco.reserve((size_t)(L / h->decim + 2));
-        double vco = h->vcoPhase;
-        int cnt = h->dsCnt;
-        for (long long n = 0; n < L; n++) {
-            if (++cnt >= h->decim) {
-                cnt = 0;
-                vco += vinc;
-                if (vco > two_pi) vco -= two_pi;
-                h->h_kvco.push_back((unsigned char)((int)(vco * (double)256 / two_pi) % 256));
-            }
-        }
-        h->v_vco0 = h->vcoPhase;
-        h->v_ds0 = h->dsCnt;
-        h->v_L = L;
-        h->v_vco1 = vco;
-        h->v_ds1 = cnt;
-        h->vco_valid = true;
-        *fresh = true;
-    }
-    h->vcoPhase = h->v_vco1;
-    h->dsCnt = h->v_ds1;
-    return (long long)h->h_kvco.size();
+    *fresh = vco_schedule(h->vco, h->vcoPhase, h->dsCnt, h->decim, L);
+    h->vcoPhase = h->vco.vco1;
+    h->dsCnt = h->vco.ds1;
+    return (long long)h->vco.kvco.size();
 }
 
 // the bands the FFT-acquire channels search (bit 0: lower, bit 1: upper): what the three-phase scratch is cut for
@@ -1188,19 +957,16 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     bool fresh[CHAN_MAX];
     chan_schedules(h, L, first, fresh);
     if (vfresh && nds > 0)
-        if (h2d_call(h, h->kvco.p, h->h_kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
+        if (h2d_call(h, h->kvco.p, h->vco.kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
     for (int c = 0; c < h->nch; c++) {
         BpskChan &cc = h->chan[c];
         if (cc.seam == SEAM_TO_TUNE) {
             // k_front_split's table in the channel's device slot: the schedule's index of every sample of the call, 256 (pass-through)
-            // for the 26 history samples -- they are the FFT path's unmixed doubles.  The slot no longer holds cc.tab: see below
-            cc.k9x.resize((size_t)L + 26);
-            for (int i = 0; i < 26; i++) cc.k9x[(size_t)i] = 256;
-            for (long long n = 0; n < L; n++)
-                cc.k9x[(size_t)(26 + n)] = cc.per > 0 ? cc.tab[(size_t)((n + 26) % cc.per)] : cc.tab[(size_t)(26 + n)];
+            // for the 26 history samples -- they are the FFT path's unmixed doubles.  The slot no longer holds the schedule's table: see below
+            expand_k9(cc.k9x, cc.sched.tab.data(), cc.sched.per, L, nullptr, 1, L);
             if (h2d_call(h, cc.dev.p, cc.k9x.data(), sizeof(unsigned short) * cc.k9x.size(), st) != JSDR_OK) return JSDR_ERR;
         } else if (fresh[c]) {
-            if (h2d_call(h, cc.dev.p, cc.tab.data(), sizeof(unsigned short) * cc.tab.size(), st) != JSDR_OK) return JSDR_ERR;
+            if (h2d_call(h, cc.dev.p, cc.sched.tab.data(), sizeof(unsigned short) * cc.sched.tab.size(), st) != JSDR_OK) return JSDR_ERR;
         }
     }
     if (h->rx_frame_bytes) {  // receive(): the frame waits at the pinned arena's head
@@ -1274,7 +1040,7 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         for (int c = 0; c < h->nch; c++) {  // the tune-mode channels (all of them, but on a handle with FFT-acquire channels)
             if (h->chan[c].do_fft || h->chan[c].seam == SEAM_TO_TUNE) continue;
             fa.k9[fa.nch] = h->chan[c].dev.p;
-            fa.per[fa.nch] = h->chan[c].per;
+            fa.per[fa.nch] = h->chan[c].sched.per;
             fa.chan_of[fa.nch] = c;
             fa.nch++;
         }
@@ -1322,7 +1088,7 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
             if (launch_front_split(fs, cc.dev.p, h->sincos9.p, h->decim, h->fft_state.p + (size_t)c * (size_t)h->nin, h->nin, st) != JSDR_OK)
                 return JSDR_ERR;
         }
-        cc.valid = false;  // (its device slot holds this call's table, not the cached schedule's)
+        cc.sched.valid = false;  // (its device slot holds this call's table, not the cached schedule's)
     }
     for (int c = 0; c < h->nch; c++) h->chan[c].seam = SEAM_NONE;  // every pending seam has been carried
     if (run_hist_in(h, hist_args(h, raw, rawf, stride_pairs, L, ic, qc, h->nin), st) != JSDR_OK) return JSDR_ERR;  // per input
@@ -1353,11 +1119,11 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
     const long long g_first = h->n_ds;
     const long long nds = build_schedule(h, L);
     JSDR_REQUIRE(nds <= h->max_ds, "bpsk: internal: %lld decimated samples exceed capacity %lld", nds, h->max_ds);
-    if (!h->cache_valid) {
+    if (!h->tables_on_device) {
         h->tab_cur ^= 1;  // (double-buffered as bpsk_run's)
         if (nds > 0)
-            if (h2d_call(h, h->kvco.p + (size_t)h->tab_cur * (size_t)h->max_ds, h->h_kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
-        h->cache_valid = true;
+            if (h2d_call(h, h->kvco.p + (size_t)h->tab_cur * (size_t)h->max_ds, h->cur.kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
+        h->tables_on_device = true;
     }
     unsigned char *kvco_p = h->kvco.p + (size_t)h->tab_cur * (size_t)h->max_ds;
     double2 *tcs_p = h->tcs.p + (size_t)h->tab_cur * (256 + FM_TABLE_SLACK);
@@ -1438,23 +1204,23 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     JSDR_REQUIRE(nds <= h->max_ds, "bpsk: internal: %lld decimated samples exceed capacity %lld", nds, h->max_ds);
     // after a retune the call's samples, or the 26 history samples its first windows reach into, may lie on both sides of
     // the tuner's sign test (:388): those calls take k_front_split (in the steady state every flag is the call's own)
-    const int f0 = h->c_f0;  // (both paths of build_schedule leave the call's in c_f0 / c_n0)
-    const long long n0 = h->c_n0;
+    const int f0 = h->cur.f0;
+    const long long n0 = h->cur.n0;
     if (h->n_in == 0) memset(h->h_mhist, f0, 26);  // (the history of a stream's first call is zeros: either side is exact)
     bool split = false;
     if (!h->do_fft) {
-        split = h->mix < 0 || h->seam == SEAM_TO_TUNE;
+        split = h->cur.mix < 0 || h->seam == SEAM_TO_TUNE;
         for (int i = 0; i < 26 && !split; i++) split = h->h_mhist[i] != (unsigned char)f0;
     }
     // fused path (k_fm; k_fm_f32 for the float batches of jsdr_bpsk_batch_f32): a tuner schedule that is periodic with a
     // period dividing the lane span (or no tuner at all), 32-bit sample indices
     const bool std_decim = h->decim == 4 || h->decim == 5 || h->decim == 10 || h->decim == 20;  // the specialised front ends
     const int fm_rd = h->decim == 4 ? 20 : h->decim * 4;  // D * R of the k_fm instantiation
-    const bool per_ok = !h->do_fft && !split && h->mix == 1 && h->c_tper > 0 && fm_rd % h->c_tper == 0;
+    const bool per_ok = !h->do_fft && !split && h->cur.mix == 1 && h->cur.tper > 0 && fm_rd % h->cur.tper == 0;
     const bool fm_ok = h->use_fm && std_decim && !h->do_fft && !split && nds > 0 && L <= 0x3fffffffLL &&
-                       ((raw_dev && !rawf_dev) || (rawf_dev && h->f32_batch && h->variant == 0 && h->fm_edges_f32.p)) && (h->mix == 0 || per_ok);
+                       ((raw_dev && !rawf_dev) || (rawf_dev && h->f32_batch && h->variant == 0 && h->fm_edges_f32.p)) && (h->cur.mix == 0 || per_ok);
     const int kshift = 0;
-    const bool fresh = !h->cache_valid;
+    const bool fresh = !h->tables_on_device;
     if (fresh) h->ktu_uploaded = false;
     if (fresh) {
         // The VCO / tuner tables are double-buffered: the fast variant's tail (side stream) may still re-read those of
@@ -1467,10 +1233,10 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     double2 *tcs_p = h->tcs.p + (size_t)h->tab_cur * (256 + FM_TABLE_SLACK);
     // the 1 B/sample index table is only read by the kernels without the periodic table (k_front, k_front_reg<PER = false>)
     const bool reg_will_run = front_reg_enabled() && std_decim && raw_dev && !rawf_dev && L <= 0x3fffffffLL && L >= 64;
-    const bool need_ktu = !h->do_fft && !split && !fm_ok && !(per_ok && reg_will_run) && h->mix != 0;
+    const bool need_ktu = !h->do_fft && !split && !fm_ok && !(per_ok && reg_will_run) && h->cur.mix != 0;
     if (need_ktu && (!h->ktu_uploaded || kshift != h->c_kshift)) {
         h->c_kshift = kshift;
-        if (h2d_call(h, h->ktu.p + kshift, h->h_ktu.data(), (size_t)L + 26, st) != JSDR_OK) return JSDR_ERR;
+        if (h2d_call(h, h->ktu.p + kshift, h->cur.ktu.data(), (size_t)L + 26, st) != JSDR_OK) return JSDR_ERR;
         h->ktu_uploaded = true;
     }
     ScatterArgs sc;
@@ -1481,16 +1247,16 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         // the frame in the same copy and k_fm_prep scatters them (three copies were ~10 us each of a 70 us call)
         size_t total = h->rx_frame_bytes;
         const size_t o1 = (total + 63) & ~(size_t)63;
-        const size_t tcs_bytes = h->c_tper > 0 ? sizeof(double2) * h->h_tcs.size() : 0;
+        const size_t tcs_bytes = h->cur.tper > 0 ? sizeof(double2) * h->cur.tcs.size() : 0;
         const size_t o2 = (o1 + (size_t)nds + 63) & ~(size_t)63;
         if (fm_ok && fresh && nds > 0 && o2 + tcs_bytes <= h->pin_bytes && o2 + tcs_bytes <= h->stage_raw.n * sizeof(int)) {
             unsigned char *dev = reinterpret_cast<unsigned char *>(h->stage_raw.p);
-            memcpy(h->pin + o1, h->h_kvco.data(), (size_t)nds);
+            memcpy(h->pin + o1, h->cur.kvco.data(), (size_t)nds);
             sc.src[0] = dev + o1;
             sc.dst[0] = kvco_p;
             sc.bytes[0] = (int)nds;
             if (tcs_bytes) {
-                memcpy(h->pin + o2, h->h_tcs.data(), tcs_bytes);
+                memcpy(h->pin + o2, h->cur.tcs.data(), tcs_bytes);
                 sc.src[1] = dev + o2;
                 sc.dst[1] = reinterpret_cast<unsigned char *>(tcs_p);
                 sc.bytes[1] = (int)tcs_bytes;
@@ -1516,30 +1282,26 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         JSDR_HIP_TRY(hipMemcpyAsync(h->stage_raw.p, h->pin, total, hipMemcpyHostToDevice, st));
         h->rx_frame_bytes = 0;
     }
-    if (fresh && tables_sent) h->cache_valid = true;
+    if (fresh && tables_sent) h->tables_on_device = true;
     if (fresh && !tables_sent) {
         if (nds > 0)
-            if (h2d_call(h, kvco_p, h->h_kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
+            if (h2d_call(h, kvco_p, h->cur.kvco.data(), (size_t)nds, st) != JSDR_OK) return JSDR_ERR;
         if (nds > 0 && h->do_fft) {
             h->vco_cs_in_blob = false;
             if (send_vco_cs(h, nds, st) != JSDR_OK) return JSDR_ERR;
         }
-        if (h->c_tper > 0)
-            if (h2d_call(h, tcs_p, h->h_tcs.data(), sizeof(double2) * h->h_tcs.size(), st) != JSDR_OK) return JSDR_ERR;
+        if (h->cur.tper > 0)
+            if (h2d_call(h, tcs_p, h->cur.tcs.data(), sizeof(double2) * h->cur.tcs.size(), st) != JSDR_OK) return JSDR_ERR;
         // the host vectors must stay untouched until the copies ran; pageable memcpyAsync stages
         // synchronously, so they are safe to reuse on return
-        h->cache_valid = true;
+        h->tables_on_device = true;
     }
     if (split && nds > 0) {
         // k_front_split's index table: the schedule's index where the sample was mixed, 256 (pass-through) where not
         if (!h->ktu9.p && h->ktu9.alloc((size_t)h->max_batch + 26) != JSDR_OK) return JSDR_ERR;
         if (sincos9_ensure(h) != JSDR_OK) return JSDR_ERR;
-        h->h_ktu9.resize((size_t)L + 26);
-        for (int i = 0; i < 26; i++) h->h_ktu9[(size_t)i] = (h->h_mhist[i] && h->seam != SEAM_TO_TUNE) ? h->h_ktu[(size_t)i] : 256;
-        for (long long n = 0; n < L; n++) {
-            const int m = (n < n0) ? f0 : !f0;
-            h->h_ktu9[(size_t)(26 + n)] = m ? h->h_ktu[(size_t)(26 + n)] : 256;
-        }
+        // (the history of the first tune call after FFT-acquire frames is the FFT path's unmixed doubles)
+        expand_k9(h->h_ktu9, h->cur.ktu.data(), 0, L, h->seam != SEAM_TO_TUNE ? h->h_mhist : nullptr, f0, n0);
         if (h2d_call(h, h->ktu9.p, h->h_ktu9.data(), sizeof(unsigned short) * ((size_t)L + 26), st) != JSDR_OK) return JSDR_ERR;
     }
     // the 64-sample halo of VCO-mixed samples lives where the previous call's path left it
@@ -1553,7 +1315,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     fa.nsamples = L;
     fa.ic = ic;
     fa.qc = qc;
-    fa.mix = h->mix;
+    fa.mix = h->cur.mix;
     fa.ktu = h->ktu.p + kshift;
     fa.kvco = kvco_p;
     fa.sincos = h->sincos.p;
@@ -1564,7 +1326,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     fa.nds = nds;
     fa.first_out = first_out;
     fa.tcs = per_ok ? tcs_p : nullptr;
-    fa.tper = h->c_tper;
+    fa.tper = h->cur.tper;
     bool hist_done = false;  // the next call's input history has been written (k_fm_prep does it in the k_fm path)
     if (h->do_fft && nds > 0 && h->halo_in_dmh)  // (the last tune call left the matched filter's halo in dmh)
         if (move_halo(h, false, st) != JSDR_OK) return JSDR_ERR;
@@ -1654,7 +1416,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         ma.qc = qc;
         ma.edges = h->fm_edges.p;
         ma.tcs = tcs_p;
-        ma.tper = h->mix ? h->c_tper : 1;
+        ma.tper = h->cur.mix ? h->cur.tper : 1;
         ma.kvco = kvco_p;
         ma.sincos = h->sincos.p;
         ma.dmh_old = h->dmh[h->dmh_cur].p;
@@ -1703,10 +1465,10 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
             mf.rawf = fa.rawf;
             mf.edges = h->fm_edges_f32.p;
             h->front_name = "k_fm_f32";
-            if (launch_fm_f32(mf, h->decim, h->mix != 0, S, st, &h->last_fm_items, &h->last_fm_grid) != JSDR_OK) return JSDR_ERR;
+            if (launch_fm_f32(mf, h->decim, h->cur.mix != 0, S, st, &h->last_fm_items, &h->last_fm_grid) != JSDR_OK) return JSDR_ERR;
         } else {
         h->front_name = "k_fm";
-        if (launch_fm(ma, h->decim, h->mix != 0, (ic != 0) || (qc != 0), h->variant != 0, S, st, &h->last_fm_items, &h->last_fm_grid) != JSDR_OK)
+        if (launch_fm(ma, h->decim, h->cur.mix != 0, (ic != 0) || (qc != 0), h->variant != 0, S, st, &h->last_fm_items, &h->last_fm_grid) != JSDR_OK)
             return JSDR_ERR;
         }
         h->dmh_cur ^= 1;
@@ -1730,13 +1492,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         h->hist_is_float = rawf_dev != nullptr;
     }
     if (!h->do_fft) {
-        // the mix flags of the 26 samples before the next call
-        unsigned char nh[26];
-        for (int i = 0; i < 26; i++) {
-            const long long n = L - 26 + i;
-            nh[i] = n < 0 ? h->h_mhist[L + i] : (unsigned char)((n < n0) ? f0 : !f0);
-        }
-        memcpy(h->h_mhist, nh, 26);
+        mhist_advance(h->h_mhist, L, f0, n0);  // the mix flags of the 26 samples before the next call
     }
     return JSDR_OK;
 }
@@ -1881,7 +1637,7 @@ int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuni
     // so a call with more hits than this flags the stream instead of returning a truncated log)
     h->trig_cap = h->max_bits / 2600 + 4;
     if (h->trig_cap < MIN_TRIG) h->trig_cap = MIN_TRIG;
-    h->tuPhaseInc = 2.0 * JPI * (double)tuning_hz / (double)rate;  // :196
+    h->tuPhaseInc = tuner_inc((double)tuning_hz, rate);  // :196
     while ((1 << h->logn) < nsamples_per_frame) h->logn++;
     if (do_fft) h->max_batch = (h->max_batch / nsamples_per_frame) * nsamples_per_frame;
     // one stream (the receive() drop-in): nothing of another stream to run beside the tail, and the hop to the side
@@ -1945,7 +1701,7 @@ int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuni
     // tables (:159-162): Math.sin/cos are allowed 1 ulp; the host libm stands in (DESIGN.md "tables")
     std::vector<double> sc(512);
     for (int n = 0; n < 256; n++) {  // double argument as in Java, correctly rounded function value
-        double arg = n * 2.0 * JPI / 256;
+        double arg = n * 2.0 * TUNER_PI / 256;
         sc[n] = (double)cosl((long double)arg);
         sc[256 + n] = (double)sinl((long double)arg);
     }
@@ -2740,9 +2496,10 @@ int jsdr_bpsk_set_variant(jsdr_bpsk *h, int variant)
 // ------------------------------------------------------------------------------------------- live control
 // FUNcubeBPSKDemod.actionPerformed (:177-190) between two calls.  Every check comes first: a refused call leaves the handle
 // exactly as it was.  Then the handle's own work is waited for (the previous call's tail and FEC on the side stream finish
-// with the settings they were launched with), the schedule prefetch is joined and both schedule caches are dropped (their
-// key does not hold tuPhaseInc), and dmMaxCorr is zeroed in every stream.  tuPhase, the down-sampler and matched-filter
-// histories, vcoPhase, the tail state, the FEC register and the counters carry on.
+// with the settings they were launched with), the schedule prefetch is joined, and dmMaxCorr is zeroed in every stream.
+// tuPhase, the down-sampler and matched-filter histories, vcoPhase, the tail state, the FEC register and the counters carry on.
+// The schedules need no word from here: their keys hold tuPhaseInc and the mode, so one computed for the old settings does
+// not match the next call.  The device copy of the tables is marked stale, which makes that call send its own.
 }  // extern "C"
 
 int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who)
@@ -2789,10 +2546,9 @@ static int live_apply(jsdr_bpsk *h, double tuning, int do_fft, int do_up, bool z
     }
     h->tuning = tuning;
     h->do_up = do_up;
-    h->tuPhaseInc = 2.0 * JPI * tuning / (double)h->rate;  // :189
+    h->tuPhaseInc = tuner_inc(tuning, h->rate);  // :189
     h->retuned = true;
-    h->prefetch.valid = false;
-    h->cache_valid = false;
+    h->tables_on_device = false;
     return JSDR_OK;
 }
 
@@ -2847,7 +2603,7 @@ static int chan_apply(jsdr_bpsk *h, int ch, const double *tuning, const int *do_
         BpskChan &cc = h->chan[c];
         if (tuning) {
             cc.tuning = *tuning;
-            cc.tuPhaseInc = 2.0 * JPI * *tuning / (double)h->rate;  // :189
+            cc.tuPhaseInc = tuner_inc(*tuning, h->rate);  // :189
         }
         if (do_up) cc.do_up = *do_up;
         if (do_fft && (*do_fft != 0) != (cc.do_fft != 0)) {
@@ -2893,7 +2649,7 @@ static int pst_apply(jsdr_bpsk *h, int first, int count, const double *tunings, 
 {
     if (sync_last(h) != JSDR_OK) return JSDR_ERR;
     std::vector<double> inc((size_t)count);
-    for (int i = 0; i < count; i++) inc[(size_t)i] = 2.0 * JPI * (tunings ? tunings[i] : one) / (double)h->rate;  // :189
+    for (int i = 0; i < count; i++) inc[(size_t)i] = tuner_inc(tunings ? tunings[i] : one, h->rate);  // :189
     if (zero_maxcorr) {
         std::vector<int> ids((size_t)count);
         for (int i = 0; i < count; i++) ids[(size_t)i] = first + i;
@@ -2986,7 +2742,7 @@ int jsdr_bpsk_create_channels(jsdr_bpsk **out, int rate, int nsamples_per_frame,
     for (int c = 0; c < nchannels && ok; c++) {
         BpskChan &cc = h->chan[c];
         cc.tuning = tuning_hz[c];
-        cc.tuPhaseInc = 2.0 * JPI * tuning_hz[c] / (double)rate;  // :196
+        cc.tuPhaseInc = tuner_inc(tuning_hz[c], rate);  // :196
         cc.do_up = do_up ? do_up[c] != 0 : 0;
         ok = cc.dev.alloc((size_t)h->max_batch + 26) == JSDR_OK;
     }
@@ -3155,7 +2911,7 @@ int jsdr_bpsk_create_tuned(jsdr_bpsk **out, int rate, int nsamples_per_frame, in
     const size_t S = (size_t)nstreams;
     h->pst_tuning.assign(tuning_hz, tuning_hz + nstreams);
     std::vector<double> inc(S);
-    for (size_t s = 0; s < S; s++) inc[s] = 2.0 * JPI * tuning_hz[s] / (double)rate;  // :196
+    for (size_t s = 0; s < S; s++) inc[s] = tuner_inc(tuning_hz[s], rate);  // :196
     h->pst_ckpt_stride = h->max_batch / PST_C + 1;
     const bool ok = sincos9_ensure(h) == JSDR_OK && h->pst_tu.alloc(S) == JSDR_OK && h->pst_inc.alloc(S) == JSDR_OK &&
                     h->pst_ckpt.alloc(S * (size_t)h->pst_ckpt_stride) == JSDR_OK && h->pst_kh[0].alloc(S * 32) == JSDR_OK &&

@@ -1,10 +1,12 @@
-// bpsk_tuner.h -- the tuner recurrence of FUNcubeBPSKDemod.doBufferTune (:384-390), stated once for the host walk
-// (jsdr_bpsk_tuner_walk_host) and the two kernels of a tuned handle (bpsk_pst.hip: k_tuner_walk, k_front_pst).
+// bpsk_tuner.h -- the input-independent recurrences of FUNcubeBPSKDemod, each stated once for the host and the device: the tuner
+// of doBufferTune (:384-390), the VCO of the demodulator (:511-516) and tuPhaseInc (:189 / :196).  The host scheduler
+// (bpsk_sched.hip), jsdr_bpsk_tuner_walk_host and the two kernels of a tuned handle (bpsk_pst.hip: k_tuner_walk, k_front_pst)
+// all step them through these functions.
 //
-// The operations are chan_compute's (bpsk_handle.hip), in its order: the phase moves on and wraps with ONE subtraction, and the
-// table index is the product tu * 256.0 divided by 2 pi -- multiplied, then divided, never multiplied by a reciprocal -- and
-// truncated.  Every unit that includes this is compiled with -ffp-contract=off: each operation rounds by itself, as Java's do,
-// and the device's FP64 add, multiply and divide are IEEE's, so host and device produce the same doubles and the same indices.
+// The tuner phase moves on and wraps with ONE subtraction, and the table index is the product tu * 256.0 divided by 2 pi --
+// multiplied, then divided, never multiplied by a reciprocal -- and truncated.  Every unit that includes this is compiled with
+// -ffp-contract=off: each operation rounds by itself, as Java's do, and the device's FP64 add, multiply and divide are IEEE's,
+// so host and device produce the same doubles and the same indices.
 // The index is 9 bits wide: 0 .. 255 are the reference's sin / cos tables, 256 is the sample the reference passes through
 // unmixed (tuPhase <= 0, :388 / :395) -- entry 256 of the kernels' table is (1.0, 1.0).
 #pragma once
@@ -12,7 +14,10 @@
 
 namespace jsdr {
 
-constexpr double TUNER_PI = 3.14159265358979323846;  // (bpsk_handle.hip's JPI)
+constexpr double TUNER_PI = 3.14159265358979323846;  // Math.PI
+
+// tuPhaseInc = 2 pi tuning / rate, evaluated left to right   (:189 / :196)
+inline double tuner_inc(double tuning, int rate) { return 2.0 * TUNER_PI * tuning / (double)rate; }
 
 // tuPhase += tuPhaseInc; if (tuPhase > 2 pi) tuPhase -= 2 pi   (:384-385)
 __host__ __device__ inline void tuner_advance(double &tu, double inc)
@@ -34,6 +39,17 @@ __host__ __device__ inline int tuner_step(double &tu, double inc)
 {
     tuner_advance(tu, inc);
     return tuner_k9(tu);
+}
+
+// one decimated sample of the VCO: vcoPhase += VCO_PHASE_INC; if (vcoPhase > 2 pi) vcoPhase -= 2 pi; the table index of the
+// sample (:511-516).  VCO_PHASE_INC = 2 pi 1200 / 9600 (:88)
+__host__ __device__ inline int vco_step(double &vco)
+{
+    const double two_pi = 2.0 * TUNER_PI;
+    const double vinc = 2.0 * TUNER_PI * 1200.0 / (double)9600;
+    vco += vinc;
+    if (vco > two_pi) vco -= two_pi;
+    return (int)(vco * (double)256 / two_pi) % 256;
 }
 
 }  // namespace jsdr
