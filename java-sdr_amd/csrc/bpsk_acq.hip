@@ -53,8 +53,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long long wg_t0 = a.clk != nullptr ? (long long)__builtin_amdgcn_s_memrealtime() : 0;
     for (int i = tid; i < ACQ_TWL - 1; i += T) TsL[i] = tsg[i];
-    const int beg = a.do_up ? N / 4 : 0;
-    const int end = a.do_up ? N / 2 : N / 4;
+    const int beg = acq_band_beg(N, a.do_up), end = acq_band_end(N, a.do_up);
     const int pbase = beg + 24;
     const long long nfr = (long long)a.S * a.F;
     // the first pass's non-trivial twiddles tw[4], tw[6] (wing 4) and tw[8..10], tw[12..14] (wing 8): uniform, scalar registers
@@ -119,7 +118,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
 #pragma unroll
             for (int m = 0; m < 16; m++) {
                 if (F32IN) {
-                    v[m] = make_double2((double)pref[m].x, (double)pref[m].y);
+                    v[m] = acq_sample(pref[m]);
                 } else {
                     double di, dq;
                     fm_convert(pre[m], a.ic, a.qc, true, di, dq);  // both rails on the packed FP32 pipe (common.h)
@@ -136,7 +135,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
             for (int m = 0; m < 16; m++) X[16 * q1f + (m ^ key)] = v[m];
         }
         acq_barrier<T>();
-        ACQ_PHASE(0)
+        ACQ_PHASE(clkL, 0)
         // The last pass's twiddles (wings >= 256: no room in LDS) are requested HERE, a whole pass ahead of their use and ahead of
         // the next frame's samples: VMEM operations return in order on this part, so a wait for a twiddle requested after the
         // samples would be a wait for the samples (a round trip to HBM at two waves a SIMD).
@@ -153,7 +152,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
             if (first && tid == 0) tkL[1] = (int)tk + zlate;
         }
         acq_barrier<T>();
-        ACQ_PHASE(1)
+        ACQ_PHASE(clkL, 1)
         r_next = tkL[1];
         // the frame this workgroup takes next (or this one again)
         bool more = true;
@@ -189,7 +188,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
         fetch(sn, fn);
         __builtin_amdgcn_sched_barrier(0);
         acq_barrier<T>();  // the image is dead: |X| goes over it
-        ACQ_PHASE(2)
+        ACQ_PHASE(clkL, 2)
         double2 *specg = a.spec + g * a.nsb;
 #pragma unroll
         for (int it = 0; it < NGL; it++) {
@@ -223,7 +222,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
             }
         }
         acq_barrier<T>();
-        ACQ_PHASE(3)
+        ACQ_PHASE(clkL, 3)
         // ---- 100-wide boxcar, summed j ascending for every i (:433-437); first maximum (:439-442).  A thread owns RB consecutive
         // outputs i0 .. i0 + RB - 1: their windows P[i - 50 .. i + 49] are one run of 99 + RB values, each output its own
         // ascending chain.
@@ -278,7 +277,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
                 }
             }
         }
-        ACQ_PHASE(4)
+        ACQ_PHASE(clkL, 4)
         // the wave's first maximum: the largest value (sums of |X| are never negative), and of the lanes that hold it the
         // lowest -- outputs ascend with the lane, and a lane kept the first of its own
         {
@@ -301,14 +300,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
                 double mv = 0.0;
                 int mi = -1;
 #pragma unroll
-                for (int w = 0; w < T / 64; w++) {
-                    const double ov = redv[w];
-                    const int oi = redi[w];
-                    if (oi >= 0 && (ov > mv || (ov == mv && (mi < 0 || oi < mi)))) {
-                        mv = ov;
-                        mi = oi;
-                    }
-                }
+                for (int w = 0; w < T / 64; w++) first_max_merge(mv, mi, redv[w], redi[w]);
                 AcqPeak pk;
                 pk.maxBin = mv;
                 pk.binPos = mi;
@@ -325,7 +317,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_fwd(AcqArgs a)
             }
             acq_barrier<T>();  // P is read before the next frame's first pass stores over it
         }
-        ACQ_PHASE(5)
+        ACQ_PHASE(clkL, 5)
         first = fn != f + 1 || sn != s;
         have = more;
         s = sn;
@@ -349,21 +341,16 @@ __global__ __launch_bounds__(64) void k_acq_scan(AcqArgs a)
 {
     const int s = blockIdx.x, lane = threadIdx.x;
     const int n = a.n;
-    const int beg = a.do_up ? n / 4 : 0;
-    const int end = a.do_up ? n / 2 : n / 4;
+    const int beg = acq_band_beg(n, a.do_up), end = acq_band_end(n, a.do_up);
     FftFrontState *sp = &a.st[s];
-    double avePeakPower = sp->avePeakPower, aveCentreBin = sp->aveCentreBin;
-    int centreBin = sp->centreBin;
-    // :399-402 -- float expressions widened to double
-    const double CFREQ_INV = (double)(1.0F - (2.0F / (1 + 1))), CFREQ_AVG = (double)(2.0F / (1 + 1));
-    const double PSD_INV = (double)(1.0F - (2.0F / (10 + 1))), PSD_AVG = (double)(2.0F / (10 + 1));
+    double avePeakPower, aveCentreBin;
+    int centreBin;
+    acq_state_load(sp, avePeakPower, aveCentreBin, centreBin);
     const long long g0 = (long long)s * a.F;
     int f = 0;
     while (f < a.F) {
         // :444-445 for the block's first frame; the lanes behind it assume the centre bin stays
-        int cb = centreBin;
-        if (cb < 0) cb = 0;
-        if (cb > end - 1) cb = end - 1;
+        const int cb = centre_bin_clamp(centreBin, end);
         const int fl = f + lane;
         double atc = 0.0, mb = 0.0;
         int bp = -1;
@@ -372,7 +359,7 @@ __global__ __launch_bounds__(64) void k_acq_scan(AcqArgs a)
             mb = pk.maxBin;
             bp = pk.binPos;
             // avePsd is cleared per frame (:431) and only [beg + 75, end - 75) is filled
-            if (cb >= beg + 75 && cb < end - 75) atc = a.aband[(g0 + fl) * a.na + (cb - (beg + 75))];
+            if (acq_band_filled(cb, beg, end)) atc = a.aband[(g0 + fl) * a.na + (cb - (beg + 75))];
         }
         const int cnt = (a.F - f) < 64 ? (a.F - f) : 64;
         int done = 0;
@@ -382,28 +369,18 @@ __global__ __launch_bounds__(64) void k_acq_scan(AcqArgs a)
             const double atc_l = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(atc), l), __builtin_amdgcn_readlane(__double2loint(atc), l));
             const double mb_l = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(mb), l), __builtin_amdgcn_readlane(__double2loint(mb), l));
             const int bp_l = __builtin_amdgcn_readlane(bp, l);
-            if (centreBin < 0) centreBin = 0;
-            if (centreBin > end - 1) centreBin = end - 1;
-            avePeakPower = (PSD_AVG * atc_l) + (PSD_INV * avePeakPower);
-            if (mb_l > (avePeakPower / 4) * 5 && bp_l > 0) {
-                aveCentreBin = (CFREQ_AVG * (double)(float)bp_l) + (CFREQ_INV * aveCentreBin);
-                centreBin = (int)(aveCentreBin + (double)1.0F);
-            }
-            if (centreBin < 102) centreBin = 102;
+            centreBin = centre_bin_clamp(centreBin, end);
+            centre_bin_step(avePeakPower, aveCentreBin, centreBin, atc_l, mb_l, bp_l);
             if (lane == 0) a.cbin[g0 + f + l] = centreBin;
             done = l + 1;
             // the next frame reads avePsd under THIS frame's centre bin (after its own clamps): if that is not what the block
             // was loaded under, reload from the next frame on
-            int cn = centreBin;
-            if (cn > end - 1) cn = end - 1;
-            if (cn != cb) break;
+            if (centre_bin_clamp(centreBin, end) != cb) break;
         }
         f += done;
     }
     if (lane == 0) {
-        sp->avePeakPower = avePeakPower;
-        sp->aveCentreBin = aveCentreBin;
-        sp->centreBin = centreBin;
+        acq_state_store(sp, avePeakPower, aveCentreBin, centreBin);
     }
 }
 
@@ -436,7 +413,6 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_inv(AcqArgs a)
     if (tid < 2) negzL[tid] = 0;
     const int D = a.decim;
     const double norm = 1.0 / (double)N;
-    const double HOWARD = 0.9 * 32768.0;
     const long long nfr = (long long)a.S * a.F;
     const int lo1 = a.do_up ? N / 4 - 26 : 0;
     // in registers for the whole launch: the wing-8 twiddle of this thread's slot of a first-pass group, negated for the slots
@@ -548,7 +524,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_inv(AcqArgs a)
         // (a SCALAR load: the value is uniform, and as a vector load the compiler makes it so on the spot -- global_load, s_waitcnt
         //  vmcnt(0), v_readfirstlane: a round trip to memory, and the previous frame's stores, at the top of every frame)
         c_next = ((const __attribute__((address_space(4))) int *)a.cbin)[gn];
-        ACQ_PHASE(0)
+        ACQ_PHASE(clkL, 0)
         // ---- inverse transform (:459).  Slot 16 q + m of the bit-reversed array holds input brev4(m) N/16 + brev(q): below 204 only
         // for m = 0 (N >= 2048; and m = 8 at N = 2048), so the first three stages of a group are broadcasts of its slots 0 and 8
         // -- a butterfly whose second operand is +0 returns its first operand twice, unless that holds a -0.0 (IEEE: (-0) + (+0) =
@@ -622,7 +598,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_inv(AcqArgs a)
             if (first && tid == 0) tkL[1] = (int)tk + zlate;
         }
         acq_barrier<T>();
-        ACQ_PHASE(1)
+        ACQ_PHASE(clkL, 1)
         if (tf == 0) negzL[par] = 0;  // (read by everybody before the barrier above; set again two frames on at the earliest)
         if constexpr (Plan::G4 != 0) {
             acq_mid_pass<Plan::G3, 256, true, LOGN>(X, TsL, tsg, tf);
@@ -649,7 +625,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_inv(AcqArgs a)
             for (int m = 0; m < ML; m++) o[it][m] = v[m].x * norm;
         }
         acq_barrier<T>();  // every butterfly of the pass is in registers: the compact samples go over the image
-        ACQ_PHASE(2)
+        ACQ_PHASE(clkL, 2)
         double *Rb = reinterpret_cast<double *>(smem);
 #pragma unroll
         for (int it = 0; it < NGL; it++) {
@@ -659,7 +635,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_inv(AcqArgs a)
         }
         store_bins(tf, par ^ 1);  // the NEXT frame's bins (requested before the last pass; nothing is stored to memory in between)
         acq_barrier<T>();
-        ACQ_PHASE(3)
+        ACQ_PHASE(clkL, 3)
         // ---- the frame's first and last 26 samples for the windows that cross into / out of it (k_acq_edges)
         if (tf < 26) {
             double *eg = a.edges + g * 52;
@@ -677,37 +653,15 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acq_inv(AcqArgs a)
                 if (te < t0 + N && j < nds) {
                     const int e = te - t0;
                     if (e >= 26) {
-                        double fi = 0.0;
-                        if (even_d) {
-                            // the 27 samples e-26 .. e as 14 aligned 16-byte reads
-                            const double2 *w2 = reinterpret_cast<const double2 *>(Rb + ((e + ACQ_RB0 - 26) & ~1));
-                            double d[28];
-#pragma unroll
-                            for (int i = 0; i < 14; i++) {
-                                const double2 t = w2[i];
-                                d[2 * i] = t.x;
-                                d[2 * i + 1] = t.y;
-                            }
-                            if (wpar) {
-#pragma unroll
-                                for (int k = 0; k < 27; k++) fi += d[27 - k] * ds_tap(k);  // newest first (:479-483)
-                            } else {
-#pragma unroll
-                                for (int k = 0; k < 27; k++) fi += d[26 - k] * ds_tap(k);
-                            }
-                        } else {
-                            const double *w = Rb + (ACQ_RB0 + e);
-#pragma unroll
-                            for (int k = 0; k < 27; k++) fi += w[-k] * ds_tap(k);
-                        }
-                        const double ov = fi * HOWARD;  // fi == fq: both rails get the same samples
+                        const double fi = ds_window_compact(Rb, ACQ_RB0, e, even_d, wpar);
+                        const double ov = fi * ACQ_HOWARD;  // fi == fq: both rails get the same samples
                         a.dm[(long long)s * a.dm_stride + 64 + j] = make_double2(ov * cs[b].x, ov * cs[b].y);  // :515-516
                     }
                 }
             }
         }
         acq_barrier<T>();  // every window is read before the next frame's passes store over the image
-        ACQ_PHASE(4)
+        ACQ_PHASE(clkL, 4)
         r_next = tkL[1];
         if (!more && first && f + 1 >= fe && r_next < nruns) {
             // a run of ONE frame (a stream's last, F not a multiple of the run): its successor was not known at its top -- it is now
@@ -738,7 +692,6 @@ __global__ __launch_bounds__(256) void k_acq_edges(AcqArgs a)
     const int n = a.n, D = a.decim;
     const int EO = 26 / D + 2;   // upper bound of the windows per frame that end within its first 26 samples
     const int FB = 256 / EO;     // frames a block takes: one thread per (frame, window)
-    const double HOWARD = 0.9 * 32768.0;
     FftFrontState *sp = &a.st[s];
     // rows[i] = the first / last 26 samples of frame fb - 1 + i, i = 0 .. FB: read once, coalesced (a window walks 27 of them, and from
     // global memory that was 27 dependent loads a thread); for the call's first frame the row in front is the stream's history
@@ -774,7 +727,7 @@ __global__ __launch_bounds__(256) void k_acq_edges(AcqArgs a)
                     const double x = i >= 0 ? head[i] : prev[26 + i];
                     fiv += x * ds_tap(k);
                 }
-                const double ov = fiv * HOWARD;
+                const double ov = fiv * ACQ_HOWARD;
                 const double2 cs = a.vco_cs[j];
                 a.dm[(long long)s * a.dm_stride + 64 + j] = make_double2(ov * cs.x, ov * cs.y);
             }
@@ -791,7 +744,7 @@ extern int g_acq_last_grid[4];
 static void acq3_layout(int n, int do_up, int *nsb, int *na)
 {
     // (Java's integer n / 4 and n / 2, as the reference computes its band, :429-430)
-    const int beg = do_up ? n / 4 : 0, end = do_up ? n / 2 : n / 4;
+    const int beg = acq_band_beg(n, do_up), end = acq_band_end(n, do_up);
     *nsb = do_up ? 204 + (n / 2 + 28 - (n / 4 - 26)) : n / 4 + 28;
     if (*nsb < 204) *nsb = 204;  // (frames below 704 samples, any-frame path: the gather at the clamp value 102 takes bins [0, 204))
     *na = ((end - beg - 150) + 1) & ~1;

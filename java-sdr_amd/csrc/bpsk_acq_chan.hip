@@ -244,14 +244,7 @@ __global__ __launch_bounds__((1 << LOGN) / 16, 2) void k_acqc_fwd(AcqcFwdArgs ca
                 double mv = 0.0;
                 int mi = -1;
 #pragma unroll
-                for (int w = 0; w < T / 64; w++) {
-                    const double ov = redv[8 * u + w];
-                    const int oi = redi[8 * u + w];
-                    if (oi >= 0 && (ov > mv || (ov == mv && (mi < 0 || oi < mi)))) {
-                        mv = ov;
-                        mi = oi;
-                    }
-                }
+                for (int w = 0; w < T / 64; w++) first_max_merge(mv, mi, redv[8 * u + w], redi[8 * u + w]);
                 AcqPeak pk;
                 pk.maxBin = mv;
                 pk.binPos = mi;
@@ -293,7 +286,6 @@ __global__ __launch_bounds__(64) void k_acq_edges_seam(AcqArgs a, const double *
     const int s = blockIdx.x, j = threadIdx.x;
     const int e = (int)a.first_out + a.decim * j;  // the sample of frame 0 whose arrival completes output j
     if (j >= J || e >= 26 || e >= a.n || j >= (int)a.nds) return;
-    const double HOWARD = 0.9 * 32768.0;
     const double *head = a.edges + (long long)s * a.F * 52;  // frame 0 of the launch is frame 0 of the call (a.f0 == 0)
     const double *prev = qcol + (long long)s * 26;
     double fq = 0.0;
@@ -303,7 +295,7 @@ __global__ __launch_bounds__(64) void k_acq_edges_seam(AcqArgs a, const double *
         const double x = i >= 0 ? head[i] : prev[26 + i];
         fq += x * ds_tap(k);
     }
-    const double ov = fq * HOWARD;
+    const double ov = fq * ACQ_HOWARD;
     a.dm[(long long)s * a.dm_stride + 64 + j].y = ov * a.vco_cs[j].y;
 }
 

@@ -35,17 +35,7 @@ __global__ __launch_bounds__(AG_T) void k_acqg_load(AcqArgs a, double2 *img, int
     if (t >= a.n) return;
     const int s = (int)(g / (unsigned)a.F), f = (int)(g - (unsigned)s * (unsigned)a.F);
     const long long src = (long long)s * a.stride_pairs + (long long)(a.f0 + f) * a.n + t;
-    double di, dq;
-    if (F32IN) {
-        const float2 w = a.rawf[src];
-        di = (double)w.x;
-        dq = (double)w.y;
-    } else {
-        const int w = a.raw[src];
-        di = (double)i16_to_float_java(java_short_add((int)(short)(w & 0xffff), a.ic));
-        dq = (double)i16_to_float_java(java_short_add(w >> 16, a.qc));
-    }
-    img[(long long)g * a.n + (logn ? ag_bitrev(t, logn) : t)] = make_double2(di, dq);
+    img[(long long)g * a.n + (logn ? ag_bitrev(t, logn) : t)] = F32IN ? acq_sample(a.rawf[src]) : acq_sample(a.raw[src], a.ic, a.qc);
 }
 
 // NST consecutive radix-2 stages of jo_fft_f64 (half = half0, 2 half0, ...), in place: a thread holds the 2^NST elements
@@ -185,8 +175,7 @@ __global__ __launch_bounds__(AG_T) void k_acqg_band(AcqArgs a, const double2 *im
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n;
     const double2 *X = img + g * n;
-    const int beg = a.do_up ? n / 4 : 0;
-    const int end = a.do_up ? n / 2 : n / 4;
+    const int beg = acq_band_beg(n, a.do_up), end = acq_band_end(n, a.do_up);
     {
         double2 *specg = a.spec + g * a.nsb;
         const int lo1 = n / 4 - 26;
@@ -210,21 +199,14 @@ __global__ __launch_bounds__(AG_T) void k_acqg_band(AcqArgs a, const double2 *im
 #pragma unroll 4
             for (int j = 0; j < 100; j++) acc += Pm[u + j];
             ab[i0 + u - (beg + 75)] = acc;
-            if (bestv < acc) {
-                bestv = acc;
-                besti = i0 + u;
-            }
+            first_max_update(bestv, besti, acc, i0 + u);
         }
         __syncthreads();
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         const double ov = __shfl_xor(bestv, off, 64);
-        const int oi = __shfl_xor(besti, off, 64);
-        if (oi >= 0 && (ov > bestv || (ov == bestv && (besti < 0 || oi < besti)))) {
-            bestv = ov;
-            besti = oi;
-        }
+        first_max_merge(bestv, besti, ov, __shfl_xor(besti, off, 64));
     }
     if (lane == 0) {
         redv[wave] = bestv;
@@ -234,14 +216,7 @@ __global__ __launch_bounds__(AG_T) void k_acqg_band(AcqArgs a, const double2 *im
     if (tid == 0) {
         double mv = 0.0;
         int mi = -1;
-        for (int w = 0; w < AG_T / 64; w++) {
-            const double ov = redv[w];
-            const int oi = redi[w];
-            if (oi >= 0 && (ov > mv || (ov == mv && (mi < 0 || oi < mi)))) {
-                mv = ov;
-                mi = oi;
-            }
-        }
+        for (int w = 0; w < AG_T / 64; w++) first_max_merge(mv, mi, redv[w], redi[w]);
         AcqPeak pk;
         pk.maxBin = mv;
         pk.binPos = mi;
@@ -285,10 +260,9 @@ __global__ __launch_bounds__(AG_T) void k_acqg_rx(AcqArgs a, const double2 *img,
     const int s = (int)(g / (unsigned)a.F), f = (int)(g - (unsigned)s * (unsigned)a.F);
     const double2 *X = img + (long long)g * n;
     const double norm = 1.0 / (double)n;
-    const double HOWARD = 0.9 * 32768.0;
     if (r < 52) a.edges[(long long)g * 52 + r] = X[r < 26 ? r : n - 52 + r].x * norm;
     const long long t0 = (long long)(a.f0 + f) * n;  // call-relative index of the frame's first sample
-    const long long jlo = t0 <= a.first_out ? 0 : (t0 - a.first_out + D - 1) / D;
+    const long long jlo = ds_first_output(t0, a.first_out, D);
     const long long j = jlo + r;
     const long long te = a.first_out + (long long)D * j;  // window end, call-relative
     if (te >= t0 + n || j >= a.nds) return;
@@ -297,7 +271,7 @@ __global__ __launch_bounds__(AG_T) void k_acqg_rx(AcqArgs a, const double2 *img,
     double fi = 0.0;
 #pragma unroll
     for (int k = 0; k < 27; k++) fi += (X[e - k].x * norm) * ds_tap(k);  // newest first (:479-483)
-    const double o = fi * HOWARD;
+    const double o = fi * ACQ_HOWARD;
     const double2 cs = a.vco_cs[j];
     a.dm[(long long)s * a.dm_stride + 64 + j] = make_double2(o * cs.x, o * cs.y);  // :515-516
 }

@@ -1,6 +1,6 @@
 // bpsk_fft.h -- interface of the FFT-acquire front end (bpsk_fft.hip) used by the pipeline host code (bpsk_handle.hip)
 #pragma once
-#include "common.h"
+#include "bpsk_acq_rule.h"
 #include <vector>
 
 namespace jsdr {
@@ -129,6 +129,118 @@ __device__ __forceinline__ void wave_first_max(double &bestv, int &besti)
     besti = mi == 0x7fffffff ? -1 : mi;
 }
 
+// ---- the frame stages every FFT-acquire front end shares (bpsk_fft.hip, bpsk_fftm.hip, bpsk_acq*.hip); the scalar rules they
+// step are bpsk_acq_rule.h's
+
+// :416-421 -- a sample of the frame as the transform's input: (double) of JavaAudio's float sample, int16 words with the
+// DC corrections ic / qc added as Java shorts
+__device__ __forceinline__ double2 acq_sample(int w, int ic, int qc)
+{
+    return make_double2((double)i16_to_float_java(java_short_add((int)(short)(w & 0xffff), ic)),
+                        (double)i16_to_float_java(java_short_add(w >> 16, qc)));
+}
+__device__ __forceinline__ double2 acq_sample(const float2 w)
+{
+    return make_double2((double)w.x, (double)w.y);
+}
+
+// One step of the boxcar search (:433-442): the pair of sums (boxcar_pair) at i (even) and i + 1, stored to ai[0] and ai[1]
+// where they lie in [beg + 75, end - 75), and the thread's first maximum brought up to date (i ascends within a thread).
+__device__ __forceinline__ void boxcar_put(double a0, double a1, double *ai, int i, int beg, int end, double &bestv, int &besti)
+{
+    asm volatile("" : "+v"(a0), "+v"(a1));  // due here: sunk into the conditional uses below, the sums drag all 51 reads along
+    if (i >= beg + 75) {
+        ai[0] = a0;
+        first_max_update(bestv, besti, a0, i);
+    }
+    if (i + 1 < end - 75) {
+        ai[1] = a1;
+        first_max_update(bestv, besti, a1, i + 1);
+    }
+}
+
+// The workgroup's first maximum (maxBin, binPos), uniform, from its NW waves' in (redv, redi)[wave] behind a workgroup barrier:
+// they meet in lanes 0 .. NW - 1 of every wave (the same combine: larger value, then smaller index; an empty candidate never
+// wins) -- as an NW-step loop run by every thread this cost the SIMDs 3.6k cycles a frame at NW = 12.
+template <int NW>
+__device__ __forceinline__ void wg_first_max(const double *redv, const int *redi, int lane, double &maxBin, int &binPos)
+{
+    double mv = 0.0;
+    int mi = -1;
+    if (lane < NW) {
+        mv = redv[lane];
+        mi = redi[lane];
+    }
+    wave_first_max(mv, mi);
+    maxBin = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(mv)), __builtin_amdgcn_readfirstlane(__double2loint(mv)));
+    binPos = __builtin_amdgcn_readfirstlane(mi);
+}
+
+// RxDownSample (:470-492) for the window that ends at w[0], newest first (:479-483): 27 samples at w[0], w[-1], ..
+__device__ __forceinline__ double ds_sample(const double &x) { return x; }
+__device__ __forceinline__ double ds_sample(const double2 &x) { return x.x; }  // the real parts of an image
+template <class T>
+__device__ __forceinline__ double ds_window(const T *w)
+{
+    double fi = 0.0;
+#pragma unroll
+    for (int k = 0; k < 27; k++) fi += ds_sample(w[-k]) * ds_tap(k);
+    return fi;
+}
+// The same from the COMPACT samples of a frame -- sample t at double slot rb0 + t of Rb, the previous frame's last 26 in front
+// of them, so that every window is one contiguous run -- for the window that ends at sample e.  With an even decimation
+// (even_d) every window of a call ends on the same parity par = (first_out - t0) & 1 (frames are even): the 27 samples
+// e - 26 .. e are 14 aligned 16-byte reads, d[i] = slot ((e + rb0 - 26) & ~1) + i.
+__device__ __forceinline__ double ds_window_compact(const double *Rb, int rb0, int e, bool even_d, int par)
+{
+    double fi = 0.0;
+    if (even_d) {
+        const double2 *w2 = reinterpret_cast<const double2 *>(Rb + ((e + rb0 - 26) & ~1));
+        double d[28];
+#pragma unroll
+        for (int i = 0; i < 14; i++) {
+            const double2 t = w2[i];
+            d[2 * i] = t.x;
+            d[2 * i + 1] = t.y;
+        }
+        if (par) {
+#pragma unroll
+            for (int k = 0; k < 27; k++) fi += d[27 - k] * ds_tap(k);  // newest first (:479-483)
+        } else {
+#pragma unroll
+            for (int k = 0; k < 27; k++) fi += d[26 - k] * ds_tap(k);
+        }
+    } else {
+        const double *w = Rb + (rb0 + e);
+#pragma unroll
+        for (int k = 0; k < 27; k++) fi += w[-k] * ds_tap(k);
+    }
+    return fi;
+}
+
+// the three numbers a stream carries from frame to frame (:403-405)
+__device__ __forceinline__ void acq_state_load(const FftFrontState *sp, double &avePeakPower, double &aveCentreBin, int &centreBin)
+{
+    avePeakPower = sp->avePeakPower;
+    aveCentreBin = sp->aveCentreBin;
+    centreBin = sp->centreBin;
+}
+__device__ __forceinline__ void acq_state_store(FftFrontState *sp, double avePeakPower, double aveCentreBin, int centreBin)
+{
+    sp->avePeakPower = avePeakPower;
+    sp->aveCentreBin = aveCentreBin;
+    sp->centreBin = centreBin;
+}
+
+// diagnostics (JSDR_FFT_PHASECLK=1; never in the product's default path): the thread for which `timing` holds accumulates the
+// clock ticks of every phase in acc[] (LDS); `tprev` is the tick the phase began at
+#define ACQ_PHASE(acc, k)                            \
+    if (timing) {                                    \
+        const long long now_ = (long long)clock64(); \
+        acc[k] += now_ - tprev;                      \
+        tprev = now_;                                \
+    }
+
 int launch_front_fft(const FftFrontArgs &a, int nstreams, hipStream_t st);
 // round 6 (bpsk_acq.hip): the same front end in three phases -- forward transform + boxcar per frame, one scan per stream,
 // inverse transform + RxDownSample per frame -- for calls of two or more frames per stream; frames of 1024 .. 8192 samples
@@ -167,14 +279,6 @@ struct AcqArgs {
     int rps;               // runs per stream = ceil(F / run): a run lies inside one stream
     long long *clk;        // diagnostics (JSDR_FFT_PHASECLK=1): [16] clock ticks per phase of workgroup 0, k_acq_fwd [0..7], k_acq_inv [8..15]; or null
 };
-
-// thread 0 of workgroup 0 accumulates the clock ticks of every phase in LDS (never in the product's default path: clk is null)
-#define ACQ_PHASE(k)                                 \
-    if (timing) {                                    \
-        const long long now_ = (long long)clock64(); \
-        clkL[k] += now_ - tprev;                     \
-        tprev = now_;                                \
-    }
 
 // where bin b of a frame sits in its spec row, or -1
 __device__ __forceinline__ int acq_spec_index(int b, int n, int do_up)

@@ -335,14 +335,10 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
     FftFrontState *sp = &a.st[s];
     if (tid < 26) hist[tid] = sp->hist[tid];
     (void)taps;  // (the taps are compile-time constants now: ds_tap(); the slot stays for the layout)
-    double avePeakPower = sp->avePeakPower, aveCentreBin = sp->aveCentreBin;
-    int centreBin = sp->centreBin;
-    // :399-402 -- float expressions widened to double
-    const double CFREQ_INV = (double)(1.0F - (2.0F / (1 + 1))), CFREQ_AVG = (double)(2.0F / (1 + 1));
-    const double PSD_INV = (double)(1.0F - (2.0F / (10 + 1))), PSD_AVG = (double)(2.0F / (10 + 1));
-    const double HOWARD = 0.9 * 32768.0;
-    const int beg = a.do_up ? N / 4 : 0;
-    const int end = a.do_up ? N / 2 : N / 4;
+    double avePeakPower, aveCentreBin;
+    int centreBin;
+    acq_state_load(sp, avePeakPower, aveCentreBin, centreBin);
+    const int beg = acq_band_beg(N, a.do_up), end = acq_band_end(N, a.do_up);
     const int D = a.decim;
     const double norm = 1.0 / (double)N;
     const int *__restrict__ raw = a.raw + (long long)s * a.stride_pairs;
@@ -354,12 +350,6 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
     const bool timing = a.phase_clk != nullptr && s == 0 && tid == 0;
     if (timing)
         for (int k = 0; k < 8; k++) clk[k] = 0;
-#define PHASE(k)                                     \
-    if (timing) {                                    \
-        const long long now_ = (long long)clock64(); \
-        clk[k] += now_ - tprev;                      \
-        tprev = now_;                                \
-    }
     // First-pass group q = tid + 256*c owns slots 8q..8q+7, i.e. the frame elements brev(8q+m) =
     // brev3(m)*N/8 + brev(q): eight loads N/8 apart.  Frame 0 now; every later frame is fetched while its
     // predecessor is processed.
@@ -387,8 +377,7 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
     for (int f = 0; f < a.nframes; f++) {
         const long long t0 = (long long)f * N;  // call-relative index of the frame's first sample
         // VCO factors of this frame's RxDownSample outputs: in flight during the transforms
-        long long jlo = (t0 - a.first_out + D - 1) / D;
-        if (t0 <= a.first_out) jlo = 0;
+        const long long jlo = ds_first_output(t0, a.first_out, D);
         double2 cs0 = make_double2(0.0, 0.0);
         {
             const long long j = jlo + tid;
@@ -403,13 +392,7 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
                 double2 v[8];
 #pragma unroll
                 for (int m = 0; m < 8; m++) {
-                    if (F32IN) {
-                        v[m] = make_double2((double)pref[c][m].x, (double)pref[c][m].y);
-                    } else {
-                        const int w = pre[c][m];
-                        v[m] = make_double2((double)i16_to_float_java(java_short_add((int)(short)(w & 0xffff), a.ic)),
-                                            (double)i16_to_float_java(java_short_add(w >> 16, a.qc)));
-                    }
+                    v[m] = F32IN ? acq_sample(pref[c][m]) : acq_sample(pre[c][m], a.ic, a.qc);
                 }
                 if (f + 1 < a.nframes) {
 #pragma unroll
@@ -429,13 +412,13 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
                 for (int m = 0; m < 8; m++) X[xpad(8 * q + m)] = v[m];
             }
         }
-        PHASE(0)
+        ACQ_PHASE(clk, 0)
 #ifdef JSDR_X_FFT_NOBAND  // (probe: the forward transform's last pass in full)
         fft_rest<false, LOGN, false>(X, TsL, tsg, tid, norm);
 #else
         fft_rest<false, LOGN, false>(X, TsL, tsg, tid, norm, nullptr, LOGN == 11 ? end + 102 : 0);  // bins < end + 102 are read
 #endif
-        PHASE(1)
+        ACQ_PHASE(clk, 1)
         // ---- |X| (:425-427), for the bins the boxcar reads: [beg+24, end-24) -- a quarter band, not the N/2 bins the
         // reference fills (the double-precision root is ~28 instructions a bin)
         constexpr int NBAND = N / 4 - 48;
@@ -449,7 +432,7 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
             }
         }
         __syncthreads();
-        PHASE(2)
+        ACQ_PHASE(clk, 2)
         // ---- 100-wide boxcar, summed j ascending for every i (:433-437); first maximum (:439-442).  A thread owns
         // the outputs i (even) and i+1: their windows P[i-50..i+49] and P[i-49..i+50] come out of the same 51
         // aligned 16-byte reads, each summed in its own ascending chain.
@@ -462,21 +445,7 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
                 const double2 *w = reinterpret_cast<const double2 *>(P + i - 50);
                 double a0, a1;
                 boxcar_pair(w, a0, a1);
-                asm volatile("" : "+v"(a0), "+v"(a1));  // due here: sunk into the conditional uses below, the sums drag all 51 reads along
-                if (i >= beg + 75) {
-                    A[i] = a0;
-                    if (bestv < a0) {  // i ascends within a thread: strict '<' keeps the first maximum
-                        bestv = a0;
-                        besti = i;
-                    }
-                }
-                if (i + 1 < end - 75) {
-                    A[i + 1] = a1;
-                    if (bestv < a1) {
-                        bestv = a1;
-                        besti = i + 1;
-                    }
-                }
+                boxcar_put(a0, a1, A + i, i, beg, end, bestv, besti);
             }
         }
         wave_first_max(bestv, besti);  // (DPP: bpsk_fft.h)
@@ -485,32 +454,18 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
             redi[wave] = besti;
         }
         __syncthreads();
-        PHASE(3)
+        ACQ_PHASE(clk, 3)
         // ---- centre-bin rule (:444-453), evaluated by every thread on the same values
         {
             double maxBin = 0.0;
             int binPos = -1;
 #pragma unroll
-            for (int w = 0; w < 4; w++) {
-                const double ov = redv[w];
-                const int oi = redi[w];
-                if (oi >= 0 && (ov > maxBin || (ov == maxBin && (binPos < 0 || oi < binPos)))) {
-                    maxBin = ov;
-                    binPos = oi;
-                }
-            }
-            if (centreBin < 0) centreBin = 0;
-            if (centreBin > end - 1) centreBin = end - 1;
-            // aveTemp is cleared per frame (:431) and only [beg+75, end-75) is filled
-            const double atc = (centreBin >= beg + 75 && centreBin < end - 75) ? A[centreBin] : 0.0;
-            avePeakPower = (PSD_AVG * atc) + (PSD_INV * avePeakPower);
-            if (maxBin > (avePeakPower / 4) * 5 && binPos > 0) {
-                aveCentreBin = (CFREQ_AVG * (double)(float)binPos) + (CFREQ_INV * aveCentreBin);
-                centreBin = (int)(aveCentreBin + (double)1.0F);
-            }
-            if (centreBin < 102) centreBin = 102;
+            for (int w = 0; w < 4; w++) first_max_merge(maxBin, binPos, redv[w], redi[w]);
+            centreBin = centre_bin_clamp(centreBin, end);
+            const double atc = acq_band_filled(centreBin, beg, end) ? A[centreBin] : 0.0;
+            centre_bin_step(avePeakPower, aveCentreBin, centreBin, atc, maxBin, binPos);
         }
-        PHASE(4)
+        ACQ_PHASE(clk, 4)
         // ---- inverse FFT of the 204 bins around the centre moved to bin 0 of a zeroed array (:458-459)
         if constexpr (LOGN >= 11) {
             // Only input 0 of every first-pass group can be non-zero (bins >= N/8 > 204 are zero), and a butterfly
@@ -560,7 +515,7 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
 #pragma unroll
                 for (int m = 0; m < 8; m++) x0[9 * m] = vin[c][m];
             }
-            PHASE(5)
+            ACQ_PHASE(clk, 5)
             fft_rest<true, LOGN, true, true>(X, TsL, tsg, tid, norm, hist);  // leaves re/N compact (:462)
         } else {
             // N = 1024: two inputs of a first-pass group can be non-zero; the first pass runs in full on registers
@@ -586,10 +541,10 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
                     for (int m = 0; m < 8; m++) X[xpad(8 * q + m)] = vin[c][m];
                 }
             }
-            PHASE(5)
+            ACQ_PHASE(clk, 5)
             fft_rest<true, LOGN, false, true>(X, TsL, tsg, tid, norm, hist);  // leaves re/N compact (:462)
         }
-        PHASE(6)
+        ACQ_PHASE(clk, 6)
         // ---- RxDownSample(re, re) (:461-463, :470-492): outputs whose window ends inside this frame, from the compact samples
         // (sample t at double slot FF_RB0 + t, the previous frame's last 26 in front: every window is one contiguous run)
         {
@@ -602,6 +557,8 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
                 const long long te = (long long)a.first_out + (long long)D * j;  // window end, call-relative
                 if (te < t0 + N && j < a.nds) {
                     const int e = (int)(te - t0);  // 0..N-1 within the frame
+                    // (ds_window_compact, typed out: through the shared helper this kernel's register allocation moves -- scratch at
+                    //  n = 1024, a VGPR granule at n = 8192, float input)
                     double fi = 0.0;
                     if (even_d) {
                         // the 27 samples e-26 .. e as 14 aligned 16-byte reads: d[i] = slot ((e + 6) & ~1) + i
@@ -625,7 +582,7 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
 #pragma unroll
                         for (int k = 0; k < 27; k++) fi += w[-k] * ds_tap(k);
                     }
-                    const double o = fi * HOWARD;  // fi == fq: both rails get the same samples
+                    const double o = fi * ACQ_HOWARD;  // fi == fq: both rails get the same samples
                     const double2 cs = (b == 0) ? cs0 : a.vco_cs[j];
                     dm[64 + j] = make_double2(o * cs.x, o * cs.y);  // :515-516
                 }
@@ -633,15 +590,12 @@ __global__ __launch_bounds__(256, (LOGN <= 11 ? JSDR_FF_MINWG11 : (LOGN == 12 ? 
             if (tid < 26) hist[tid] = Rb[FF_RB0 + N - 26 + tid];  // (nobody reads hist[] before the next frame's last pass)
             __syncthreads();  // every window is read before the next frame's first pass overwrites the image
         }
-        PHASE(7)
+        ACQ_PHASE(clk, 7)
     }
-#undef PHASE
     __syncthreads();
     if (tid < 26) sp->hist[tid] = hist[tid];
     if (tid == 0) {
-        sp->avePeakPower = avePeakPower;
-        sp->aveCentreBin = aveCentreBin;
-        sp->centreBin = centreBin;
+        acq_state_store(sp, avePeakPower, aveCentreBin, centreBin);
         if (timing)
             for (int k = 0; k < 8; k++) a.phase_clk[k] = clk[k];
     }

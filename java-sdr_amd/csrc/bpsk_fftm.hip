@@ -60,6 +60,8 @@ typedef __attribute__((address_space(3))) double lds_f64;
 typedef __attribute__((address_space(1))) const d2v gbl_d2v;
 typedef __attribute__((address_space(1))) const int gbl_i32;
 typedef __attribute__((address_space(1))) const f2v gbl_f2v;
+// (bpsk_fft.h's float sample conversion, for a sample read through the typed view)
+__device__ __forceinline__ double2 acq_sample(const f2v w) { return acq_sample(make_float2(w.x, w.y)); }
 
 struct LdsRef {
     lds_d2v *q;
@@ -538,11 +540,7 @@ __device__ __attribute__((noinline)) void fm_first_from_raw(LdsArr X0, const int
             double2 v[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                if (F32IN)
-                    v[j] = make_double2((double)wf[it][j].x, (double)wf[it][j].y);
-                else
-                    v[j] = make_double2((double)i16_to_float_java(java_short_add((int)(short)(w[it][j] & 0xffff), ic)),
-                                        (double)i16_to_float_java(java_short_add(w[it][j] >> 16, qc)));
+                v[j] = F32IN ? acq_sample(wf[it][j]) : acq_sample(w[it][j], ic, qc);
             }
             dft_r<4>(v);
             fm_store4_rotated(X, b, v, tid);
@@ -702,11 +700,7 @@ __device__ __forceinline__ void fm_first_from_regs2(LdsArr X0, const FmRaw16 &r,
             double2 v[4];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                if (F32IN)
-                    v[j] = make_double2((double)r.wf[4 * it + j].x, (double)r.wf[4 * it + j].y);
-                else
-                    v[j] = make_double2((double)i16_to_float_java(java_short_add((int)(short)(r.w[4 * it + j] & 0xffff), ic)),
-                                        (double)i16_to_float_java(java_short_add(r.w[4 * it + j] >> 16, qc)));
+                v[j] = F32IN ? acq_sample(r.wf[4 * it + j]) : acq_sample(r.w[4 * it + j], ic, qc);
             }
             dft_r<4>(v);
             fm_store4_rotated(X, b, v, tid);
@@ -1158,8 +1152,7 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < aa.lds_tw; i += FM_T) twL[i] = aa.f.tw[i];
     const int s = blockIdx.x;
-    const int beg = a.do_up ? n / 4 : 0;
-    const int end = a.do_up ? n / 2 : n / 4;
+    const int beg = acq_band_beg(n, a.do_up), end = acq_band_end(n, a.do_up);
     // |X| over [beg+24, end-24) and the boxcar sums over [beg+74, end-74) live in the upper part of the image, dead
     // after the forward transform (bins up to n/2+101 are still gathered below); beg is a multiple of 4
     const int pbase = beg + 24;
@@ -1168,12 +1161,9 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
     const int abase = beg + 74;
     FftFrontState *sp = &a.st[s];
     if (tid < 26) hist[tid] = sp->hist[tid];
-    double avePeakPower = sp->avePeakPower, aveCentreBin = sp->aveCentreBin;
-    int centreBin = sp->centreBin;
-    // :399-402 -- float expressions widened to double
-    const double CFREQ_INV = (double)(1.0F - (2.0F / (1 + 1))), CFREQ_AVG = (double)(2.0F / (1 + 1));
-    const double PSD_INV = (double)(1.0F - (2.0F / (10 + 1))), PSD_AVG = (double)(2.0F / (10 + 1));
-    const double HOWARD = 0.9 * 32768.0;
+    double avePeakPower, aveCentreBin;
+    int centreBin;
+    acq_state_load(sp, avePeakPower, aveCentreBin, centreBin);
     const int D = a.decim;
     const double norm = 1.0 / (double)n;
     const int *__restrict__ raw = a.raw + (long long)s * a.stride_pairs;
@@ -1185,12 +1175,6 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
     const bool timing = a.phase_clk != nullptr && s == 0 && tid == 0;
     if (timing)
         for (int k = 0; k < 8; k++) clk[k] = 0;
-#define PHASE(k)                                     \
-    if (timing) {                                    \
-        const long long now_ = (long long)clock64(); \
-        clk[k] += now_ - tprev;                      \
-        tprev = now_;                                \
-    }
     __syncthreads();
     if (timing) tprev = (long long)clock64();
     FmRaw16 pre;  // n = 9600: the next frame's samples, requested during RxDownSample
@@ -1229,30 +1213,22 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
                 for (int q = 0; q < NLD; q++) {
                     const int t = tf + q * FM_T;
                     if (t < n) {
-                        double di, dq;
-                        if (F32IN) {
-                            di = (double)wf[q].x;
-                            dq = (double)wf[q].y;
-                        } else {
-                            di = (double)i16_to_float_java(java_short_add((int)(short)(w[q] & 0xffff), a.ic));
-                            dq = (double)i16_to_float_java(java_short_add(w[q] >> 16, a.qc));
-                        }
-                        X[t] = make_double2(di, dq);
+                        X[t] = F32IN ? acq_sample(wf[q]) : acq_sample(w[q], a.ic, a.qc);
                     }
                 }
             }
             __syncthreads();
         }
-        PHASE(0)
+        ACQ_PHASE(clk, 0)
         fm_forward<true>(XL, twL, aa, tf, fused_first, compact ? FM_FWD_BAND : FM_FULL, end + 102);  // :422-423; bins < end + 102 are read
-        PHASE(1)
+        ACQ_PHASE(clk, 1)
         // ---- |X| (:425-427) over the band the boxcar reads
         for (int i = pbase + tf; i < end - 24; i += FM_T) {
             const double2 v = X[i];
             P[i - pbase] = sqrt(v.x * v.x + v.y * v.y);
         }
         __syncthreads();
-        PHASE(6)
+        ACQ_PHASE(clk, 6)
         // ---- 100-wide boxcar, summed j ascending for every i (:433-437); first maximum (:439-442).  A thread owns
         // the outputs i (even) and i+1: both windows come out of the same 51 aligned 16-byte reads.
         double bestv = 0.0;  // maxBin starts at 0.0, binPos at -1
@@ -1261,21 +1237,7 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
             const double2 *w = reinterpret_cast<const double2 *>(P + (i - 50 - pbase));
             double a0, a1;
             boxcar_pair(w, a0, a1);
-            asm volatile("" : "+v"(a0), "+v"(a1));  // due here: sunk into the conditional uses below, the sums drag all 51 reads along
-            if (i >= beg + 75) {
-                A[i - abase] = a0;
-                if (bestv < a0) {  // i ascends within a thread: strict '<' keeps the first maximum
-                    bestv = a0;
-                    besti = i;
-                }
-            }
-            if (i + 1 < end - 75) {
-                A[i + 1 - abase] = a1;
-                if (bestv < a1) {
-                    bestv = a1;
-                    besti = i + 1;
-                }
-            }
+            boxcar_put(a0, a1, A + (i - abase), i, beg, end, bestv, besti);
         }
         wave_first_max(bestv, besti);
         if (lane == 0) {
@@ -1283,34 +1245,17 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
             redi[wave] = besti;
         }
         __syncthreads();
-        PHASE(7)
+        ACQ_PHASE(clk, 7)
         // ---- centre-bin rule (:444-453), evaluated by every thread on the same values
         {
-            // the twelve per-wave maxima meet in lanes 0..11 of every wave (the same combine as above: larger value,
-            // then smaller index; an empty candidate never wins) -- as a 12-step loop run by every thread this cost the
-            // SIMDs 3.6k cycles a frame
-            double mv = 0.0;
-            int mi = -1;
-            if (lane < FM_T / 64) {
-                mv = redv[lane];
-                mi = redi[lane];
-            }
-            wave_first_max(mv, mi);
-            const double maxBin = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(mv)),
-                                                   __builtin_amdgcn_readfirstlane(__double2loint(mv)));
-            const int binPos = __builtin_amdgcn_readfirstlane(mi);
-            if (centreBin < 0) centreBin = 0;
-            if (centreBin > end - 1) centreBin = end - 1;
-            // aveTemp is cleared per frame (:431) and only [beg+75, end-75) is filled
-            const double atc = (centreBin >= beg + 75 && centreBin < end - 75) ? A[centreBin - abase] : 0.0;
-            avePeakPower = (PSD_AVG * atc) + (PSD_INV * avePeakPower);
-            if (maxBin > (avePeakPower / 4) * 5 && binPos > 0) {
-                aveCentreBin = (CFREQ_AVG * (double)(float)binPos) + (CFREQ_INV * aveCentreBin);
-                centreBin = (int)(aveCentreBin + (double)1.0F);
-            }
-            if (centreBin < 102) centreBin = 102;
+            double maxBin;
+            int binPos;
+            wg_first_max<FM_T / 64>(redv, redi, lane, maxBin, binPos);
+            centreBin = centre_bin_clamp(centreBin, end);
+            const double atc = acq_band_filled(centreBin, beg, end) ? A[centreBin - abase] : 0.0;
+            centre_bin_step(avePeakPower, aveCentreBin, centreBin, atc, maxBin, binPos);
         }
-        PHASE(2)
+        ACQ_PHASE(clk, 2)
         // ---- 204 bins around the centre to bin 0 of a zeroed array (:458), inverse transform (:459) as
         // conj o forward o conj; only real parts are read afterwards, so the closing conjugation is dropped
         if (compact) {
@@ -1322,17 +1267,16 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
                 fm_inv_blocks<4800, true>(XL, XL + (centreBin - 102), t64, 1, t64, 2, tf);
             else
                 fm_inv_pair_from_bins<2, 3, 4410>(XL, XL + (centreBin - 102), lds_arr(twL) + 2, tf);  // 4410: the first pair
-            PHASE(3)
+            ACQ_PHASE(clk, 3)
             fm_forward<true>(XL, twL, aa, tf, true, FM_INV_REAL, 0, norm, hist);
-            PHASE(4)
+            ACQ_PHASE(clk, 4)
             // ---- RxDownSample(re, re) (:461-463, :470-492) from the compact samples: sample t of the frame at double slot
             // FM_RB0 + t, the previous frame's last 26 in front of them -- every window is one contiguous run
             {
                 // (the last frame asks for itself again: a request under a branch would make every later wait the minimum over both paths)
                 if (n == 9600) fm_first2_request<9600, F32IN>(pre, raw + (f + 1 < a.nframes ? t0 + n : t0), rawf + (f + 1 < a.nframes ? t0 + n : t0), tf);
                 const double *Rb = reinterpret_cast<const double *>(smem);
-                long long jlo = (t0 - a.first_out + D - 1) / D;
-                if (t0 <= a.first_out) jlo = 0;
+                const long long jlo = ds_first_output(t0, a.first_out, D);
                 const bool even_d = (D & 1) == 0;                 // then every window of the call ends on the same parity (n is even)
                 const int par = (int)((a.first_out - t0) & 1);
                 for (long long j = jlo + tf;; j += FM_T) {
@@ -1340,36 +1284,14 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
                     if (te >= t0 + n || j >= a.nds) break;
                     const double2 cs = a.vco_cs[j];
                     const int e = (int)(te - t0);  // 0..n-1 within the frame
-                    double fi = 0.0;
-                    if (even_d) {
-                        // the 27 samples e-26 .. e as 14 aligned 16-byte reads: d[i] = slot ((e + 6) & ~1) + i
-                        const double2 *w2 = reinterpret_cast<const double2 *>(Rb + ((e + FM_RB0 - 26) & ~1));
-                        double d[28];
-#pragma unroll
-                        for (int i = 0; i < 14; i++) {
-                            const double2 t = w2[i];
-                            d[2 * i] = t.x;
-                            d[2 * i + 1] = t.y;
-                        }
-                        if (par) {
-#pragma unroll
-                            for (int k = 0; k < 27; k++) fi += d[27 - k] * ds_tap(k);  // newest first (:479-483)
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 27; k++) fi += d[26 - k] * ds_tap(k);
-                        }
-                    } else {
-                        const double *w = Rb + (FM_RB0 + e);
-#pragma unroll
-                        for (int k = 0; k < 27; k++) fi += w[-k] * ds_tap(k);
-                    }
-                    const double o = fi * HOWARD;  // fi == fq: both rails get the same samples
+                    const double fi = ds_window_compact(Rb, FM_RB0, e, even_d, par);
+                    const double o = fi * ACQ_HOWARD;  // fi == fq: both rails get the same samples
                     dm[64 + j] = make_double2(o * cs.x, o * cs.y);  // :515-516
                 }
                 if (tf < 26) hist[tf] = Rb[FM_RB0 + n - 26 + tf];  // (nobody reads hist[] before the next frame's last pass)
                 __syncthreads();  // every window is read before the next frame's first pass overwrites the image
             }
-            PHASE(5)
+            ACQ_PHASE(clk, 5)
             continue;
         } else {
             double2 keep = make_double2(0.0, 0.0);
@@ -1379,34 +1301,25 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
             __syncthreads();
             if (tf < 204) X[tf] = make_double2(keep.x, -keep.y);
             __syncthreads();
-            PHASE(3)
+            ACQ_PHASE(clk, 3)
             fm_forward<true>(XL, twL, aa, tf, false);
             for (int i = tf; i < n; i += FM_T) X[i].x = X[i].x * norm;  // re = X.x / n (:462)
             __syncthreads();
         }
-        PHASE(4)
+        ACQ_PHASE(clk, 4)
         if (tf < 26) hist[26 + tf] = X[tf].x;
         __syncthreads();
         // ---- RxDownSample(re, re) (:461-463, :470-492): outputs whose window ends inside this frame
         {
-            long long jlo = (t0 - a.first_out + D - 1) / D;
-            if (t0 <= a.first_out) jlo = 0;
+            const long long jlo = ds_first_output(t0, a.first_out, D);
             for (long long j = jlo + tf;; j += FM_T) {
                 const long long te = (long long)a.first_out + (long long)D * j;  // window end, call-relative
                 if (te >= t0 + n || j >= a.nds) break;
                 const double2 cs = a.vco_cs[j];
                 const int e = (int)(te - t0);  // 0..n-1 within the frame
-                double fi = 0.0;
-                if (e >= 26) {  // all but the first three windows of a frame: no history, constant offsets
-                    const double2 *w = X + e;
-#pragma unroll
-                    for (int k = 0; k < 27; k++) fi += w[-k].x * ds_tap(k);  // newest first (:479-483)
-                } else {
-                    const double *w = hist + 26 + e;  // the first three windows of a frame: history, then the frame's head
-#pragma unroll
-                    for (int k = 0; k < 27; k++) fi += w[-k] * ds_tap(k);
-                }
-                const double o = fi * HOWARD;  // fi == fq: both rails get the same samples
+                // all but the first three windows of a frame: no history, constant offsets; those three: history, then the head of the frame
+                const double fi = e >= 26 ? ds_window(X + e) : ds_window(hist + 26 + e);
+                const double o = fi * ACQ_HOWARD;  // fi == fq: both rails get the same samples
                 dm[64 + j] = make_double2(o * cs.x, o * cs.y);  // :515-516
             }
         }
@@ -1415,14 +1328,11 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
         __syncthreads();
         if (tf < 26) hist[tf] = hnew;
         __syncthreads();
-        PHASE(5)
+        ACQ_PHASE(clk, 5)
     }
-#undef PHASE
     if (tid < 26) sp->hist[tid] = hist[tid];
     if (tid == 0) {
-        sp->avePeakPower = avePeakPower;
-        sp->aveCentreBin = aveCentreBin;
-        sp->centreBin = centreBin;
+        acq_state_store(sp, avePeakPower, aveCentreBin, centreBin);
         if (timing)
             for (int k = 0; k < 8; k++) a.phase_clk[k] = clk[k];
     }
@@ -1437,6 +1347,8 @@ __global__ __launch_bounds__(FM_T) void k_front_fftm(FftmArgs aa)
 // halves with each frame's own centre bin, and RxDownSample: frame f + 1's windows reach back into frame f's samples, which lie in
 // the first image.  A call's odd last frame runs as a pair whose second half is computed and dropped.  Same operations on the same
 // operands per frame as k_front_fftm.
+// (This kernel states the frame stages itself and not through bpsk_fft.h / bpsk_acq_rule.h: on the shared ones its 4800 form
+//  ran 7.7 % slower at unchanged resources, profiles/acq_stages_ab.md.)
 template <int NN, bool F32IN>
 __global__ __launch_bounds__(FM_T) void k_front_fftm2(FftmArgs aa)
 {
@@ -1748,8 +1660,7 @@ __global__ __launch_bounds__(FM_T) void k_acqm_fwd(FftmArgs aa, AcqArgs a)
     int *tkL = reinterpret_cast<int *>(twL + aa.lds_tw);  // (the 64 spare bytes behind the tables)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid; i < aa.lds_tw; i += FM_T) twL[i] = aa.f.tw[i];
-    const int beg = a.do_up ? n / 4 : 0;
-    const int end = a.do_up ? n / 2 : n / 4;
+    const int beg = acq_band_beg(n, a.do_up), end = acq_band_end(n, a.do_up);
     const int pbase = beg + 24;
     double *P = reinterpret_cast<double *>(X + (n / 2 + 104));  // (the sums go straight to the frame's row in global memory)
     const long long nfr = (long long)a.S * a.F;
@@ -1783,15 +1694,7 @@ __global__ __launch_bounds__(FM_T) void k_acqm_fwd(FftmArgs aa, AcqArgs a)
             for (int q = 0; q < NLD; q++) {
                 const int t = tf + q * FM_T;
                 if (t < n) {
-                    double di, dq;
-                    if (F32IN) {
-                        di = (double)wf[q].x;
-                        dq = (double)wf[q].y;
-                    } else {
-                        di = (double)i16_to_float_java(java_short_add((int)(short)(w[q] & 0xffff), a.ic));
-                        dq = (double)i16_to_float_java(java_short_add(w[q] >> 16, a.qc));
-                    }
-                    X[t] = make_double2(di, dq);
+                    X[t] = F32IN ? acq_sample(wf[q]) : acq_sample(w[q], a.ic, a.qc);
                 }
             }
             __syncthreads();
@@ -1819,21 +1722,7 @@ __global__ __launch_bounds__(FM_T) void k_acqm_fwd(FftmArgs aa, AcqArgs a)
             const double2 *w = reinterpret_cast<const double2 *>(P + (i - 50 - pbase));
             double a0, a1;
             boxcar_pair(w, a0, a1);
-            asm volatile("" : "+v"(a0), "+v"(a1));
-            if (i >= beg + 75) {
-                ab[i - (beg + 75)] = a0;
-                if (bestv < a0) {
-                    bestv = a0;
-                    besti = i;
-                }
-            }
-            if (i + 1 < end - 75) {
-                ab[i + 1 - (beg + 75)] = a1;
-                if (bestv < a1) {
-                    bestv = a1;
-                    besti = i + 1;
-                }
-            }
+            boxcar_put(a0, a1, ab + (i - (beg + 75)), i, beg, end, bestv, besti);
         }
         wave_first_max(bestv, besti);
         if (lane == 0) {
@@ -1844,14 +1733,7 @@ __global__ __launch_bounds__(FM_T) void k_acqm_fwd(FftmArgs aa, AcqArgs a)
         if (tid == 0) {
             double mv = 0.0;
             int mi = -1;
-            for (int w = 0; w < FM_T / 64; w++) {
-                const double ov = redv[w];
-                const int oi = redi[w];
-                if (oi >= 0 && (ov > mv || (ov == mv && (mi < 0 || oi < mi)))) {
-                    mv = ov;
-                    mi = oi;
-                }
-            }
+            for (int w = 0; w < FM_T / 64; w++) first_max_merge(mv, mi, redv[w], redi[w]);
             AcqPeak pk;
             pk.maxBin = mv;
             pk.binPos = mi;
@@ -1878,7 +1760,6 @@ __global__ __launch_bounds__(FM_T) void k_acqm_inv(FftmArgs aa, AcqArgs a)
     if (tid < 32) hist[tid] = 0.0;
     const int D = a.decim;
     const double norm = 1.0 / (double)n;
-    const double HOWARD = 0.9 * 32768.0;
     const int lo1 = a.do_up ? n / 4 - 26 : 0;
     const long long nfr = (long long)a.S * a.F;
     __syncthreads();
@@ -1920,8 +1801,7 @@ __global__ __launch_bounds__(FM_T) void k_acqm_inv(FftmArgs aa, AcqArgs a)
                 eg[tf] = Rb[FM_RB0 + tf];
                 eg[26 + tf] = Rb[FM_RB0 + n - 26 + tf];
             }
-            long long jlo = (t0 - a.first_out + D - 1) / D;
-            if (t0 <= a.first_out) jlo = 0;
+            const long long jlo = ds_first_output(t0, a.first_out, D);
             const bool even_d = (D & 1) == 0;
             const int par = (int)((a.first_out - t0) & 1);
             for (long long j = jlo + tf;; j += FM_T) {
@@ -1930,29 +1810,8 @@ __global__ __launch_bounds__(FM_T) void k_acqm_inv(FftmArgs aa, AcqArgs a)
                 const int e = (int)(te - t0);
                 if (e < 26) continue;
                 const double2 cs = a.vco_cs[j];
-                double fi = 0.0;
-                if (even_d) {
-                    const double2 *w2 = reinterpret_cast<const double2 *>(Rb + ((e + FM_RB0 - 26) & ~1));
-                    double d[28];
-#pragma unroll
-                    for (int i = 0; i < 14; i++) {
-                        const double2 t = w2[i];
-                        d[2 * i] = t.x;
-                        d[2 * i + 1] = t.y;
-                    }
-                    if (par) {
-#pragma unroll
-                        for (int k = 0; k < 27; k++) fi += d[27 - k] * ds_tap(k);  // newest first (:479-483)
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 27; k++) fi += d[26 - k] * ds_tap(k);
-                    }
-                } else {
-                    const double *w = Rb + (FM_RB0 + e);
-#pragma unroll
-                    for (int k = 0; k < 27; k++) fi += w[-k] * ds_tap(k);
-                }
-                const double o = fi * HOWARD;
+                const double fi = ds_window_compact(Rb, FM_RB0, e, even_d, par);
+                const double o = fi * ACQ_HOWARD;
                 a.dm[(long long)s * a.dm_stride + 64 + j] = make_double2(o * cs.x, o * cs.y);  // :515-516
             }
         }
@@ -2133,19 +1992,16 @@ __global__ __launch_bounds__(FM_T) void k_front_fft2x(Fft2xArgs aa)
     const bool pruned = (m == 9600);  // the 192 kHz default: pruned passes (fm_inv_blocks, fm_pass5_band / _real)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = blockIdx.x;
-    const int beg = a.do_up ? n / 4 : 0;
-    const int end = a.do_up ? n / 2 : n / 4;
+    const int beg = acq_band_beg(n, a.do_up), end = acq_band_end(n, a.do_up);
     const int pbase = beg + 24, abase = beg + 74;
     // |X| and the boxcar sums live behind the odd bins the gather may still need (bins < n/2 + 102 <=> slot < m/2 + 51)
     double *P = reinterpret_cast<double *>(X + (m / 2 + 56));
     double *A = P + (n / 4 - 48);
     FftFrontState *sp = &a.st[s];
     if (tid < 26) hist[tid] = sp->hist[tid];
-    double avePeakPower = sp->avePeakPower, aveCentreBin = sp->aveCentreBin;
-    int centreBin = sp->centreBin;
-    const double CFREQ_INV = (double)(1.0F - (2.0F / (1 + 1))), CFREQ_AVG = (double)(2.0F / (1 + 1));
-    const double PSD_INV = (double)(1.0F - (2.0F / (10 + 1))), PSD_AVG = (double)(2.0F / (10 + 1));
-    const double HOWARD = 0.9 * 32768.0;
+    double avePeakPower, aveCentreBin;
+    int centreBin;
+    acq_state_load(sp, avePeakPower, aveCentreBin, centreBin);
     const int D = a.decim;
     const double norm = 1.0 / (double)n;
     const int *__restrict__ raw = a.raw + (long long)s * a.stride_pairs;
@@ -2159,18 +2015,8 @@ __global__ __launch_bounds__(FM_T) void k_front_fft2x(Fft2xArgs aa)
     // the radix-2 first pass straight from the frame's samples: X[b] = x[b] +/- x[b + m]   (:416-421, dft_r<2>)
     auto load_half = [&](long long t0, int c, int tf) {
         for (int b = tf; b < m; b += FM_T) {
-            double2 v0, v1;
-            if (F32IN) {
-                const float2 f0 = rawf[t0 + b], f1 = rawf[t0 + b + m];
-                v0 = make_double2((double)f0.x, (double)f0.y);
-                v1 = make_double2((double)f1.x, (double)f1.y);
-            } else {
-                const int w0 = raw[t0 + b], w1 = raw[t0 + b + m];
-                v0 = make_double2((double)i16_to_float_java(java_short_add((int)(short)(w0 & 0xffff), a.ic)),
-                                  (double)i16_to_float_java(java_short_add(w0 >> 16, a.qc)));
-                v1 = make_double2((double)i16_to_float_java(java_short_add((int)(short)(w1 & 0xffff), a.ic)),
-                                  (double)i16_to_float_java(java_short_add(w1 >> 16, a.qc)));
-            }
+            const double2 v0 = F32IN ? acq_sample(rawf[t0 + b]) : acq_sample(raw[t0 + b], a.ic, a.qc);
+            const double2 v1 = F32IN ? acq_sample(rawf[t0 + b + m]) : acq_sample(raw[t0 + b + m], a.ic, a.qc);
             X[b] = c ? cdsub(v0, v1) : cdadd(v0, v1);
         }
         __syncthreads();
@@ -2223,21 +2069,7 @@ __global__ __launch_bounds__(FM_T) void k_front_fft2x(Fft2xArgs aa)
             const double2 *w = reinterpret_cast<const double2 *>(P + (i - 50 - pbase));
             double a0, a1;
             boxcar_pair(w, a0, a1);
-            asm volatile("" : "+v"(a0), "+v"(a1));
-            if (i >= beg + 75) {
-                A[i - abase] = a0;
-                if (bestv < a0) {
-                    bestv = a0;
-                    besti = i;
-                }
-            }
-            if (i + 1 < end - 75) {
-                A[i + 1 - abase] = a1;
-                if (bestv < a1) {
-                    bestv = a1;
-                    besti = i + 1;
-                }
-            }
+            boxcar_put(a0, a1, A + (i - abase), i, beg, end, bestv, besti);
         }
         wave_first_max(bestv, besti);
         if (lane == 0) {
@@ -2247,28 +2079,12 @@ __global__ __launch_bounds__(FM_T) void k_front_fft2x(Fft2xArgs aa)
         __syncthreads();
         // ---- centre-bin rule (:444-453)
         {
-            // the twelve per-wave maxima meet in lanes 0..11 of every wave (the same combine as above: larger value,
-            // then smaller index; an empty candidate never wins) -- as a 12-step loop run by every thread this cost the
-            // SIMDs 3.6k cycles a frame
-            double mv = 0.0;
-            int mi = -1;
-            if (lane < FM_T / 64) {
-                mv = redv[lane];
-                mi = redi[lane];
-            }
-            wave_first_max(mv, mi);
-            const double maxBin = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(mv)),
-                                                   __builtin_amdgcn_readfirstlane(__double2loint(mv)));
-            const int binPos = __builtin_amdgcn_readfirstlane(mi);
-            if (centreBin < 0) centreBin = 0;
-            if (centreBin > end - 1) centreBin = end - 1;
-            const double atc = (centreBin >= beg + 75 && centreBin < end - 75) ? A[centreBin - abase] : 0.0;
-            avePeakPower = (PSD_AVG * atc) + (PSD_INV * avePeakPower);
-            if (maxBin > (avePeakPower / 4) * 5 && binPos > 0) {
-                aveCentreBin = (CFREQ_AVG * (double)(float)binPos) + (CFREQ_INV * aveCentreBin);
-                centreBin = (int)(aveCentreBin + (double)1.0F);
-            }
-            if (centreBin < 102) centreBin = 102;
+            double maxBin;
+            int binPos;
+            wg_first_max<FM_T / 64>(redv, redi, lane, maxBin, binPos);
+            centreBin = centre_bin_clamp(centreBin, end);
+            const double atc = acq_band_filled(centreBin, beg, end) ? A[centreBin - abase] : 0.0;
+            centre_bin_step(avePeakPower, aveCentreBin, centreBin, atc, maxBin, binPos);
         }
         // ---- 204 bins around the centre to bin 0 of a zeroed array (:458); inverse (:459) as conj o forward o conj
         double2 keep = make_double2(0.0, -0.0);  // conj of the zeroed array
@@ -2312,8 +2128,7 @@ __global__ __launch_bounds__(FM_T) void k_front_fft2x(Fft2xArgs aa)
             return t < 0 ? hist[26 + t] : ((t & 1) ? (pruned ? Ro[t >> 1] : X[t >> 1].x) : r0[t >> 1]);
         };
         {
-            long long jlo = (t0 - a.first_out + D - 1) / D;
-            if (t0 <= a.first_out) jlo = 0;
+            const long long jlo = ds_first_output(t0, a.first_out, D);
             // with an even decimation (20 at 192 kHz) every window of the call ends on the same parity (t0 is even): which
             // of the 27 taps read the scratch and which the image is then known at compile time
             const bool uniform_parity = (D & 1) == 0;
@@ -2379,7 +2194,7 @@ __global__ __launch_bounds__(FM_T) void k_front_fft2x(Fft2xArgs aa)
 #pragma unroll
                     for (int k = 0; k < 27; k++) fi += sample(e - k) * ds_tap(k);  // newest first (:479-483)
                 }
-                const double o = fi * HOWARD;
+                const double o = fi * ACQ_HOWARD;
                 __builtin_nontemporal_store(o * cs.x, &dm[64 + j].x);  // :515-516 (written once, read by the next kernel)
                 __builtin_nontemporal_store(o * cs.y, &dm[64 + j].y);
             }
@@ -2392,9 +2207,7 @@ __global__ __launch_bounds__(FM_T) void k_front_fft2x(Fft2xArgs aa)
     }
     if (tid < 26) sp->hist[tid] = hist[tid];
     if (tid == 0) {
-        sp->avePeakPower = avePeakPower;
-        sp->aveCentreBin = aveCentreBin;
-        sp->centreBin = centreBin;
+        acq_state_store(sp, avePeakPower, aveCentreBin, centreBin);
     }
 }
 
