@@ -36,12 +36,29 @@ struct FftFrontArgs {
 // dsFilter (FUNcubeBPSKDemod.java:27-55, symmetric: first 14 of 27), device-side copy with a static initialiser:
 // indexed with compile-time constants in the front-end kernels, so the taps fold into the instruction stream (14
 // distinct values) instead of occupying 54 SGPRs or an LDS read per multiply
-static __constant__ const float kDsHalf[14] = {-6.103515625000e-004F, -1.220703125000e-004F, +2.380371093750e-003F,
+static __constant__ constexpr float kDsHalf[14] = {-6.103515625000e-004F, -1.220703125000e-004F, +2.380371093750e-003F,
                                         +6.164550781250e-003F, +7.324218750000e-003F, +7.629394531250e-004F,
                                         -1.464843750000e-002F, -3.112792968750e-002F, -3.225708007813e-002F,
                                         -1.617431640625e-003F, +6.463623046875e-002F, +1.502380371094e-001F,
                                         +2.231445312500e-001F, +2.518310546875e-001F};
 __device__ __forceinline__ double ds_tap(int n) { return (double)kDsHalf[n < 14 ? n : 26 - n]; }
+// bit n: tap n is +-2^k, so a product with it is exact and `a + d*tap` is the same double as fma(d, tap, a) -- which the
+// exact-order filters (-ffp-contract=off) then write themselves (k_fm).  Derived from the table: today taps 1 and 25 (-2^-13).
+constexpr unsigned ds_pow2_mask()
+{
+    unsigned mask = 0;
+    for (int n = 0; n < 27; n++) {
+        float v = kDsHalf[n < 14 ? n : 26 - n];
+        v = v < 0 ? -v : v;
+        if (v == 0) continue;
+        while (v < 1) v *= 2;
+        while (v >= 2) v /= 2;
+        if (v == 1) mask |= 1u << n;
+    }
+    return mask;
+}
+constexpr unsigned kDsPow2Mask = ds_pow2_mask();
+static_assert(kDsPow2Mask == ((1u << 1) | (1u << 25)), "dsFilter: taps 1 and 25 are the powers of two");
 
 // Two adjacent 100-wide boxcar sums from the same 51 aligned 16-byte reads w[0..50] (w[0].x = P[i-50]):
 //   a0 = P[i-50] + ... + P[i+49],  a1 = P[i-49] + ... + P[i+50], each in ascending order (:433-437).

@@ -243,7 +243,10 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
     const int *edges = a.edges + (long long)s * (4 * FM_EDGE);
     const double2 *dmh_old = a.dmh_old + (long long)s * 64;
     const int Lm1 = a.nsamples - 1, nds = a.nds, P = a.tper;
-    const double HOWARD = 0.9 * 32768.0;  // :469
+    // :469 HOWARD_FUDGE_FACTOR = 0.9 * 32768, times the 2^-15 that takes out the conversion's scale (fm_convert_2p15: di, dq
+    // and with them the tuner products and the 27-tap sums are 2^15 times the reference's, exactly; the product with
+    // HOWARD * 2^-15 -- an exact constant -- is then the reference's double)
+    const double HOWARD = 0.9 * 32768.0 * (double)I16_2P15_UNSCALE;
     // tile-uniform base into the unwrapped tuner table: window sample m of ANY job of this tile uses entry e0 + m
     // (the lane span RD is a multiple of the period)
     int e0 = 0;
@@ -332,7 +335,7 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
                     if (m < NS) {
                         const int w = (t == 0) ? w4.x : (t == 1) ? w4.y : (t == 2) ? w4.z : w4.w;
                         double di, dq;
-                        fm_convert(w, a.ic, a.qc, DC, di, dq, FAST ? &amx : nullptr);
+                        fm_convert_2p15(w, a.ic, a.qc, DC, di, dq, FAST ? &amx : nullptr);  // 2^15 x the reference's (HOWARD)
                         if constexpr (MIX) {  // :388-390 component-wise, not a complex multiply
                             di = di * tb[2 * m];
                             dq = dq * tb[2 * m + 1];
@@ -340,8 +343,13 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
 #pragma unroll
                         for (int r = 0; r < R; r++) {
                             if (m >= D * r && m <= D * r + 26) {  // age D*r+26-m in the window of output r
-                                const double tp = ds_tap(D * r + 26 - m);
-                                if constexpr (FAST) {
+                                const int age = D * r + 26 - m;
+                                const double tp = ds_tap(age);
+                                // exact order, and still one instruction where the fma IS the separately rounded pair:
+                                // the output's first tap (the sum is +0.0: a product of either sign of zero gives +0
+                                // both ways) and a tap that is a power of two (the product is exact)
+                                const bool same = age == 0 || ((kDsPow2Mask >> age) & 1);
+                                if (FAST || same) {
                                     ai[r] = __builtin_fma(di, tp, ai[r]);
                                     aq[r] = __builtin_fma(dq, tp, aq[r]);
                                 } else {

@@ -22,14 +22,21 @@ __device__ __forceinline__ void matched_block(const double2 *xl /* &X[s0] of thi
                                               double (&aq)[R])
 {
     const double *f = c_bpsk.dm_taps;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        ai[r] = 0.0;
-        aq[r] = 0.0;
-    }
     // phase 1: s = s0 - i, ages u+i.  main part: every output still has a tap
-    const int n1 = 66 - u0 - R;
-    int i = 0;
+    const int n1 = 66 - u0 - R;  // >= 1
+    // step i = 0 is every accumulator's first product.  The reference's `0.0 + x*t` is written as fma(x, t, +0.0): the same
+    // double (a non-zero product is rounded once either way, a zero product of either sign gives +0 either way) in one
+    // instruction instead of two; the compiler may not do that itself, for the signed zero.
+    {
+        const double2 v = xl[0];
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const double t = f[u0 + r];
+            ai[r] = __builtin_fma(v.x, t, 0.0);
+            aq[r] = __builtin_fma(v.y, t, 0.0);
+        }
+    }
+    int i = 1;
 #ifndef JSDR_MATCHED_NO_CHUNKS
     // eight steps at a time: their 8+R-1 taps come in with one pair of scalar loads and their eight samples with eight
     // LDS reads in flight together -- as a plain loop the compiler reloads all R taps every other step and waits for each

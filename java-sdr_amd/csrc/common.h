@@ -126,12 +126,28 @@ struct SyncOnExit {
 // rl = RN(1/d - rh): rh+rl carries 1/d to 2^-48 and no a/32767 lies that close to a rounding boundary.
 // Checked for every input in exact rational arithmetic and on the GPU against the CPU's
 // division (tests/test_gpu_fft.py, all 65536 inputs).
+// (k_fm and k_fft's int16 path convert with i16_to_float_java_2p15 below, one instruction instead of two; every other
+//  caller uses this form.)
 __device__ __forceinline__ float i16_to_float_java(int s)
 {
     const float rh = 0x1.0002p-15f;
     const float rl = 0x1.0002p-45f;
     const float a = (float)s;
     return __builtin_fmaf(a, rh, a * rl);
+}
+
+// 2^15 * i16_to_float_java(s), EXACTLY, in one fused multiply-add: RN(a + a*c) with c = RN(1/32767) = 0x1.0002p-15f is
+// 32768 * RN(a / 32767) for every int16 a (a * (1 + c) carries 32768/32767 to 2^-46 relative, and no quotient lies that
+// close to a rounding boundary; one ulp more in c fails for four inputs).  Proved for all 65536 inputs in exact rational
+// arithmetic by tests/test_i16_scaled_convert.py.  A caller carries the factor 2^15 -- an exact scaling, which commutes
+// with every rounded multiply, add and fma as long as nothing overflows or goes subnormal -- through its linear
+// arithmetic and takes it out in a constant that is multiplied in anyway (k_fm: HOWARD; k_fft: the second pass's
+// twiddles).
+constexpr float I16_2P15_UNSCALE = 0x1p-15f;
+__device__ __forceinline__ float i16_to_float_java_2p15(int s)
+{
+    const float a = (float)s;
+    return __builtin_fmaf(a, 0x1.0002p-15f, a);
 }
 
 // `short s = getShort(); s += (short)corr;` -- 16-bit wrap-around add
@@ -157,6 +173,24 @@ __device__ __forceinline__ void fm_convert(int w, int ic, int qc, bool dc, doubl
     if (amax) *amax = fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), *amax);  // v_max3_f32 with |.| modifiers: one instruction
     const v2f rh = {0x1.0002p-15f, 0x1.0002p-15f}, rl = {0x1.0002p-45f, 0x1.0002p-45f};
     const v2f q = __builtin_elementwise_fma(a, rh, a * rl);
+    di = (double)q.x;
+    dq = (double)q.y;
+}
+
+// fm_convert with the quotients SCALED by 2^15 (i16_to_float_java_2p15: one v_pk_fma_f32, no v_pk_mul_f32): di, dq are
+// exactly 32768 times what fm_convert gives; amax is taken from (float)s and is the same.
+__device__ __forceinline__ void fm_convert_2p15(int w, int ic, int qc, bool dc, double &di, double &dq, float *amax = nullptr)
+{
+    int si = (int)(short)(w & 0xffff), sq = w >> 16;
+    if (dc) {
+        si = java_short_add(si, ic);
+        sq = java_short_add(sq, qc);
+    }
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const v2f a = {(float)si, (float)sq};
+    if (amax) *amax = fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), *amax);
+    const v2f c = {0x1.0002p-15f, 0x1.0002p-15f};
+    const v2f q = __builtin_elementwise_fma(a, c, a);
     di = (double)q.x;
     dq = (double)q.y;
 }

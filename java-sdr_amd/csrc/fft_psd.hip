@@ -103,7 +103,19 @@ __device__ __forceinline__ void fft_fetch(const FftArgs &a, long long frame, int
 // One Stockham pass of one frame by T threads.  Each thread owns ITERS = (N/R)/T butterflies, loads
 // them all (global for the first pass, LDS otherwise), transforms in registers, and only after a
 // barrier (every load of the in-place image has landed) writes its outputs.
-template <int N, int T, int IN, int OUT, int R, int P, bool FIRST, bool LAST, class RAW = int>
+//
+// The int16 path's scale (SC): its first pass converts with i16_to_float_java_2p15 (common.h) -- one fma per value where
+// the reference rule takes a multiply and an fma -- so its butterflies (P = 1: no table; sums and constant products only)
+// run on values that are EXACTLY 2^15 times the float path's.  The second pass takes the factor out in the multiply it does
+// anyway: the int16 launch's copy of that pass's "direct" table is pre-multiplied by 2^-15 (jsdr_fft::tw_i16; exact, and
+// (2^15 a) * (2^-15 w) is the same real product, hence the same float), and element 0 of each butterfly, which has no
+// twiddle, gets one packed multiply.  From there on every value is bit for bit the float path's
+// (tests/test_gpu_fft_i16_scaled.py).  SC_IN: this (first) pass produces scaled values; SC_OUT: this (second) pass removes
+// the scale.  A plan whose second pass is not "direct" keeps the two-instruction conversion.
+enum { SC_NONE = 0, SC_IN = 1, SC_OUT = 2 };
+constexpr bool fft_i16_scaled(int R0, int R1) { return tw_direct(R0, R1); }
+
+template <int N, int T, int IN, int OUT, int R, int P, bool FIRST, bool LAST, class RAW = int, int SC = SC_NONE>
 __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool active, int tid, float2 *buf,
                                          const float2 *tab, Best &best, const RAW *raw = nullptr)
 {
@@ -123,17 +135,17 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool
                 if (active) {
                     if constexpr (IN == IN_I16) {
                         const RAW *w = raw;
+                        auto cvt = [](int s) { return SC == SC_IN ? i16_to_float_java_2p15(s) : i16_to_float_java(s); };
                         if ((a.ic | a.qc) == 0) {  // uniform: no DC correction (the usual case), two adds per sample less
 #pragma unroll
                             for (int r = 0; r < R; r++)
-                                v[gi][r] = make_float2(i16_to_float_java((int)(short)(w[r] & 0xffff)),
-                                                       i16_to_float_java(w[r] >> 16));
+                                v[gi][r] = make_float2(cvt((int)(short)(w[r] & 0xffff)), cvt(w[r] >> 16));
                         } else {
 #pragma unroll
                             for (int r = 0; r < R; r++) {
                                 int si = java_short_add((int)(short)(w[r] & 0xffff), a.ic);
                                 int sq = java_short_add(w[r] >> 16, a.qc);
-                                v[gi][r] = make_float2(i16_to_float_java(si), i16_to_float_java(sq));
+                                v[gi][r] = make_float2(cvt(si), cvt(sq));
                             }
                         }
                     } else {
@@ -148,6 +160,7 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool
 #pragma unroll
                 for (int r = 0; r < R; r++) v[gi][r] = buf[lds_pad(b + r * NB)];
             }
+            if constexpr (SC == SC_OUT) v[gi][0] = from_v(to_v(v[gi][0]) * I16_2P15_UNSCALE);
             apply_twiddles<R, P>(v[gi], b & (P - 1), tab);
             dft_reg<R>(v[gi]);
         }
@@ -215,12 +228,13 @@ __device__ __forceinline__ void fft_frame(const FftArgs &a, long long frame, lon
     best.v = -3.402823466e+38f;
     best.k = 0x7fffffff;
     constexpr int O1 = 0, O2 = tw_size(R0, R1), O3 = O2 + tw_size(R0 * R1, R2);
-    fft_pass<N, T, IN, OUT, R0, 1, true, false, RAW>(a, frame, active, tid, buf, tw_lds, best, raw);
+    constexpr bool SC = IN == IN_I16 && fft_i16_scaled(R0, R1);
+    fft_pass<N, T, IN, OUT, R0, 1, true, false, RAW, SC ? SC_IN : SC_NONE>(a, frame, active, tid, buf, tw_lds, best, raw);
     // (unconditional: a workgroup's last frame fetches itself again -- with a branch around the loads the compiler cannot
     //  count what is in flight at the loop head and waits for everything, the previous frame's stores included)
     auto prefetch = [&] { fft_fetch<N, T, IN, R0>(a, next, tid, raw); };
     if constexpr (NPASS == 2) prefetch();
-    fft_pass<N, T, IN, OUT, R1, R0, false, NPASS == 2>(a, frame, active, tid, buf, tw_lds + O1, best);
+    fft_pass<N, T, IN, OUT, R1, R0, false, NPASS == 2, int, SC ? SC_OUT : SC_NONE>(a, frame, active, tid, buf, tw_lds + O1, best);
     if constexpr (NPASS >= 3) {
         if constexpr (NPASS == 3) prefetch();
         fft_pass<N, T, IN, OUT, R2, R0 * R1, false, NPASS == 3>(a, frame, active, tid, buf, tw_lds + O2, best);
@@ -379,6 +393,7 @@ struct jsdr_fft {
     int n = 0;
     int rate = 0;
     DevBuf<float2> tw;
+    DevBuf<float2> tw_i16;           // k_fft's int16 launches: `tw` with the second pass's segment times 2^-15 (fft_pass, SC)
     DevBuf<unsigned char> in_stage;  // one frame, for the host-buffer receive() forms
     DevBuf<float> out_stage;
     PinnedStage pin;                 // [frame in (8 n bytes) | psd out (4 (n + 2) bytes)] for the receive() forms
@@ -438,7 +453,7 @@ static int fft_run(jsdr_fft *h, const void *in_dev, int in_kind, int out_kind, l
     JSDR_REQUIRE(l.launch, "fft: no kernel for n=%d in=%d out=%d", h->n, in_kind, out_kind);
     a.in = in_dev;
     a.out = out_dev;
-    a.tw = h->tw.p;
+    a.tw = in_kind == IN_I16 ? h->tw_i16.p : h->tw.p;
     a.nframes = nframes;
     a.rate = h->rate;
     a.ic = ic;
@@ -559,12 +574,18 @@ int jsdr_fft_create(jsdr_fft **out, int n, int rate)
         delete h;
         return JSDR_ERR;
     }
-    if (h->tw.alloc(tw.size()) != JSDR_OK || h->in_stage.alloc((size_t)n * 8) != JSDR_OK ||
-        h->out_stage.alloc((size_t)n + 2) != JSDR_OK) {
+    // the int16 launches' copy: the second pass's segment (the table's first) takes the conversion's 2^15 out again
+    std::vector<float2> tw16(tw);
+    if (fft_i16_scaled(l.radix[0], l.radix[1]))
+        for (int i = 0; i < tw_size(l.radix[0], l.radix[1]); i++)
+            tw16[i] = make_float2(tw16[i].x * I16_2P15_UNSCALE, tw16[i].y * I16_2P15_UNSCALE);
+    if (h->tw.alloc(tw.size()) != JSDR_OK || h->tw_i16.alloc(tw16.size()) != JSDR_OK ||
+        h->in_stage.alloc((size_t)n * 8) != JSDR_OK || h->out_stage.alloc((size_t)n + 2) != JSDR_OK) {
         jsdr_fft_destroy(h);
         return JSDR_ERR;
     }
-    if (hipMemcpy(h->tw.p, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(h->tw.p, tw.data(), sizeof(float2) * tw.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->tw_i16.p, tw16.data(), sizeof(float2) * tw16.size(), hipMemcpyHostToDevice) != hipSuccess) {
         set_error("jsdr_fft_create: twiddle upload failed");
         jsdr_fft_destroy(h);
         return JSDR_ERR;
@@ -577,6 +598,7 @@ int jsdr_fft_destroy(jsdr_fft *h)
 {
     if (!h) return JSDR_OK;
     h->tw.release();
+    h->tw_i16.release();
     h->in_stage.release();
     h->out_stage.release();
     h->pin.release();
