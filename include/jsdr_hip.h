@@ -341,6 +341,63 @@ int jsdr_bpsk_get_stream_tuning(jsdr_bpsk *h, int stream, double *tuning_hz);
  * tu_inc -- k9_out[i]: the table index of sample i, 0 .. 255, or 256 where the sample passes through unmixed; *tu_end: tuPhase
  * after the last one (may be NULL) */
 int jsdr_bpsk_tuner_walk_host(double tu0, double tu_inc, int64_t n, uint16_t *k9_out, double *tu_end);
+/* Checkpoints: the state of a range of streams out of a handle and into one -- across a restart, a library upgrade, another
+ * machine, or between handles (a split is two saves with ranges, a merge two restores at offsets).  A blob is self-contained,
+ * versioned (format 1) and position-independent: little-endian fixed-width fields, a 192-byte header with the sizes and a
+ * 64-bit FNV-1a checksum over everything behind it, then one 7184-byte record per stream (DESIGN.md 7 has the layout).  It
+ * holds a SHARED block -- tuning, do_fft, do_up, tuPhase, tuPhaseInc, vcoPhase, dsCnt, the samples consumed and demodulated, the
+ * tuner indices and mix flags of the last 26 samples, a pending mode-switch seam, the form (int16 / float) of the input
+ * history -- and per stream: the bit clock and energy IIRs, the differential memory, the counters, the 5200-entry FEC
+ * register, decoded[], the 26-sample down-sampler and 64-sample matched-filter histories, avePeakPower / aveCentreBin /
+ * centreBin and the FFT path's history, and on a tuned handle the stream's tuning, tuPhase, tuPhaseInc and tuner indices.  A
+ * record does not depend on max_batch_samples, on the handle's strides, on which buffers were current or on which kernels
+ * the last call took: a blob restores into a handle of another max_batch_samples and another nstreams, and blobs of the
+ * same streams from two such handles are byte-identical.
+ *   state_bytes: the size of a blob of `count` streams.
+ *   save: waits for the handle's pending work (as the getters do), writes streams first .. first + count - 1 into blob_host
+ *     (cap bytes; *bytes: the blob's size) and changes nothing in the handle: a call after it gives what it would have given.
+ *     A save between set_mode / set_tuning / reconfigure and the next call carries the pending seam.
+ *   restore: writes all of the blob's streams into streams dst_first .. dst_first + count - 1.  From the next call on they
+ *     continue bit for bit as the saved ones would have: bits, (fi, fq) trace, FEC rc / bit index / bytes, the ten counters,
+ *     the 18 state doubles, decoded[].  Per-call results are not state: until that call get_bits / get_fec_count / get_trace
+ *     report an empty call for the restored streams; get_counters / get_state / get_decoded report the restored values.
+ *     jsdr_bpsk_snapshot_read of a one-stream handle is not touched: it reports "nothing received yet" (or the frame it held)
+ *     until the next receive_*.
+ *   The shared-block rule: a handle that has consumed no sample and has had nothing restored ADOPTS the blob's shared block,
+ *     a pending seam included (the FFT-acquire buffers are allocated as jsdr_bpsk_set_mode allocates them).  Any other handle
+ *     must already be at exactly that block, bit for bit, and then only the streams are written.  Streams of an adopting
+ *     handle that no blob fills run on from the zero state at the adopted sample count: which streams mean something is the
+ *     caller's business.  A restored handle cannot become JSDR_VARIANT_FAST (as a retuned one cannot).
+ *   blob_info: no device, no handle -- what a caller needs to create the right handle for a blob.
+ *   state_kernel_ms: a diagnostic -- the device time of the last save's gather kernel and of the last restore's scatter kernel
+ *     on this handle (HIP events around the launch; -1: none yet).
+ * JSDR_ERR, the handle exactly as it was, everything checked before the first write: a null pointer, a range outside the
+ * handle, cap too small, a blob that is short, has a wrong magic / version / record size or fails its checksum, a rate, frame
+ * size or kind (ordinary / tuned) other than the blob's, a shared block that is not a non-fresh handle's, a handle of
+ * jsdr_bpsk_create_channels / _create_mode_channels / _create_live_channels, a JSDR_VARIANT_FAST handle; and, because a
+ * checksum is easy to forge, a blob whose index-like values are out of range: non-finite or out-of-range tuning and phases, a
+ * tuPhaseInc that is not 2 pi tuning / rate, dsCnt or the sample counts, a bit-clock position outside 0 .. 7, a centre bin the
+ * FFT-acquire rule cannot leave, a tuned stream's tuner index above 256.  Everything else in a record (energies, counters,
+ * register entries) is data the kernels carry without indexing by it.  The promise covers REFUSALS: a call that fails later, in
+ * a device allocation, copy or launch, may leave allocated what it allocated (the staging image, the FFT-acquire buffers --
+ * which a blob holding FFT-acquire state makes any handle allocate, whatever its mode).
+ * Not covered: channel handles of all three kinds, the FAST variant and its shadow, jsdr_group_*, JNI / Java classes, device-
+ * resident blobs, jsdr_demod_* handles. */
+typedef struct jsdr_bpsk_blob_info_t {
+    int32_t version;            /* format version (1) */
+    int32_t kind;               /* 0: jsdr_bpsk_create, 1: jsdr_bpsk_create_tuned */
+    int32_t rate, nsamples_per_frame, nstreams;
+    int32_t do_fft, do_up;      /* the mode the streams continue in */
+    int32_t seam;               /* 0, or a mode switch whose first call is still to come (1: to FFT-acquire, 2: to the tune mode) */
+    int32_t record_bytes, header_bytes;
+    int64_t n_in, n_ds;         /* samples consumed / demodulated per stream (cntRaw, cntDS) */
+    double tuning_hz;           /* the shared tuning (a tuned handle: 0, each record has its own) */
+} jsdr_bpsk_blob_info_t;
+int jsdr_bpsk_state_bytes(jsdr_bpsk *h, int count, size_t *bytes);
+int jsdr_bpsk_save(jsdr_bpsk *h, int first, int count, void *blob_host, size_t cap, size_t *bytes);
+int jsdr_bpsk_restore(jsdr_bpsk *h, int dst_first, const void *blob_host, size_t bytes);
+int jsdr_bpsk_blob_info(const void *blob_host, size_t bytes, jsdr_bpsk_blob_info_t *out);
+int jsdr_bpsk_state_kernel_ms(jsdr_bpsk *h, double *pack_ms, double *unpack_ms);
 int jsdr_bpsk_acq_last_launch(jsdr_bpsk *h, int64_t *fwd_frames, int64_t *inv_frames);
 int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels);
 int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz);

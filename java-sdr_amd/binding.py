@@ -607,6 +607,31 @@ class Bpsk:
     def pack_slots(self, slots_dev, stream=None):  # stream: raw hipStream_t value
         _check(lib().jsdr_bpsk_pack_slots(self.h, _addr(slots_dev), C.c_void_p(stream)), "jsdr_bpsk_pack_slots")
 
+    # checkpoints (jsdr_hip.h "Checkpoints"): the state of a range of streams as a self-contained blob
+    def state_bytes(self, count):
+        n = C.c_size_t()
+        _check(lib().jsdr_bpsk_state_bytes(self.h, int(count), C.byref(n)), "jsdr_bpsk_state_bytes")
+        return n.value
+
+    def save(self, first=0, count=None):
+        """streams first .. first + count - 1 (None: to the last) -> bytes; the handle is not changed"""
+        count = self.nstreams - int(first) if count is None else int(count)
+        buf = np.empty(max(self.state_bytes(count), 1), np.uint8)
+        n = C.c_size_t()
+        _check(lib().jsdr_bpsk_save(self.h, int(first), count, _addr(buf), C.c_size_t(buf.size), C.byref(n)), "jsdr_bpsk_save")
+        return buf[:n.value].tobytes()
+
+    def state_kernel_ms(self):
+        """(device ms of the last save's k_state_pack, of the last restore's k_state_unpack); -1.0: none yet"""
+        a, b = C.c_double(), C.c_double()
+        _check(lib().jsdr_bpsk_state_kernel_ms(self.h, C.byref(a), C.byref(b)), "jsdr_bpsk_state_kernel_ms")
+        return a.value, b.value
+
+    def restore(self, blob, dst_first=0):
+        """all of the blob's streams into streams dst_first ..; a handle that has taken no sample and no blob adopts its shared block"""
+        buf = np.frombuffer(bytes(blob), np.uint8)
+        _check(lib().jsdr_bpsk_restore(self.h, int(dst_first), _addr(buf) if buf.size else None, C.c_size_t(buf.size)), "jsdr_bpsk_restore")
+
     def __del__(self):
         try:
             if getattr(self, "borrowed", False):
@@ -643,6 +668,21 @@ class BpskTuned(Bpsk):
         t = C.c_double()
         _check(lib().jsdr_bpsk_get_stream_tuning(self.h, int(stream), C.byref(t)), "jsdr_bpsk_get_stream_tuning")
         return t.value
+
+
+class BpskBlobInfo(C.Structure):
+    _fields_ = [("version", C.c_int32), ("kind", C.c_int32), ("rate", C.c_int32), ("nsamples_per_frame", C.c_int32),
+                ("nstreams", C.c_int32), ("do_fft", C.c_int32), ("do_up", C.c_int32), ("seam", C.c_int32),
+                ("record_bytes", C.c_int32), ("header_bytes", C.c_int32), ("n_in", C.c_int64), ("n_ds", C.c_int64),
+                ("tuning_hz", C.c_double)]
+
+
+def blob_info(blob):
+    """what a checkpoint blob says of itself (no device, no handle): the fields of jsdr_bpsk_blob_info_t as a dict"""
+    buf = np.frombuffer(bytes(blob), np.uint8)
+    info = BpskBlobInfo()
+    _check(lib().jsdr_bpsk_blob_info(_addr(buf) if buf.size else None, C.c_size_t(buf.size), C.byref(info)), "jsdr_bpsk_blob_info")
+    return {name: getattr(info, name) for name, _ in BpskBlobInfo._fields_}
 
 
 def tuner_walk_host(tu0, inc, n):
