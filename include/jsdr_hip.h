@@ -403,7 +403,10 @@ int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels);
 int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz);
 int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up);
 int jsdr_bpsk_get_channel_control(jsdr_bpsk *h, int channel, double *tuning_hz, int *do_fft, int *do_up);
-/* receive(float[]) / raw form for stream 0 of a 1-stream handle (:357-364) */
+/* receive(float[]) / raw form for stream 0 of a 1-stream handle (:357-364).
+ * Non-finite input (NaN, +-Infinity) and huge floats are taken as Java takes them: a comparison with a NaN is false, the filters
+ * and IIRs carry it.  One NaN therefore freezes the peak tracker (dmNewPeak, :586-592) for the life of the stream, as in the
+ * reference; bits go on being sliced at the frozen position. */
 int jsdr_bpsk_receive_f32(jsdr_bpsk *h, const float *iq_host);
 int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc);
 /* batched: raw_dev[s*stream_stride + 2*t .. +1] = I,Q of sample t of stream s; nsamples must be a
@@ -420,7 +423,10 @@ int jsdr_bpsk_batch_i16(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stream_str
  *   (the both-band transform is an int16 kernel); jsdr_bpsk_acq_last_launch reports what ran.
  *   Calls of the two forms may alternate on one handle: float after int16 converts the 26-sample input history (per input on
  *   a channel handle), int16 after floats that are (float)s/32767f values converts it back, int16 after any other float is
- *   refused with the handle unchanged.
+ *   refused with the handle unchanged (a NaN or an Infinity among the last 26 floats is such a float).
+ *   Non-finite input (NaN, +-Infinity) and huge floats are taken as Java takes them: a comparison with a NaN is false, the
+ *   filters and IIRs carry it.  One NaN therefore freezes the peak tracker (dmNewPeak, :586-592) of ITS stream for the life of
+ *   that stream, as in the reference, while its bits go on being sliced at the frozen position; other streams are untouched.
  *   jsdr_bpsk_front_kernel: "k_fm_f32", the fused float kernel, where an int16 call would take "k_fm" (a standard decimation, a
  *   periodic tuner schedule or none, no call that straddles a retune); jsdr_bpsk_set_cu_share / _last_launch and the k_fm and
  *   k_fm_prep profile slots apply to it.  JSDR_FM=0 (JSDR_KNOBS=1): always the three-kernel path.

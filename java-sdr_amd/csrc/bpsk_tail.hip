@@ -315,10 +315,13 @@ __global__ __launch_bounds__(64) void k_tail(TailArgs a)
         if (lane < nper) {
             const long long g7 = 8 * (MB + lane) + 7;
             if (g7 >= g_first && g7 < g_end) {
-                double bv = eT[0][lane], sv = -1.0e300;
-                np = 0;
+                // eMax starts at -1.0e10F and only a slot ABOVE it takes dmNewPeak (:586-592): a NaN slot is passed over, and with
+                // all eight NaN no slot is taken -- np = -2, dmNewPeak keeps its value.  (Energies are never below 0: on finite
+                // input slot 0 always takes the first step, and the runner-up sv is a real energy from slot 1 on.)
+                double bv = (double)-1.0e10F, sv = -1.0e300;
+                np = -2;
 #pragma unroll
-                for (int c = 1; c < 8; c++) {
+                for (int c = 0; c < 8; c++) {
                     double ov = eT[c][lane];
                     if (ov > bv) {  // strict: the first maximum wins
                         sv = bv;
@@ -332,6 +335,19 @@ __global__ __launch_bounds__(64) void k_tail(TailArgs a)
                     // (m_en == 0: nothing but zeros has gone through the fast kernels, both variants hold the same numbers)
                     if (!(bv - sv > m_en) && m_en > 0.0) uncert = 1;  // the order of the two largest is not certain
                 }
+            }
+        }
+        // A period that took no slot keeps the dmNewPeak it entered with: the peak of the nearest measured period below it that took
+        // one, or the carried newPeak where there is none.  One ballot finds whether any lane has such a period (none on finite
+        // input); a second one, taken only then, gives every lane the lanes that did take a slot, whatever the pattern.  From here
+        // on np is what dmNewPeak holds after the period, as everything below reads it.
+        {
+            const unsigned long long kept = __ballot(np == -2);
+            if (kept) {
+                const unsigned long long below = __ballot(np >= 0) & ((1ull << lane) - 1ull);
+                const int src = below ? 63 - __clzll((long long)below) : 0;
+                const int from = __shfl(np, src, 64);
+                if (np == -2) np = below ? from : newPeak;
             }
         }
         T8_CLK(2);  // argmax
@@ -697,8 +713,11 @@ __global__ __launch_bounds__(64 * WPB) void k_tail8(TailArgs a)
             const int p = 8 * i + c;
             const double2 *row = reinterpret_cast<const double2 *>(&EoL[p * ROW + s8 * 10]);
             const double2 q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
-            double bv = q0.x;
-            int np = 0;
+            // eMax starts at -1.0e10F and only a slot ABOVE it takes dmNewPeak (:586): a NaN slot is passed over, and with all
+            // eight NaN none is taken -- np stays 8, which the machine below already reads as "dmNewPeak keeps its value"
+            double bv = (double)-1.0e10F;
+            int np = 8;
+            if (q0.x > bv) { bv = q0.x; np = 0; }
             if (q0.y > bv) { bv = q0.y; np = 1; }  // strict: the first maximum wins
             if (q1.x > bv) { bv = q1.x; np = 2; }
             if (q1.y > bv) { bv = q1.y; np = 3; }
@@ -709,7 +728,7 @@ __global__ __launch_bounds__(64 * WPB) void k_tail8(TailArgs a)
             const bool meas = rel0 + 8 * p + 7 < nds;
             np = meas ? np : 8;
             NPL[s8][p] = (unsigned char)np;
-            fail = fail || (meas && np != v);
+            fail = fail || (np < 8 && np != v);  // (a period that took no slot leaves a locked stream locked: newPeak == v stays)
         }
         const bool general = __ballot(fail) != 0ull;
         JSDR_WAVE_SYNC();
