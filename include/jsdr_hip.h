@@ -40,6 +40,10 @@ int jsdr_get_device(int *device);            /* the calling thread's current dev
 int jsdr_device_name(char *buf, int cap);     /* gcnArchName of the current device */
 int jsdr_malloc(void **dev, size_t bytes);
 int jsdr_free(void *dev);
+/* what the library's handles and calls hold at the moment, process-wide: device buffers and their bytes, pinned host buffers,
+ * streams + events.  The caller's own jsdr_malloc / jsdr_stream_create are not counted; any pointer may be null.  Back at its
+ * earlier value once every handle created since has been destroyed. */
+int jsdr_live_resources(int64_t *device_buffers, int64_t *device_bytes, int64_t *pinned_buffers, int64_t *streams_and_events);
 int jsdr_memset(void *dev, int value, size_t bytes);
 int jsdr_memcpy_h2d(void *dev, const void *host, size_t bytes);
 int jsdr_memcpy_d2h(void *host, const void *dev, size_t bytes);

@@ -122,6 +122,13 @@ class DeviceBuffer:
             pass
 
 
+def live_resources():
+    """(device buffers, device bytes, pinned buffers, streams + events) the library's handles and calls hold at the moment"""
+    v = [C.c_int64(0) for _ in range(4)]
+    _check(lib().jsdr_live_resources(*[C.byref(x) for x in v]), "jsdr_live_resources")
+    return tuple(x.value for x in v)
+
+
 class Stream:
     """a non-blocking HIP stream (pass `.ptr` as the `stream` argument of the batch calls)"""
 

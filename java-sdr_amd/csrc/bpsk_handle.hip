@@ -22,6 +22,7 @@
 #include <math.h>
 #include <cmath>
 #include <atomic>
+#include <memory>
 #include <thread>
 #include <stddef.h>
 #include <stdlib.h>
@@ -127,9 +128,9 @@ struct jsdr_bpsk {
     std::thread worker;
     bool prefetch_on = true;       // JSDR_SCHED_PREFETCH=0: always on the calling thread
     long long sched_sync = 0, sched_prefetched = 0;  // schedules computed on the calling thread / taken from the worker
-    hipStream_t tail_stream = nullptr;   // non-blocking side stream for the latency-bound 9600 Hz tail + FEC
-    hipEvent_t ev_matched = nullptr;     // caller stream -> tail stream: (fi,fq) of this call are complete
-    hipEvent_t ev_tail_done[2] = {nullptr, nullptr};  // tail stream -> caller stream: y[i] may be overwritten
+    Stream tail_stream;                  // non-blocking side stream for the latency-bound 9600 Hz tail + FEC
+    Event ev_matched;                    // caller stream -> tail stream: (fi,fq) of this call are complete
+    Event ev_tail_done[2];               // tail stream -> caller stream: y[i] may be overwritten
     bool tail_pending[2] = {false, false};
     // results of the last receive_*() of a 1-stream handle, double-buffered for a reader on another thread (the Swing
     // EDT paints while the audio thread receives): the writer fills the idle copy, then publishes it
@@ -137,7 +138,7 @@ struct jsdr_bpsk {
     std::atomic<unsigned> snap_seq[2];   // odd while that copy is being written
     std::atomic<int> snap_cur{-1};       // -1: nothing received yet
     long long snap_count = 0;
-    hipEvent_t ev_pack_done = nullptr;   // pack stream -> tail stream: the result arrays of the previous call have been read
+    Event ev_pack_done;                  // pack stream -> tail stream: the result arrays of the previous call have been read
     bool pack_pending = false;
     bool overlap = true;
     long long dm_stride = 0, y_stride = 0;
@@ -156,7 +157,7 @@ struct jsdr_bpsk {
     // the schedule's tables when they change, the packed results out).  A copy from / to pageable memory is staged by the
     // runtime and costs a multiple of the transfer; the arena is reused every call, which is safe because receive()
     // synchronises before it returns.  Batch calls (asynchronous, caller-owned streams) keep the pageable path.
-    unsigned char *pin = nullptr;
+    PinnedStage pin;               // (the SnapPack slot sits behind pin_bytes)
     size_t pin_bytes = 0, pin_off = 0;
     bool pin_call = false;
     bool vco_cs_in_blob = false;  // FFT-acquire mode: the current schedule's VCO factors sit behind the frame in stage_raw
@@ -185,7 +186,10 @@ struct jsdr_bpsk {
     int acq_chunk = 0;
     // round 6, fast variant: the streams jsdr_bpsk_recover_uncertified() has replayed live on in an EXACT shadow handle (lock-step
     // with this one from then on); their getters and their packed slots come from it
-    jsdr_bpsk *shadow = nullptr;
+    struct Destroy {
+        void operator()(jsdr_bpsk *h) const { (void)jsdr_bpsk_destroy(h); }
+    };
+    std::unique_ptr<jsdr_bpsk, Destroy> shadow;
     std::vector<int> shadow_ids;   // ascending stream ids, index = the shadow's stream
     std::vector<int> shadow_map;   // [nstreams] index into the shadow, or -1
     DevBuf<int16_t> shadow_in;     // [U][2 max_batch] the shadow's rows of a call's input
@@ -200,13 +204,13 @@ struct jsdr_bpsk {
     bool prof_on = false;
     struct ProfRec {
         int kernel;
-        hipEvent_t a, b;
+        Event a, b;
     };
     std::vector<ProfRec> prof_recs;
-    std::vector<hipEvent_t> prof_pool;
+    std::vector<Event> prof_pool;
     // channel handle (jsdr_bpsk_create_channels): nch > 0 channels per input, stream = input * nch + channel
     int nch = 0, nin = 0;
-    BpskChan *chan = nullptr;
+    std::vector<BpskChan> chan;
     VcoSchedule vco;                 // the VCO schedule of the last call, shared by every channel and input
     // jsdr_bpsk_create_mode_channels: every channel in the tune mode or in FFT-acquire, fixed at creation.  nfftch of them run
     // FFT-acquire (bpsk_acq_chan.hip); fft_state is then CHANNEL-major, [nch][nin]
@@ -233,7 +237,7 @@ struct jsdr_bpsk {
     DevBuf<unsigned char> state_img;
     bool restored = false;                   // a blob has been restored: the handle is no longer free to adopt a shared block
     std::vector<unsigned char> trace_void;   // [S] 1: restored since the last call -- the stream's last call is an empty one
-    hipEvent_t ev_state[2] = {nullptr, nullptr};  // around the last k_state_pack / k_state_unpack launch (created at the first use)
+    Event ev_state[2];                       // around the last k_state_pack / k_state_unpack launch (created at the first use)
     float state_pack_ms = -1.f, state_unpack_ms = -1.f;  // jsdr_bpsk_state_kernel_ms; -1: none yet
 };
 
@@ -253,21 +257,21 @@ static const char *const kProfNames[PK_COUNT] = {"k_front", "k_hist_in", "k_matc
                                                  "k_sync_fin", "k_fec_bpsk", "k_fm", "k_sync_t", "k_fm_prep",
                                                  "k_acq_fwd", "k_acq_scan", "k_acq_inv", "k_acq_edges", "k_acqc_fwd", "k_tuner_walk"};
 
-static hipEvent_t prof_event(jsdr_bpsk *h)
+static Event prof_event(jsdr_bpsk *h)
 {
-    if (!h->prof_pool.empty()) {
-        hipEvent_t e = h->prof_pool.back();
+    Event e;
+    if (h->prof_pool.empty()) {
+        (void)e.create();  // (none: the scope records nothing)
+    } else {
+        e = std::move(h->prof_pool.back());
         h->prof_pool.pop_back();
-        return e;
     }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
     return e;
 }
 struct ProfScope {
     jsdr_bpsk *h;
     hipStream_t st;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     int k;
     ProfScope(jsdr_bpsk *h_, int k_, hipStream_t st_) : h(h_), st(st_), k(k_)
     {
@@ -281,7 +285,7 @@ struct ProfScope {
     {
         if (h->prof_on && a && b) {
             (void)hipEventRecord(b, st);
-            h->prof_recs.push_back({k, a, b});
+            h->prof_recs.push_back({k, std::move(a), std::move(b)});
         }
     }
 };
@@ -289,7 +293,7 @@ struct ProfScope {
 // the three-phase front end's launches (bpsk_acq.hip) under the same timing scopes
 struct AcqProfCtx {
     jsdr_bpsk *h;
-    hipEvent_t a[5];  // (phase 4: the channel handle's both-band forward kernel)
+    Event a[5];  // (phase 4: the channel handle's both-band forward kernel)
 };
 static void acq_prof_mark(void *ctx, int phase, bool begin, hipStream_t st)
 {
@@ -299,9 +303,9 @@ static void acq_prof_mark(void *ctx, int phase, bool begin, hipStream_t st)
         c->a[phase] = prof_event(c->h);
         (void)hipEventRecord(c->a[phase], st);
     } else {
-        hipEvent_t b = prof_event(c->h);
+        Event b = prof_event(c->h);
         (void)hipEventRecord(b, st);
-        c->h->prof_recs.push_back({PK_ACQ_FWD + phase, c->a[phase], b});
+        c->h->prof_recs.push_back({PK_ACQ_FWD + phase, std::move(c->a[phase]), std::move(b)});
     }
 }
 
@@ -398,12 +402,12 @@ static int publish_snapshot(jsdr_bpsk *h);
 // host -> device copy of a call's input or tables: through the pinned arena inside receive_*(), pageable otherwise
 static int h2d_call(jsdr_bpsk *h, void *dst_dev, const void *src_host, size_t bytes, hipStream_t st)
 {
-    if (h->pin_call && h->pin) {
+    if (h->pin_call && h->pin.p) {
         const size_t off = (h->pin_off + 63) & ~(size_t)63;
         if (off + bytes <= h->pin_bytes) {
-            memcpy(h->pin + off, src_host, bytes);
+            memcpy(h->pin.p + off, src_host, bytes);
             h->pin_off = off + bytes;
-            JSDR_HIP_TRY(hipMemcpyAsync(dst_dev, h->pin + off, bytes, hipMemcpyHostToDevice, st));
+            JSDR_HIP_TRY(hipMemcpyAsync(dst_dev, h->pin.p + off, bytes, hipMemcpyHostToDevice, st));
             return JSDR_OK;
         }
     }
@@ -627,7 +631,7 @@ static void acq_launch_ctx(jsdr_bpsk *h, AcqLaunchCtx &c)
     c.plan.rad = h->fm_rad;
     c.plan.tw_off = h->fm_off;
     c.plan.wr_off = h->fm_off1;
-    c.pc = AcqProfCtx{h, {nullptr, nullptr, nullptr, nullptr, nullptr}};
+    c.pc.h = h;
     c.prof.ctx = &c.pc;
     c.prof.mark = acq_prof_mark;
 }
@@ -979,7 +983,7 @@ static int chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         }
     }
     if (h->rx_frame_bytes) {  // receive(): the frame waits at the pinned arena's head
-        JSDR_HIP_TRY(hipMemcpyAsync(h->stage_raw.p, h->pin, h->rx_frame_bytes, hipMemcpyHostToDevice, st));
+        JSDR_HIP_TRY(hipMemcpyAsync(h->stage_raw.p, h->pin.p, h->rx_frame_bytes, hipMemcpyHostToDevice, st));
         h->rx_frame_bytes = 0;
     }
     const int *raw = reinterpret_cast<const int *>(raw_dev);
@@ -1260,12 +1264,12 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         const size_t o2 = (o1 + (size_t)nds + 63) & ~(size_t)63;
         if (fm_ok && fresh && nds > 0 && o2 + tcs_bytes <= h->pin_bytes && o2 + tcs_bytes <= h->stage_raw.n * sizeof(int)) {
             unsigned char *dev = reinterpret_cast<unsigned char *>(h->stage_raw.p);
-            memcpy(h->pin + o1, h->cur.kvco.data(), (size_t)nds);
+            memcpy(h->pin.p + o1, h->cur.kvco.data(), (size_t)nds);
             sc.src[0] = dev + o1;
             sc.dst[0] = kvco_p;
             sc.bytes[0] = (int)nds;
             if (tcs_bytes) {
-                memcpy(h->pin + o2, h->cur.tcs.data(), tcs_bytes);
+                memcpy(h->pin.p + o2, h->cur.tcs.data(), tcs_bytes);
                 sc.src[1] = dev + o2;
                 sc.dst[1] = reinterpret_cast<unsigned char *>(tcs_p);
                 sc.bytes[1] = (int)tcs_bytes;
@@ -1280,7 +1284,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
             //  a cached schedule were overwritten by the next float frame that failed the short-grid check, and read as they were)
             const size_t ov = (sizeof(float) * 2 * (size_t)h->nsf + 63) & ~(size_t)63, vb = sizeof(double2) * (size_t)nds;
             if (ov + vb <= h->pin_bytes && ov + vb <= h->stage_raw.n * sizeof(int)) {
-                fill_vco_cs(h, reinterpret_cast<double2 *>(h->pin + ov), nds);
+                fill_vco_cs(h, reinterpret_cast<double2 *>(h->pin.p + ov), nds);
                 total = ov + vb;
                 h->pin_off = total;
                 h->vco_cs_in_blob = true;
@@ -1288,7 +1292,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
                 tables_sent = true;
             }
         }
-        JSDR_HIP_TRY(hipMemcpyAsync(h->stage_raw.p, h->pin, total, hipMemcpyHostToDevice, st));
+        JSDR_HIP_TRY(hipMemcpyAsync(h->stage_raw.p, h->pin.p, total, hipMemcpyHostToDevice, st));
         h->rx_frame_bytes = 0;
     }
     if (fresh && tables_sent) h->tables_on_device = true;
@@ -1567,13 +1571,6 @@ static int fft_mode_alloc(jsdr_bpsk *h, FftFront kind, bool seam)
     if (ok) ok = hipDeviceSynchronize() == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        st.release();
-        st2.release();
-        tw.release();
-        vcs.release();
-        ek.release();
-        dm2.release();
-        r0.release();
         set_error("jsdr_bpsk_set_mode: could not allocate the FFT-acquire buffers (%zu streams of %d-sample frames); the handle is unchanged",
                   S, n);
         return JSDR_ERR;
@@ -1599,6 +1596,55 @@ static int fft_mode_alloc(jsdr_bpsk *h, FftFront kind, bool seam)
         h->fft_ready = true;
     }
     return JSDR_OK;
+}
+
+// JSDR_FFT_PHASECLK=1: the front ends' per-phase cycle counts of the handle's last launch, printed at destroy
+static void bpsk_phase_clocks_report(const jsdr_bpsk *h)
+{
+    if (!h->phase_clk.p) return;
+    static const char *const names_p2[8] = {"load+scatter", "forward FFT", "|X|", "boxcar+argmax", "centre-bin rule",
+                                            "gather/zero", "inverse FFT", "scale+RxDownSample"};
+    static const char *const names_mx[8] = {"load", "forward FFT", "centre-bin rule", "gather/zero/place", "inverse FFT",
+                                            "RxDownSample", "|X|", "boxcar+argmax"};
+    const char *const *names = h->fft_mixed ? names_mx : names_p2;
+    long long c[16] = {0};
+    if (hipDeviceSynchronize() == hipSuccess &&
+        hipMemcpy(c, h->phase_clk.p, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess) {
+        if (h->acq_chunk > 0) {  // the three-phase front end ran: the last launch's workgroup 0 of k_acq_fwd / k_acq_inv
+            static const char *const nf[6] = {"convert+pass 1", "pass 2", "last pass: loads", "last pass+|X|+spec", "boxcar", "argmax+peak"};
+            static const char *const ni[5] = {"gather", "passes 1+2 fused", "last pass", "compact store", "edges+RxDownSample"};
+            long long tf = 0, ti = 0;
+            for (int k = 0; k < 6; k++) tf += c[k];
+            for (int k = 0; k < 5; k++) ti += c[8 + k];
+            for (int k = 0; k < 6; k++)
+                fprintf(stderr, "[jsdr] k_acq_fwd phase %-20s %12lld ticks  %5.1f %%\n", nf[k], c[k], tf ? 100.0 * (double)c[k] / (double)tf : 0.0);
+            for (int k = 0; k < 5; k++)
+                fprintf(stderr, "[jsdr] k_acq_inv phase %-20s %12lld ticks  %5.1f %%\n", ni[k], c[8 + k], ti ? 100.0 * (double)c[8 + k] / (double)ti : 0.0);
+            memset(c, 0, sizeof(c));
+            // every k_acq_fwd workgroup's first and last tick (100 MHz): how many ran from the start, how far apart they ended
+            std::vector<long long> w(2 * 4096);
+            if (hipMemcpy(w.data(), h->phase_clk.p + 16, sizeof(long long) * w.size(), hipMemcpyDeviceToHost) == hipSuccess) {
+                long long t0 = 0, e0 = 0, e1 = 0;
+                int n = 0, late = 0;
+                for (int i = 0; i < 4096; i++)
+                    if (w[2 * i + 1]) {
+                        if (!n || w[2 * i] < t0) t0 = w[2 * i];
+                        if (!n || w[2 * i + 1] < e0) e0 = w[2 * i + 1];
+                        if (!n || w[2 * i + 1] > e1) e1 = w[2 * i + 1];
+                        n++;
+                    }
+                for (int i = 0; i < 4096; i++)
+                    if (w[2 * i + 1] && w[2 * i] - t0 > (e1 - t0) / 10) late++;
+                fprintf(stderr, "[jsdr] k_acq_fwd %d workgroups: %d started late (> 10 %% into the launch); first end %.3f ms, last end %.3f ms after the first start\n",
+                        n, late, (double)(e0 - t0) / 1e5, (double)(e1 - t0) / 1e5);
+            }
+        }
+        long long tot = 0;
+        for (int k = 0; k < 8; k++) tot += c[k];
+        for (int k = 0; k < 8; k++)
+            fprintf(stderr, "[jsdr] k_front_fft phase %-20s %12lld ticks  %5.1f %%\n", names[k], c[k],
+                    tot ? 100.0 * (double)c[k] / (double)tot : 0.0);
+    }
 }
 
 extern "C" {
@@ -1695,13 +1741,8 @@ int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuni
         const size_t need = sizeof(float) * 2 * (size_t)nsamples_per_frame + ((size_t)h->max_batch + 26) + (size_t)h->max_ds +
                             (do_fft ? sizeof(double2) * (size_t)h->max_ds : 0) + sizeof(double2) * (256 + FM_TABLE_SLACK) + 8 * 64;
         const size_t arena = (need + 63) & ~(size_t)63;
-        void *pp = nullptr;
-        if (arena <= ((size_t)8 << 20) && hipHostMalloc(&pp, arena + sizeof(SnapPack), hipHostMallocDefault) == hipSuccess) {
-            h->pin = static_cast<unsigned char *>(pp);
-            h->pin_bytes = arena;
-        } else {
-            (void)hipGetLastError();  // no pinned memory: the pageable path serves
-        }
+        if (arena <= ((size_t)8 << 20) && h->pin.alloc(arena + sizeof(SnapPack))) h->pin_bytes = arena;
+        else (void)hipGetLastError();  // no pinned memory: the pageable path serves
     }
     if (!ok) {
         jsdr_bpsk_destroy(h);
@@ -1773,11 +1814,9 @@ int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuni
               h->bitlog[0].zero() == JSDR_OK && h->bitlog[1].zero() == JSDR_OK && h->decoded.zero() == JSDR_OK &&
               h->nbits.zero() == JSDR_OK && h->trig_count.zero() == JSDR_OK && h->fec_last.zero() == JSDR_OK && h->fec_done.zero() == JSDR_OK &&
               h->cnt_dec.zero() == JSDR_OK && h->y[0].zero() == JSDR_OK && h->y[1].zero() == JSDR_OK &&
-              hipStreamCreateWithFlags(&h->tail_stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_matched, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_tail_done[0], hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_tail_done[1], hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&h->ev_pack_done, hipEventDisableTiming) == hipSuccess;
+              h->tail_stream.create(hipStreamNonBlocking) == JSDR_OK && h->ev_matched.create(hipEventDisableTiming) == JSDR_OK &&
+              h->ev_tail_done[0].create(hipEventDisableTiming) == JSDR_OK && h->ev_tail_done[1].create(hipEventDisableTiming) == JSDR_OK &&
+              h->ev_pack_done.create(hipEventDisableTiming) == JSDR_OK;
     if (!up || hipDeviceSynchronize() != hipSuccess) {
         set_error("jsdr_bpsk_create: device initialisation failed");
         jsdr_bpsk_destroy(h);
@@ -1787,145 +1826,26 @@ int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuni
     return JSDR_OK;
 }
 
+// Nothing is freed or destroyed while work of the handle can still be in flight: the worker is joined and the device and the
+// side stream are waited for first; then the members give back what they hold.
 int jsdr_bpsk_destroy(jsdr_bpsk *h)
 {
     if (!h) return JSDR_OK;
     if (h->worker.joinable()) h->worker.join();
-    if (h->chan) {
-        (void)hipDeviceSynchronize();
-        for (int c = 0; c < h->nch; c++) h->chan[c].dev.release();
-        delete[] h->chan;
-        h->chan = nullptr;
-    }
-    h->sincos.release();
-    h->ktu.release();
-    h->kvco.release();
-    h->hist_in[0].release();
-    h->hist_in[1].release();
-    h->dm.release();
-    h->hist_bad.release();
-    h->amax.release();
-    h->fm_edges.release();
-    h->fm_edges_f32.release();
-    h->snap_dev.release();
-    h->dmh[0].release();
-    h->dmh[1].release();
-    h->tcs.release();
-    h->y[0].release();
-    h->y[1].release();
-    if (h->tail_stream) {
-        (void)hipStreamSynchronize(h->tail_stream);
-        (void)hipStreamDestroy(h->tail_stream);
-    }
-    if (h->ev_matched) (void)hipEventDestroy(h->ev_matched);
-    if (h->ev_pack_done) (void)hipEventDestroy(h->ev_pack_done);
-    for (int i = 0; i < 2; i++)
-        if (h->ev_tail_done[i]) (void)hipEventDestroy(h->ev_tail_done[i]);
-    h->tail.release();
-    h->bitlog[0].release();
-    h->bitlog[1].release();
-    h->nbits.release();
-    h->trig_count.release();
-    h->trig_bits.release();
-    h->fec_rc.release();
-    h->fec_last.release();
-    h->cnt_dec.release();
-    h->corr.release();
-    h->fec_data.release();
-    h->fec_scratch.release();
-    h->fec_vit.release();
-    h->fec_work.release();
-    h->fec_done.release();
-    if (h->pin) (void)hipHostFree(h->pin);
-    h->pin = nullptr;
-    h->decoded.release();
-    h->stage_raw.release();
-    h->fft_state.release();
-    h->fft_tw.release();
-    h->fft2x_ek.release();
-    h->fft2x_r0.release();
-    h->acq_scratch.release();
-    if (h->shadow) (void)jsdr_bpsk_destroy(h->shadow);
-    h->shadow = nullptr;
-    h->shadow_in.release();
-    h->shadow_slots.release();
-    h->vco_cs.release();
-    h->ktu9.release();
-    h->sincos9.release();
-    h->fft_state2.release();
-    h->dm2.release();
-    h->seam_q.release();
-    h->pst_tu.release();
-    h->pst_inc.release();
-    h->pst_ckpt.release();
-    h->pst_kh[0].release();
-    h->pst_kh[1].release();
-    h->pst_ids.release();
-    h->state_img.release();
-    for (int i = 0; i < 2; i++)
-        if (h->ev_state[i]) (void)hipEventDestroy(h->ev_state[i]);
+    (void)hipDeviceSynchronize();
+    if (h->tail_stream) (void)hipStreamSynchronize(h->tail_stream);
     bpsk_debug_clocks_report();
-    if (h->phase_clk.p) {
-        static const char *const names_p2[8] = {"load+scatter", "forward FFT", "|X|", "boxcar+argmax", "centre-bin rule",
-                                                "gather/zero", "inverse FFT", "scale+RxDownSample"};
-        static const char *const names_mx[8] = {"load", "forward FFT", "centre-bin rule", "gather/zero/place", "inverse FFT",
-                                                "RxDownSample", "|X|", "boxcar+argmax"};
-        const char *const *names = h->fft_mixed ? names_mx : names_p2;
-        long long c[16] = {0};
-        if (hipDeviceSynchronize() == hipSuccess &&
-            hipMemcpy(c, h->phase_clk.p, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess) {
-            if (h->acq_chunk > 0) {  // the three-phase front end ran: the last launch's workgroup 0 of k_acq_fwd / k_acq_inv
-                static const char *const nf[6] = {"convert+pass 1", "pass 2", "last pass: loads", "last pass+|X|+spec", "boxcar", "argmax+peak"};
-                static const char *const ni[5] = {"gather", "passes 1+2 fused", "last pass", "compact store", "edges+RxDownSample"};
-                long long tf = 0, ti = 0;
-                for (int k = 0; k < 6; k++) tf += c[k];
-                for (int k = 0; k < 5; k++) ti += c[8 + k];
-                for (int k = 0; k < 6; k++)
-                    fprintf(stderr, "[jsdr] k_acq_fwd phase %-20s %12lld ticks  %5.1f %%\n", nf[k], c[k], tf ? 100.0 * (double)c[k] / (double)tf : 0.0);
-                for (int k = 0; k < 5; k++)
-                    fprintf(stderr, "[jsdr] k_acq_inv phase %-20s %12lld ticks  %5.1f %%\n", ni[k], c[8 + k], ti ? 100.0 * (double)c[8 + k] / (double)ti : 0.0);
-                memset(c, 0, sizeof(c));
-                // every k_acq_fwd workgroup's first and last tick (100 MHz): how many ran from the start, how far apart they ended
-                std::vector<long long> w(2 * 4096);
-                if (hipMemcpy(w.data(), h->phase_clk.p + 16, sizeof(long long) * w.size(), hipMemcpyDeviceToHost) == hipSuccess) {
-                    long long t0 = 0, e0 = 0, e1 = 0;
-                    int n = 0, late = 0;
-                    for (int i = 0; i < 4096; i++)
-                        if (w[2 * i + 1]) {
-                            if (!n || w[2 * i] < t0) t0 = w[2 * i];
-                            if (!n || w[2 * i + 1] < e0) e0 = w[2 * i + 1];
-                            if (!n || w[2 * i + 1] > e1) e1 = w[2 * i + 1];
-                            n++;
-                        }
-                    for (int i = 0; i < 4096; i++)
-                        if (w[2 * i + 1] && w[2 * i] - t0 > (e1 - t0) / 10) late++;
-                    fprintf(stderr, "[jsdr] k_acq_fwd %d workgroups: %d started late (> 10 %% into the launch); first end %.3f ms, last end %.3f ms after the first start\n",
-                            n, late, (double)(e0 - t0) / 1e5, (double)(e1 - t0) / 1e5);
-                }
-            }
-            long long tot = 0;
-            for (int k = 0; k < 8; k++) tot += c[k];
-            for (int k = 0; k < 8; k++)
-                fprintf(stderr, "[jsdr] k_front_fft phase %-20s %12lld ticks  %5.1f %%\n", names[k], c[k],
-                        tot ? 100.0 * (double)c[k] / (double)tot : 0.0);
-        }
-        h->phase_clk.release();
-    }
-    h->ds_taps_dev.release();
-    for (auto &r : h->prof_recs) {
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    for (auto e : h->prof_pool) (void)hipEventDestroy(e);
+    bpsk_phase_clocks_report(h);
     delete h;
     return JSDR_OK;
 }
 
 // the shadow's rows of a call's input, gathered into its own stream-major buffer
-static int shadow_stage(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stride, int64_t nsamples, hipStream_t st)
+static int shadow_stage(const jsdr_bpsk *h, const std::vector<int> &ids, int16_t *in, const int16_t *raw_dev, int64_t stride,
+                        int64_t nsamples, hipStream_t st)
 {
-    for (size_t i = 0; i < h->shadow_ids.size(); i++)
-        JSDR_HIP_TRY(hipMemcpyAsync(h->shadow_in.p + i * (size_t)(2 * h->max_batch), raw_dev + (int64_t)h->shadow_ids[i] * stride,
+    for (size_t i = 0; i < ids.size(); i++)
+        JSDR_HIP_TRY(hipMemcpyAsync(in + i * (size_t)(2 * h->max_batch), raw_dev + (int64_t)ids[i] * stride,
                                     (size_t)nsamples * 4, hipMemcpyDeviceToDevice, st));
     return JSDR_OK;
 }
@@ -1936,8 +1856,8 @@ int jsdr_bpsk_batch_i16(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stream_str
     if (bpsk_run(h, raw_dev, nullptr, stream_stride_i16, nsamples, ic, qc, as_stream(stream)) != JSDR_OK) return JSDR_ERR;
     h->batch_calls++;
     if (h->shadow) {  // the recovered streams, in exact order, in lock-step
-        if (shadow_stage(h, raw_dev, stream_stride_i16, nsamples, as_stream(stream)) != JSDR_OK) return JSDR_ERR;
-        if (bpsk_run(h->shadow, h->shadow_in.p, nullptr, 2 * h->max_batch, nsamples, ic, qc, as_stream(stream)) != JSDR_OK) return JSDR_ERR;
+        if (shadow_stage(h, h->shadow_ids, h->shadow_in.p, raw_dev, stream_stride_i16, nsamples, as_stream(stream)) != JSDR_OK) return JSDR_ERR;
+        if (bpsk_run(h->shadow.get(), h->shadow_in.p, nullptr, 2 * h->max_batch, nsamples, ic, qc, as_stream(stream)) != JSDR_OK) return JSDR_ERR;
     }
     return JSDR_OK;
 }
@@ -1987,27 +1907,29 @@ int jsdr_bpsk_recover_uncertified(jsdr_bpsk *h, const int16_t *const *raw_dev_ca
             if (h->shadow_map.empty() || h->shadow_map[(size_t)s] < 0) fresh++;
         }
     if (fresh == 0) return JSDR_OK;  // nothing new to recover (the shadow, if any, is up to date)
-    jsdr_bpsk *sh = nullptr;
-    if (jsdr_bpsk_create(&sh, h->rate, h->nsf, (int)h->tuning, 0, h->do_up, (int)ids.size(), h->max_batch) != JSDR_OK) return JSDR_ERR;
-    if (h->shadow) (void)jsdr_bpsk_destroy(h->shadow);
-    h->shadow = nullptr;
-    h->shadow_ids = ids;
-    h->shadow_map.assign((size_t)h->nstreams, -1);
-    for (size_t i = 0; i < ids.size(); i++) h->shadow_map[(size_t)ids[i]] = (int)i;
+    // the new shadow is built and replayed in locals and takes the old one's place only once every call has replayed: a failure
+    // leaves the handle as it was, the old shadow still serving.  (The staging buffers are declared before the shadow: it goes
+    // first, and its destroy waits for the replay that reads them.)
+    DevBuf<int16_t> in;
+    DevBuf<unsigned char> slots;
+    jsdr_bpsk *made = nullptr;
+    if (jsdr_bpsk_create(&made, h->rate, h->nsf, (int)h->tuning, 0, h->do_up, (int)ids.size(), h->max_batch) != JSDR_OK) return JSDR_ERR;
+    decltype(h->shadow) sh(made);
+    std::vector<int> map((size_t)h->nstreams, -1);
+    for (size_t i = 0; i < ids.size(); i++) map[(size_t)ids[i]] = (int)i;
     int64_t sb = 0;
     (void)jsdr_bpsk_slot_info(h, &sb, nullptr, nullptr, nullptr, nullptr);
-    if (h->shadow_in.alloc(ids.size() * (size_t)(2 * h->max_batch)) != JSDR_OK || h->shadow_slots.alloc(ids.size() * (size_t)sb) != JSDR_OK) {
-        (void)jsdr_bpsk_destroy(sh);
-        h->shadow_ids.clear();
-        h->shadow_map.clear();
-        return JSDR_ERR;
-    }
-    h->shadow = sh;
+    if (in.alloc(ids.size() * (size_t)(2 * h->max_batch)) != JSDR_OK || slots.alloc(ids.size() * (size_t)sb) != JSDR_OK) return JSDR_ERR;
     for (int k = 0; k < ncalls; k++) {
-        if (shadow_stage(h, raw_dev_calls[k], stream_stride_i16, nsamples_calls[k], as_stream(stream)) != JSDR_OK ||
-            bpsk_run(sh, h->shadow_in.p, nullptr, 2 * h->max_batch, nsamples_calls[k], ic, qc, as_stream(stream)) != JSDR_OK)
+        if (shadow_stage(h, ids, in.p, raw_dev_calls[k], stream_stride_i16, nsamples_calls[k], as_stream(stream)) != JSDR_OK ||
+            bpsk_run(sh.get(), in.p, nullptr, 2 * h->max_batch, nsamples_calls[k], ic, qc, as_stream(stream)) != JSDR_OK)
             return JSDR_ERR;
     }
+    std::swap(h->shadow, sh);  // (the old shadow and its buffers go with the locals)
+    std::swap(h->shadow_in, in);
+    std::swap(h->shadow_slots, slots);
+    h->shadow_ids = ids;
+    h->shadow_map.swap(map);
     h->recovered_events++;
     if (recovered) *recovered = (int)ids.size();
     return JSDR_OK;
@@ -2053,8 +1975,8 @@ int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
     h->pin_off = 0;
     int rc = JSDR_OK;
     const size_t fb = sizeof(int16_t) * 2 * (size_t)h->nsf;
-    if (h->pin && fb <= h->pin_bytes) {  // the frame waits at the arena's head: bpsk_run sends it (with the tables, if new)
-        memcpy(h->pin, raw_host, fb);
+    if (h->pin.p && fb <= h->pin_bytes) {  // the frame waits at the arena's head: bpsk_run sends it (with the tables, if new)
+        memcpy(h->pin.p, raw_host, fb);
         h->pin_off = fb;
         h->rx_frame_bytes = fb;
     } else {
@@ -2106,9 +2028,9 @@ int jsdr_bpsk_receive_f32(jsdr_bpsk *h, const float *iq_host)
         const char *e = knob("JSDR_F32_AS_I16");  // JSDR_F32_AS_I16=0: float frames always take the float kernels (tests)
         return !e || atoi(e) != 0;
     }();
-    bool as_i16 = route && h->variant == 0 && h->pin && (h->n_in == 0 || !h->hist_is_float) && nfl * sizeof(int16_t) <= h->pin_bytes;
+    bool as_i16 = route && h->variant == 0 && h->pin.p && (h->n_in == 0 || !h->hist_is_float) && nfl * sizeof(int16_t) <= h->pin_bytes;
     if (as_i16) {
-        int16_t *q = reinterpret_cast<int16_t *>(h->pin);  // the arena's head: the frame's slot
+        int16_t *q = reinterpret_cast<int16_t *>(h->pin.p);  // the arena's head: the frame's slot
         unsigned bad = 0;
         for (size_t i = 0; i < nfl; i++) {
             const float f = iq_host[i];
@@ -2191,7 +2113,7 @@ static int publish_snapshot(jsdr_bpsk *h)
     }
     SnapPack pk_stack;
     // (the arena's last slot: reserved at create, never handed out by h2d_call)
-    SnapPack *pkp = h->pin ? reinterpret_cast<SnapPack *>(h->pin + h->pin_bytes) : &pk_stack;
+    SnapPack *pkp = h->pin.p ? reinterpret_cast<SnapPack *>(h->pin.p + h->pin_bytes) : &pk_stack;
     JSDR_HIP_TRY(hipMemcpyAsync(pkp, h->snap_dev.p, sizeof(SnapPack), hipMemcpyDeviceToHost, ts));
     if (sync_last(h) != JSDR_OK) return JSDR_ERR;
     JSDR_HIP_TRY(hipStreamSynchronize(ts));
@@ -2230,7 +2152,7 @@ static int sync_last(jsdr_bpsk *h)
 {
     JSDR_HIP_TRY(hipStreamSynchronize(h->last_stream));
     if (h->tail_stream) JSDR_HIP_TRY(hipStreamSynchronize(h->tail_stream));
-    if (h->shadow) return sync_last(h->shadow);
+    if (h->shadow) return sync_last(h->shadow.get());
     return JSDR_OK;
 }
 
@@ -2259,7 +2181,7 @@ int jsdr_bpsk_get_counters(jsdr_bpsk *h, int stream, int32_t out[JSDR_BPSK_NCOUN
 {
     JSDR_REQUIRE(h && out, "jsdr_bpsk_get_counters: null argument");
     JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_counters: stream %d out of range", stream);
-    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_counters(h->shadow, h->shadow_map[(size_t)stream], out);
+    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_counters(h->shadow.get(), h->shadow_map[(size_t)stream], out);
     if (sync_last(h) != JSDR_OK) return JSDR_ERR;
     TailState t;
     int last[2], cdec;
@@ -2281,7 +2203,7 @@ int jsdr_bpsk_get_bits(jsdr_bpsk *h, int stream, int8_t *bits_host, int cap, int
 {
     JSDR_REQUIRE(h && nbits, "jsdr_bpsk_get_bits: null argument");
     JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_bits: stream %d out of range", stream);
-    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_bits(h->shadow, h->shadow_map[(size_t)stream], bits_host, cap, nbits);
+    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_bits(h->shadow.get(), h->shadow_map[(size_t)stream], bits_host, cap, nbits);
     if (sync_last(h) != JSDR_OK || check_overflow(h, stream, "jsdr_bpsk_get_bits") != JSDR_OK) return JSDR_ERR;
     int nb = 0;
     JSDR_HIP_TRY(hipMemcpy(&nb, h->nbits.p + stream, sizeof(int), hipMemcpyDeviceToHost));
@@ -2297,7 +2219,7 @@ int jsdr_bpsk_get_fec_count(jsdr_bpsk *h, int stream, int *count)
 {
     JSDR_REQUIRE(h && count, "jsdr_bpsk_get_fec_count: null argument");
     JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_fec_count: stream %d out of range", stream);
-    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_fec_count(h->shadow, h->shadow_map[(size_t)stream], count);
+    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_fec_count(h->shadow.get(), h->shadow_map[(size_t)stream], count);
     if (sync_last(h) != JSDR_OK || check_overflow(h, stream, "jsdr_bpsk_get_fec_count") != JSDR_OK) return JSDR_ERR;
     JSDR_HIP_TRY(hipMemcpy(count, h->trig_count.p + stream, sizeof(int), hipMemcpyDeviceToHost));
     return JSDR_OK;
@@ -2307,7 +2229,7 @@ int jsdr_bpsk_get_fec(jsdr_bpsk *h, int stream, int idx, int32_t *rc, int32_t *b
 {
     JSDR_REQUIRE(h && rc && bit_index && out_host, "jsdr_bpsk_get_fec: null argument");
     JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_fec: stream %d out of range", stream);
-    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_fec(h->shadow, h->shadow_map[(size_t)stream], idx, rc, bit_index, out_host);
+    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_fec(h->shadow.get(), h->shadow_map[(size_t)stream], idx, rc, bit_index, out_host);
     int cnt = 0;
     if (jsdr_bpsk_get_fec_count(h, stream, &cnt) != JSDR_OK) return JSDR_ERR;
     JSDR_REQUIRE(idx >= 0 && idx < cnt, "jsdr_bpsk_get_fec: index %d outside the %d calls of the last batch", idx, cnt);
@@ -2323,7 +2245,7 @@ int jsdr_bpsk_get_decoded(jsdr_bpsk *h, int stream, uint8_t out_host[256])
 {
     JSDR_REQUIRE(h && out_host, "jsdr_bpsk_get_decoded: null argument");
     JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_decoded: stream %d out of range", stream);
-    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_decoded(h->shadow, h->shadow_map[(size_t)stream], out_host);
+    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_decoded(h->shadow.get(), h->shadow_map[(size_t)stream], out_host);
     if (sync_last(h) != JSDR_OK || check_overflow(h, stream, "jsdr_bpsk_get_decoded") != JSDR_OK) return JSDR_ERR;
     JSDR_HIP_TRY(hipMemcpy(out_host, h->decoded.p + (size_t)stream * 256, 256, hipMemcpyDeviceToHost));
     return JSDR_OK;
@@ -2333,7 +2255,7 @@ int jsdr_bpsk_get_trace(jsdr_bpsk *h, int stream, double *out_host, int64_t cap_
 {
     JSDR_REQUIRE(h && npairs, "jsdr_bpsk_get_trace: null argument");
     JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_trace: stream %d out of range", stream);
-    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_trace(h->shadow, h->shadow_map[(size_t)stream], out_host, cap_pairs, npairs);
+    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_trace(h->shadow.get(), h->shadow_map[(size_t)stream], out_host, cap_pairs, npairs);
     if (sync_last(h) != JSDR_OK) return JSDR_ERR;
     const long long have = (!h->trace_void.empty() && h->trace_void[(size_t)stream]) ? 0 : h->last_nds;  // (restored since: an empty call)
     *npairs = have;
@@ -2348,7 +2270,7 @@ int jsdr_bpsk_get_state(jsdr_bpsk *h, int stream, double out[18])
 {
     JSDR_REQUIRE(h && out, "jsdr_bpsk_get_state: null argument");
     JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_state: stream %d out of range", stream);
-    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_state(h->shadow, h->shadow_map[(size_t)stream], out);
+    if (JSDR_SHADOWED(h, stream)) return jsdr_bpsk_get_state(h->shadow.get(), h->shadow_map[(size_t)stream], out);
     if (sync_last(h) != JSDR_OK) return JSDR_ERR;
     TailState t;
     JSDR_HIP_TRY(hipMemcpy(&t, h->tail.p + stream, sizeof(t), hipMemcpyDeviceToHost));
@@ -2730,17 +2652,23 @@ int jsdr_bpsk_get_control(jsdr_bpsk *h, double *tuning_hz, int *do_fft, int *do_
     return JSDR_OK;
 }
 
+// what every creator of a channel handle asks of its channel arguments, before any device work
+static int chan_args_check(const char *who, int ninputs, int nchannels, const double *tuning_hz)
+{
+    JSDR_REQUIRE(nchannels >= 1 && nchannels <= CHAN_MAX, "%s: nchannels %d outside 1 .. %d", who, nchannels, (int)CHAN_MAX);
+    JSDR_REQUIRE(ninputs >= 1 && (long long)ninputs * nchannels <= 65535, "%s: %d inputs x %d channels", who, ninputs, nchannels);
+    JSDR_REQUIRE(tuning_hz, "%s: null tuning array", who);
+    for (int c = 0; c < nchannels; c++)
+        JSDR_REQUIRE(std::isfinite(tuning_hz[c]), "%s: tuning of channel %d (%g Hz) is not finite", who, c, tuning_hz[c]);
+    return JSDR_OK;
+}
+
 int jsdr_bpsk_create_channels(jsdr_bpsk **out, int rate, int nsamples_per_frame, int ninputs, int nchannels,
                               const double *tuning_hz, const int *do_up, int64_t max_batch_samples)
 {
     JSDR_REQUIRE(out, "jsdr_bpsk_create_channels: null handle pointer");
     *out = nullptr;
-    JSDR_REQUIRE(nchannels >= 1 && nchannels <= CHAN_MAX, "jsdr_bpsk_create_channels: nchannels %d outside 1 .. %d", nchannels, (int)CHAN_MAX);
-    JSDR_REQUIRE(ninputs >= 1 && (long long)ninputs * nchannels <= 65535, "jsdr_bpsk_create_channels: %d inputs x %d channels", ninputs,
-                 nchannels);
-    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_create_channels: null tuning array");
-    for (int c = 0; c < nchannels; c++)
-        JSDR_REQUIRE(std::isfinite(tuning_hz[c]), "jsdr_bpsk_create_channels: tuning of channel %d (%g Hz) is not finite", c, tuning_hz[c]);
+    if (chan_args_check("jsdr_bpsk_create_channels", ninputs, nchannels, tuning_hz) != JSDR_OK) return JSDR_ERR;
     if (max_batch_samples < nsamples_per_frame) max_batch_samples = nsamples_per_frame;
     JSDR_REQUIRE(max_batch_samples <= 0x3fffffffLL, "jsdr_bpsk_create_channels: max_batch_samples %lld above 2^30 - 1",
                  (long long)max_batch_samples);
@@ -2750,7 +2678,7 @@ int jsdr_bpsk_create_channels(jsdr_bpsk **out, int rate, int nsamples_per_frame,
     h->nch = nchannels;
     h->nin = ninputs;
     h->use_fm = false;
-    h->chan = new BpskChan[nchannels];
+    h->chan = std::vector<BpskChan>((size_t)nchannels);
     bool ok = sincos9_ensure(h) == JSDR_OK;
     for (int c = 0; c < nchannels && ok; c++) {
         BpskChan &cc = h->chan[c];
@@ -2777,12 +2705,7 @@ int jsdr_bpsk_create_mode_channels(jsdr_bpsk **out, int rate, int nsamples_per_f
     JSDR_REQUIRE(out, "jsdr_bpsk_create_mode_channels: null handle pointer");
     *out = nullptr;
     // every check before any device work
-    JSDR_REQUIRE(nchannels >= 1 && nchannels <= CHAN_MAX, "jsdr_bpsk_create_mode_channels: nchannels %d outside 1 .. %d", nchannels, (int)CHAN_MAX);
-    JSDR_REQUIRE(ninputs >= 1 && (long long)ninputs * nchannels <= 65535, "jsdr_bpsk_create_mode_channels: %d inputs x %d channels", ninputs,
-                 nchannels);
-    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_create_mode_channels: null tuning array");
-    for (int c = 0; c < nchannels; c++)
-        JSDR_REQUIRE(std::isfinite(tuning_hz[c]), "jsdr_bpsk_create_mode_channels: tuning of channel %d (%g Hz) is not finite", c, tuning_hz[c]);
+    if (chan_args_check("jsdr_bpsk_create_mode_channels", ninputs, nchannels, tuning_hz) != JSDR_OK) return JSDR_ERR;
     JSDR_REQUIRE(rate >= 1 && nsamples_per_frame > 0, "jsdr_bpsk_create_mode_channels: rate %d, frame of %d samples", rate, nsamples_per_frame);
     int nfft = 0;
     for (int c = 0; c < nchannels; c++) nfft += (do_fft && do_fft[c]) ? 1 : 0;
@@ -2815,12 +2738,7 @@ int jsdr_bpsk_create_live_channels(jsdr_bpsk **out, int rate, int nsamples_per_f
     JSDR_REQUIRE(out, "jsdr_bpsk_create_live_channels: null handle pointer");
     *out = nullptr;
     // every check before any device work
-    JSDR_REQUIRE(nchannels >= 1 && nchannels <= CHAN_MAX, "jsdr_bpsk_create_live_channels: nchannels %d outside 1 .. %d", nchannels, (int)CHAN_MAX);
-    JSDR_REQUIRE(ninputs >= 1 && (long long)ninputs * nchannels <= 65535, "jsdr_bpsk_create_live_channels: %d inputs x %d channels", ninputs,
-                 nchannels);
-    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_create_live_channels: null tuning array");
-    for (int c = 0; c < nchannels; c++)
-        JSDR_REQUIRE(std::isfinite(tuning_hz[c]), "jsdr_bpsk_create_live_channels: tuning of channel %d (%g Hz) is not finite", c, tuning_hz[c]);
+    if (chan_args_check("jsdr_bpsk_create_live_channels", ninputs, nchannels, tuning_hz) != JSDR_OK) return JSDR_ERR;
     JSDR_REQUIRE(rate >= 1 && nsamples_per_frame > 0, "jsdr_bpsk_create_live_channels: rate %d, frame of %d samples", rate, nsamples_per_frame);
     // any channel may come to acquire: the frame must be one FFT-acquire takes, whatever the initial modes
     const FftFront front = fft_front_kind(nsamples_per_frame, rate / 9600 > 0 ? rate / 9600 : 1, true);
@@ -3002,8 +2920,8 @@ int jsdr_bpsk_profile_read(jsdr_bpsk *h, double *ms_total, int *launches)
         JSDR_HIP_TRY(hipEventElapsedTime(&ms, r.a, r.b));
         ms_total[r.kernel] += (double)ms;
         launches[r.kernel] += 1;
-        h->prof_pool.push_back(r.a);
-        h->prof_pool.push_back(r.b);
+        h->prof_pool.push_back(std::move(r.a));
+        h->prof_pool.push_back(std::move(r.b));
     }
     h->prof_recs.clear();
     return JSDR_OK;
@@ -3048,7 +2966,7 @@ extern "C" int jsdr_bpsk_pack_slots(jsdr_bpsk *h, uint8_t *slots_dev, void *stre
     h->pack_pending = true;
     if (h->shadow) {
         // the recovered streams' slots are the exact shadow's (same slot layout: same max_batch), laid over the fast handle's
-        if (jsdr_bpsk_pack_slots(h->shadow, h->shadow_slots.p, stream) != JSDR_OK) return JSDR_ERR;
+        if (jsdr_bpsk_pack_slots(h->shadow.get(), h->shadow_slots.p, stream) != JSDR_OK) return JSDR_ERR;
         for (size_t i = 0; i < h->shadow_ids.size(); i++)
             JSDR_HIP_TRY(hipMemcpyAsync(slots_dev + (size_t)h->shadow_ids[i] * (size_t)slot_bytes, h->shadow_slots.p + i * (size_t)slot_bytes,
                                         (size_t)slot_bytes, hipMemcpyDeviceToDevice, as_stream(stream)));
@@ -3131,8 +3049,7 @@ static int ckpt_stage(jsdr_bpsk *h, int count)
     if (h->state_img.n >= need) return JSDR_OK;
     DevBuf<unsigned char> img;
     if (img.alloc(need) != JSDR_OK) return JSDR_ERR;
-    std::swap(h->state_img, img);
-    img.release();
+    h->state_img = std::move(img);  // (the smaller image goes)
     return JSDR_OK;
 }
 
@@ -3140,9 +3057,8 @@ static int ckpt_stage(jsdr_bpsk *h, int count)
 static bool ckpt_events(jsdr_bpsk *h)
 {
     for (int i = 0; i < 2; i++)
-        if (!h->ev_state[i] && hipEventCreate(&h->ev_state[i]) != hipSuccess) {
+        if (!h->ev_state[i] && h->ev_state[i].create() != JSDR_OK) {
             (void)hipGetLastError();
-            h->ev_state[i] = nullptr;
             return false;
         }
     return true;

@@ -5,7 +5,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include "../../include/jsdr_hip.h"
 
 namespace jsdr {
@@ -18,6 +21,7 @@ void set_error(const char *fmt, ...);
         if (_e != hipSuccess) {                                                                    \
             ::jsdr::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__,     \
                               __LINE__);                                                           \
+            (void)hipGetLastError(); /* reported: the next launch check must not find it again */  \
             return JSDR_ERR;                                                                       \
         }                                                                                          \
     } while (0)
@@ -57,17 +61,96 @@ static inline const char *knob(const char *name)
     return on ? getenv(name) : nullptr;
 }
 
-// RAII-less device buffer (handles own them and free in destroy)
+// ---- ownership ------------------------------------------------------------------------------------------------------
+// Device memory, pinned memory, streams and events are held by the move-only types below: a handle's members and a
+// function's locals give back what they hold when they go, on every way out.  NO object of these types may have static or
+// namespace-scope storage (there is none): its destructor would call into HIP while the process exits, after the runtime
+// has been torn down.
+//
+// What they hold at the moment, process-wide (jsdr_live_resources; what a caller got from jsdr_malloc or
+// jsdr_stream_create is the caller's and is not counted).
+inline std::atomic<int64_t> live_dev_bufs{0}, live_dev_bytes{0}, live_pinned{0}, live_objects{0};
+
+// A HIP object (stream, event) and the call that destroys it.  Converts to the bare handle, so it is passed to HIP as one.
+template <class H, hipError_t (*Destroy)(H)>
+struct Owned {
+    H h = H();
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    Owned(Owned &&o) noexcept : h(o.h) { o.h = H(); }
+    Owned &operator=(Owned &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            h = o.h;
+            o.h = H();
+        }
+        return *this;
+    }
+    ~Owned() { reset(); }
+    void adopt(H fresh)
+    {
+        reset();
+        h = fresh;
+        if (h) live_objects++;
+    }
+    void reset()
+    {
+        if (h) {
+            (void)Destroy(h);
+            live_objects--;
+        }
+        h = H();
+    }
+    operator H() const { return h; }
+};
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {
+    int create(unsigned flags)
+    {
+        hipStream_t s = nullptr;
+        JSDR_HIP_TRY(hipStreamCreateWithFlags(&s, flags));
+        adopt(s);
+        return JSDR_OK;
+    }
+};
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+    int create(unsigned flags = hipEventDefault)  // (hipEventCreate is hipEventCreateWithFlags with hipEventDefault)
+    {
+        hipEvent_t e = nullptr;
+        JSDR_HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        adopt(e);
+        return JSDR_OK;
+    }
+};
+
+// A device buffer and its owner: released when it goes, or early with release().
 template <class T>
 struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p, n = o.n;
+            o.p = nullptr, o.n = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int alloc(size_t count)
     {
         release();
         if (count == 0) return JSDR_OK;
         JSDR_HIP_TRY(hipMalloc((void **)&p, count * sizeof(T)));
         n = count;
+        live_dev_bufs++;
+        live_dev_bytes += (int64_t)(n * sizeof(T));
         return JSDR_OK;
     }
     int zero(hipStream_t s = 0)
@@ -77,7 +160,11 @@ struct DevBuf {
     }
     void release()
     {
-        if (p) (void)hipFree(p);
+        if (p) {
+            (void)hipFree(p);
+            live_dev_bufs--;
+            live_dev_bytes -= (int64_t)(n * sizeof(T));
+        }
         p = nullptr;
         n = 0;
     }
@@ -87,28 +174,54 @@ struct DevBuf {
 // and costs a multiple of the transfer (BPSK receive(): 115 -> 71 us per frame with every copy through pinned memory).
 // The caller's buffer is memcpy'd in / out on the host; the device copies are asynchronous on `st` and the receive
 // synchronises before it returns, so the buffer is free again at the next call.  No pinned memory: falls back to
-// the blocking pageable copies.
-struct PinnedStage {
-    unsigned char *p = nullptr;
+// the blocking pageable copies.  Owns what it holds, like DevBuf.
+template <class T>
+struct Pinned {
+    T *p = nullptr;
     size_t bytes = 0;
-    void alloc(size_t n)
+    Pinned() = default;
+    Pinned(const Pinned &) = delete;
+    Pinned &operator=(const Pinned &) = delete;
+    Pinned(Pinned &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+    Pinned &operator=(Pinned &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            p = o.p, bytes = o.bytes;
+            o.p = nullptr, o.bytes = 0;
+        }
+        return *this;
+    }
+    ~Pinned() { release(); }
+    bool alloc(size_t n)
     {
         release();
         void *q = nullptr;
         if (n && hipHostMalloc(&q, n, hipHostMallocDefault) == hipSuccess) {
-            p = static_cast<unsigned char *>(q);
+            p = static_cast<T *>(q);
             bytes = n;
+            live_pinned++;
         } else {
             (void)hipGetLastError();
         }
+        return p != nullptr;
     }
     void release()
     {
-        if (p) (void)hipHostFree(p);
+        if (p) {
+            (void)hipHostFree(p);
+            live_pinned--;
+        }
         p = nullptr;
         bytes = 0;
     }
 };
+using PinnedStage = Pinned<unsigned char>;
+
+static_assert(!std::is_copy_constructible<DevBuf<int>>::value && std::is_nothrow_move_constructible<DevBuf<int>>::value, "DevBuf is move-only");
+static_assert(!std::is_copy_constructible<Stream>::value && std::is_nothrow_move_constructible<Stream>::value, "Stream is move-only");
+static_assert(!std::is_copy_constructible<Event>::value && std::is_nothrow_move_constructible<Event>::value, "Event is move-only");
+static_assert(!std::is_copy_constructible<PinnedStage>::value && std::is_nothrow_move_constructible<PinnedStage>::value, "PinnedStage is move-only");
 
 // Once a receive() has queued an asynchronous copy from / to its pinned stage, EVERY way out waits for the device: the next
 // call memcpy's into the same stage.  Disarmed on the path that has synchronised itself.

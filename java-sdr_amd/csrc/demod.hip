@@ -512,9 +512,9 @@ struct jsdr_demod {
     // the other one (no bubble between calls for the host's phase recurrence and its upload)
     DevBuf<float2> nco[2];
     DevBuf<float> car_dev[2];
-    float *car_pinned[2] = {nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_table[2] = {nullptr, nullptr}, ev_used[2] = {nullptr, nullptr};
+    Pinned<float> car_pinned[2];
+    Stream copy_stream;
+    Event ev_table[2], ev_used[2];
     bool used[2] = {false, false};
     unsigned calls = 0;
     DevBuf<float> d, favg, stats;
@@ -526,10 +526,10 @@ struct jsdr_demod {
     bool prof_on = false;
     struct Rec {
         int k;
-        hipEvent_t a, b;
+        Event a, b;
     };
     std::vector<Rec> recs;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     // channel handles (jsdr_demod_create_channels): nstreams = nin * nch, channel c of input i is stream i * nch + c; every
     // channel has its own controls and carrier phase (the handle-wide fields above are unused)
     bool chan = false;
@@ -543,7 +543,7 @@ struct jsdr_demod {
     std::vector<Chan> ch;
     long long nco_pitch = 0;   // entries between two carrier tables of a set
     DevBuf<float> dch;         // [dslots * nin][L] float rows (AM channels; every channel of a frame above 5 tiles)
-    hipEvent_t ev_done = nullptr, ev_clear = nullptr;  // end of the last call; a channel ring cleared after it
+    Event ev_done, ev_clear;   // end of the last call; a channel ring cleared after it
     bool done_any = false, clear_pending = false;
 };
 
@@ -554,17 +554,17 @@ static const char *const kDemodKernels[DK_COUNT] = {"k_demod_nco", "k_demod_fron
 struct DemodProf {
     jsdr_demod *h;
     hipStream_t st;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     int k;
-    static hipEvent_t get(jsdr_demod *h)
+    static Event get(jsdr_demod *h)
     {
-        if (!h->pool.empty()) {
-            hipEvent_t e = h->pool.back();
+        Event e;
+        if (h->pool.empty()) {
+            (void)e.create();  // (none: the scope records nothing)
+        } else {
+            e = std::move(h->pool.back());
             h->pool.pop_back();
-            return e;
         }
-        hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
         return e;
     }
     DemodProf(jsdr_demod *h_, int k_, hipStream_t st_) : h(h_), st(st_), k(k_)
@@ -579,7 +579,7 @@ struct DemodProf {
     {
         if (h->prof_on && a && b) {
             (void)hipEventRecord(b, st);
-            h->recs.push_back({k, a, b});
+            h->recs.push_back({k, std::move(a), std::move(b)});
         }
     }
 };
@@ -653,7 +653,7 @@ static int demod_run(jsdr_demod *h, const int16_t *raw_dev, const float *rawf_de
     if (h->dodwn) {
         // :427-429 in float, exactly as the reference steps it
         if (h->used[set]) JSDR_HIP_TRY(hipEventSynchronize(h->ev_used[set]));  // the call before last has let go of this set
-        float *tab = h->car_pinned[set];
+        float *tab = h->car_pinned[set].p;
         float car = h->car;
         const float phi = h->phi, two_pi = (float)(2 * 3.14159265358979323846);
         // a serial float recurrence, on the host; kept as a (well predicted) branch so that the dependent chain per
@@ -795,7 +795,7 @@ static int demod_chan_run(jsdr_demod *h, const int16_t *raw_dev, const float *ra
         float endcar[DCHAN_MAX];
         // :427-429 in float, exactly as demod_run steps it; one host thread per distinct table
         auto build = [&](int r) {
-            float *tab = h->car_pinned[set] + (size_t)r * h->nco_pitch;
+            float *tab = h->car_pinned[set].p + (size_t)r * h->nco_pitch;
             float car, phi;
             memcpy(&car, &key[r][0], 4);
             memcpy(&phi, &key[r][1], 4);
@@ -820,7 +820,7 @@ static int demod_chan_run(jsdr_demod *h, const int16_t *raw_dev, const float *ra
         for (int c = 0; c < K; c++)
             if (h->ch[c].dodwn) h->ch[c].car = endcar[a.c[c].nco_row];
         const long long cnt = (long long)(rows - 1) * h->nco_pitch + L;
-        JSDR_HIP_TRY(hipMemcpyAsync(h->car_dev[set].p, h->car_pinned[set], sizeof(float) * (size_t)cnt, hipMemcpyHostToDevice,
+        JSDR_HIP_TRY(hipMemcpyAsync(h->car_dev[set].p, h->car_pinned[set].p, sizeof(float) * (size_t)cnt, hipMemcpyHostToDevice,
                                     h->copy_stream));
         {
             DemodProf ps(h, DK_NCO, h->copy_stream);
@@ -950,10 +950,9 @@ int jsdr_demod_create(jsdr_demod **out, int rate, int nsamples_per_frame, int ns
              h->lilq[k].zero() == JSDR_OK;
     for (int k = 0; k < 2; k++)
         ok = ok && h->nco[k].alloc(L + 8) == JSDR_OK && h->nco[k].zero() == JSDR_OK && h->car_dev[k].alloc(L) == JSDR_OK &&
-             hipHostMalloc(reinterpret_cast<void **>(&h->car_pinned[k]), sizeof(float) * L, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&h->ev_table[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&h->ev_used[k], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) == hipSuccess;
+             h->car_pinned[k].alloc(sizeof(float) * L) && h->ev_table[k].create(hipEventDisableTiming) == JSDR_OK &&
+             h->ev_used[k].create(hipEventDisableTiming) == JSDR_OK;
+    ok = ok && h->copy_stream.create(hipStreamNonBlocking) == JSDR_OK;
     ok = ok && h->d.alloc(S * L) == JSDR_OK &&
          h->favg.alloc(nf) == JSDR_OK && h->stats.alloc(2 * nf) == JSDR_OK && h->fmax.alloc(nf) == JSDR_OK &&
          h->stage_in.alloc(2 * (size_t)h->n) == JSDR_OK && h->stage_out.alloc((size_t)h->n) == JSDR_OK &&
@@ -970,33 +969,6 @@ int jsdr_demod_destroy(jsdr_demod *h)
 {
     if (!h) return JSDR_OK;
     (void)hipDeviceSynchronize();
-    h->pin.release();
-    for (int k = 0; k < 2; k++) {
-        h->hist[k].release();
-        h->lilq[k].release();
-    }
-    for (int k = 0; k < 2; k++) {
-        h->nco[k].release();
-        h->car_dev[k].release();
-        if (h->car_pinned[k]) (void)hipHostFree(h->car_pinned[k]);
-        if (h->ev_table[k]) (void)hipEventDestroy(h->ev_table[k]);
-        if (h->ev_used[k]) (void)hipEventDestroy(h->ev_used[k]);
-    }
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    h->d.release();
-    h->favg.release();
-    h->stats.release();
-    h->fmax.release();
-    h->stage_in.release();
-    h->stage_out.release();
-    h->dch.release();
-    if (h->ev_done) (void)hipEventDestroy(h->ev_done);
-    if (h->ev_clear) (void)hipEventDestroy(h->ev_clear);
-    for (auto &r : h->recs) {
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
-    }
-    for (auto e : h->pool) (void)hipEventDestroy(e);
     delete h;
     return JSDR_OK;
 }
@@ -1022,8 +994,8 @@ int jsdr_demod_profile_read(jsdr_demod *h, double *ms_total, int *launches)
             ms_total[r.k] += ms;
             launches[r.k]++;
         }
-        h->pool.push_back(r.a);
-        h->pool.push_back(r.b);
+        h->pool.push_back(std::move(r.a));
+        h->pool.push_back(std::move(r.b));
     }
     h->recs.clear();
     return JSDR_OK;
@@ -1187,12 +1159,10 @@ int jsdr_demod_create_channels(jsdr_demod **out, int rate, int nsamples_per_fram
              h->hist[k].zero() == JSDR_OK && h->lilq[k].zero() == JSDR_OK;
     for (int k = 0; k < 2; k++)
         ok = ok && h->nco[k].alloc(tab) == JSDR_OK && h->nco[k].zero() == JSDR_OK && h->car_dev[k].alloc(tab) == JSDR_OK &&
-             hipHostMalloc(reinterpret_cast<void **>(&h->car_pinned[k]), sizeof(float) * tab, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&h->ev_table[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&h->ev_used[k], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking) == hipSuccess &&
-         hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) == hipSuccess &&
-         hipEventCreateWithFlags(&h->ev_clear, hipEventDisableTiming) == hipSuccess;
+             h->car_pinned[k].alloc(sizeof(float) * tab) && h->ev_table[k].create(hipEventDisableTiming) == JSDR_OK &&
+             h->ev_used[k].create(hipEventDisableTiming) == JSDR_OK;
+    ok = ok && h->copy_stream.create(hipStreamNonBlocking) == JSDR_OK && h->ev_done.create(hipEventDisableTiming) == JSDR_OK &&
+         h->ev_clear.create(hipEventDisableTiming) == JSDR_OK;
     ok = ok && h->favg.alloc(nfs) == JSDR_OK && h->stats.alloc(2 * nfs) == JSDR_OK && h->fmax.alloc(nfs) == JSDR_OK &&
          h->stage_in.alloc(2 * (size_t)h->n) == JSDR_OK && h->stage_out.alloc((size_t)h->n * nchannels) == JSDR_OK &&
          h->favg.zero() == JSDR_OK && hipDeviceSynchronize() == hipSuccess;

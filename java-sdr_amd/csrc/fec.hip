@@ -1129,40 +1129,29 @@ int jsdr_fec_decode(const uint8_t raw_host[5200], uint8_t out_host[256], int *rc
     JSDR_REQUIRE(raw_host && out_host && rc, "jsdr_fec_decode: null argument");
     DevBuf<unsigned char> raw, out;
     DevBuf<int> drc;
-    int ret = JSDR_ERR;
-    if (raw.alloc(SYMPBLOCK) == JSDR_OK && out.alloc(256) == JSDR_OK && drc.alloc(1) == JSDR_OK) {
-        // the reference leaves RSdecdata untouched when RS fails: seed the device copy with the caller's bytes
-        if (hipMemcpy(raw.p, raw_host, SYMPBLOCK, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(out.p, out_host, 256, hipMemcpyHostToDevice) == hipSuccess &&
-            jsdr_fec_decode_batch(raw.p, 1, out.p, drc.p, 0) == JSDR_OK &&
-            hipMemcpy(out_host, out.p, 256, hipMemcpyDeviceToHost) == hipSuccess &&
-            hipMemcpy(rc, drc.p, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
-            ret = JSDR_OK;
-        else if (jsdr_last_error()[0] == 0)
-            set_error("jsdr_fec_decode: transfer failed");
-    }
-    raw.release();
-    out.release();
-    drc.release();
-    return ret;
+    if (raw.alloc(SYMPBLOCK) != JSDR_OK || out.alloc(256) != JSDR_OK || drc.alloc(1) != JSDR_OK) return JSDR_ERR;
+    // the reference leaves RSdecdata untouched when RS fails: seed the device copy with the caller's bytes
+    if (hipMemcpy(raw.p, raw_host, SYMPBLOCK, hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemcpy(out.p, out_host, 256, hipMemcpyHostToDevice) == hipSuccess &&
+        jsdr_fec_decode_batch(raw.p, 1, out.p, drc.p, 0) == JSDR_OK &&
+        hipMemcpy(out_host, out.p, 256, hipMemcpyDeviceToHost) == hipSuccess &&
+        hipMemcpy(rc, drc.p, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
+        return JSDR_OK;
+    if (jsdr_last_error()[0] == 0) set_error("jsdr_fec_decode: transfer failed");
+    return JSDR_ERR;
 }
 
 int jsdr_fec_encode(const uint8_t data_host[256], uint8_t sym_host[5200])
 {
     JSDR_REQUIRE(data_host && sym_host, "jsdr_fec_encode: null argument");
     DevBuf<unsigned char> data, sym;
-    int ret = JSDR_ERR;
-    if (data.alloc(256) == JSDR_OK && sym.alloc(SYMPBLOCK) == JSDR_OK) {
-        if (hipMemcpy(data.p, data_host, 256, hipMemcpyHostToDevice) == hipSuccess &&
-            jsdr_fec_encode_batch(data.p, 1, sym.p, 0) == JSDR_OK &&
-            hipMemcpy(sym_host, sym.p, SYMPBLOCK, hipMemcpyDeviceToHost) == hipSuccess)
-            ret = JSDR_OK;
-        else if (jsdr_last_error()[0] == 0)
-            set_error("jsdr_fec_encode: transfer failed");
-    }
-    data.release();
-    sym.release();
-    return ret;
+    if (data.alloc(256) != JSDR_OK || sym.alloc(SYMPBLOCK) != JSDR_OK) return JSDR_ERR;
+    if (hipMemcpy(data.p, data_host, 256, hipMemcpyHostToDevice) == hipSuccess &&
+        jsdr_fec_encode_batch(data.p, 1, sym.p, 0) == JSDR_OK &&
+        hipMemcpy(sym_host, sym.p, SYMPBLOCK, hipMemcpyDeviceToHost) == hipSuccess)
+        return JSDR_OK;
+    if (jsdr_last_error()[0] == 0) set_error("jsdr_fec_encode: transfer failed");
+    return JSDR_ERR;
 }
 
 }  // extern "C"

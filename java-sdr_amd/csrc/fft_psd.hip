@@ -596,12 +596,6 @@ int jsdr_fft_create(jsdr_fft **out, int n, int rate)
 
 int jsdr_fft_destroy(jsdr_fft *h)
 {
-    if (!h) return JSDR_OK;
-    h->tw.release();
-    h->tw_i16.release();
-    h->in_stage.release();
-    h->out_stage.release();
-    h->pin.release();
     delete h;
     return JSDR_OK;
 }

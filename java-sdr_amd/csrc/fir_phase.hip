@@ -161,9 +161,6 @@ int jsdr_fir_create(jsdr_fir **out, float sample_rate)
 
 int jsdr_fir_destroy(jsdr_fir *h)
 {
-    if (!h) return JSDR_OK;
-    h->w_dev.release();
-    h->nco_dev.release();
     delete h;
     return JSDR_OK;
 }
@@ -204,39 +201,28 @@ int jsdr_fir_filter(jsdr_fir *h, const int32_t *in_host, int32_t *out_host, int6
     JSDR_REQUIRE(n >= 0, "jsdr_fir_filter: negative length");
     if (n == 0) return JSDR_OK;
     DevBuf<int> xh, out;
-    if (xh.alloc((size_t)n + 20) != JSDR_OK || out.alloc((size_t)n) != JSDR_OK) {
-        xh.release();
-        out.release();
+    if (xh.alloc((size_t)n + 20) != JSDR_OK || out.alloc((size_t)n) != JSDR_OK) return JSDR_ERR;
+    if (hipMemcpy(xh.p, h->hist, sizeof(int) * 20, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(xh.p + 20, in_host, sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(h->w_dev.p, h->wfir, sizeof(double) * 21, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("jsdr_fir_filter: upload failed");
         return JSDR_ERR;
     }
-    int rc = JSDR_OK;
-    do {
-        if (hipMemcpy(xh.p, h->hist, sizeof(int) * 20, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(xh.p + 20, in_host, sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->w_dev.p, h->wfir, sizeof(double) * 21, hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("jsdr_fir_filter: upload failed");
-            rc = JSDR_ERR;
-            break;
-        }
-        hipLaunchKernelGGL(k_fir_filter, dim3(grid_for(n, 256)), dim3(256), 0, 0, xh.p, h->w_dev.p, out.p,
-                           (long long)n);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpy(out_host, out.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
-            set_error("jsdr_fir_filter: kernel or download failed");
-            rc = JSDR_ERR;
-            break;
-        }
-        // carry the delay line: last 20 inputs, oldest first
-        int tmp[20];
-        for (int i = 0; i < 20; i++) {
-            int64_t src = n - 20 + i;
-            tmp[i] = src >= 0 ? in_host[src] : h->hist[20 + src];
-        }
-        memcpy(h->hist, tmp, sizeof(tmp));
-    } while (0);
-    xh.release();
-    out.release();
-    return rc;
+    hipLaunchKernelGGL(k_fir_filter, dim3(grid_for(n, 256)), dim3(256), 0, 0, xh.p, h->w_dev.p, out.p,
+                       (long long)n);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpy(out_host, out.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
+        set_error("jsdr_fir_filter: kernel or download failed");
+        return JSDR_ERR;
+    }
+    // carry the delay line: last 20 inputs, oldest first
+    int tmp[20];
+    for (int i = 0; i < 20; i++) {
+        int64_t src = n - 20 + i;
+        tmp[i] = src >= 0 ? in_host[src] : h->hist[20 + src];
+    }
+    memcpy(h->hist, tmp, sizeof(tmp));
+    return JSDR_OK;
 }
 
 int jsdr_fir_complex_gen(jsdr_fir *h, int freq, int start, int32_t *sig_host, int64_t n)
@@ -262,14 +248,12 @@ int jsdr_fir_complex_gen(jsdr_fir *h, int freq, int start, int32_t *sig_host, in
     if (out.alloc((size_t)n) != JSDR_OK) return JSDR_ERR;
     hipLaunchKernelGGL(k_fir_cgen, dim3(grid_for(n, 256)), dim3(256), 0, 0, h->nco_dev.p, period, start, out.p,
                        (long long)n);
-    int rc = JSDR_OK;
     if (hipGetLastError() != hipSuccess ||
         hipMemcpy(sig_host, out.p, sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) {
         set_error("jsdr_fir_complex_gen: kernel or download failed");
-        rc = JSDR_ERR;
+        return JSDR_ERR;
     }
-    out.release();
-    return rc;
+    return JSDR_OK;
 }
 
 int jsdr_fir_complex_mod(jsdr_fir *h, const int32_t *a_host, const int32_t *b_host, int32_t *out_host, int64_t n)
@@ -277,21 +261,15 @@ int jsdr_fir_complex_mod(jsdr_fir *h, const int32_t *a_host, const int32_t *b_ho
     JSDR_REQUIRE(h && a_host && b_host && out_host, "jsdr_fir_complex_mod: null argument");
     if (n <= 0) return JSDR_OK;
     DevBuf<int2> a, b, o;
-    int rc = JSDR_ERR;
-    if (a.alloc((size_t)n) == JSDR_OK && b.alloc((size_t)n) == JSDR_OK && o.alloc((size_t)n) == JSDR_OK) {
-        if (hipMemcpy(a.p, a_host, sizeof(int2) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(b.p, b_host, sizeof(int2) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess) {
-            hipLaunchKernelGGL(k_fir_cmod, dim3(grid_for(n, 256)), dim3(256), 0, 0, a.p, b.p, o.p, (long long)n);
-            if (hipGetLastError() == hipSuccess &&
-                hipMemcpy(out_host, o.p, sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess)
-                rc = JSDR_OK;
-        }
-        if (rc != JSDR_OK) set_error("jsdr_fir_complex_mod: transfer or kernel failed");
+    if (a.alloc((size_t)n) != JSDR_OK || b.alloc((size_t)n) != JSDR_OK || o.alloc((size_t)n) != JSDR_OK) return JSDR_ERR;
+    bool ok = hipMemcpy(a.p, a_host, sizeof(int2) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(b.p, b_host, sizeof(int2) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_fir_cmod, dim3(grid_for(n, 256)), dim3(256), 0, 0, a.p, b.p, o.p, (long long)n);
+        ok = hipGetLastError() == hipSuccess && hipMemcpy(out_host, o.p, sizeof(int2) * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    a.release();
-    b.release();
-    o.release();
-    return rc;
+    if (!ok) set_error("jsdr_fir_complex_mod: transfer or kernel failed");
+    return ok ? JSDR_OK : JSDR_ERR;
 }
 
 int jsdr_phase_maxabs(const float *iq_dev, int64_t nframes, int n, float *max_dev, void *stream)
@@ -336,26 +314,23 @@ int jsdr_phase_columns(const float *iq_dev, int n, int bx, int32_t *pix_host, fl
     if (ncol == 0) return JSDR_OK;
     DevBuf<int> dfirst, dcount;
     DevBuf<float> dai, daq;
-    int rc = JSDR_ERR;
-    if (dfirst.alloc(ncol) == JSDR_OK && dcount.alloc(ncol) == JSDR_OK && dai.alloc(ncol) == JSDR_OK &&
-        daq.alloc(ncol) == JSDR_OK) {
-        if (hipMemcpy(dfirst.p, first.data(), sizeof(int) * ncol, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dcount.p, count.data(), sizeof(int) * ncol, hipMemcpyHostToDevice) == hipSuccess) {
-            hipLaunchKernelGGL(k_phase_columns, dim3((ncol + 63) / 64), dim3(64), 0, 0,
-                               reinterpret_cast<const float2 *>(iq_dev), dfirst.p, dcount.p, ncol, dai.p, daq.p);
-            if (hipGetLastError() == hipSuccess &&
-                hipMemcpy(avgi_host, dai.p, sizeof(float) * ncol, hipMemcpyDeviceToHost) == hipSuccess &&
-                hipMemcpy(avgq_host, daq.p, sizeof(float) * ncol, hipMemcpyDeviceToHost) == hipSuccess)
-                rc = JSDR_OK;
-        }
-        if (rc != JSDR_OK) set_error("jsdr_phase_columns: transfer or kernel failed");
+    if (dfirst.alloc(ncol) != JSDR_OK || dcount.alloc(ncol) != JSDR_OK || dai.alloc(ncol) != JSDR_OK || daq.alloc(ncol) != JSDR_OK)
+        return JSDR_ERR;
+    bool ok = hipMemcpy(dfirst.p, first.data(), sizeof(int) * ncol, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(dcount.p, count.data(), sizeof(int) * ncol, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_phase_columns, dim3((ncol + 63) / 64), dim3(64), 0, 0,
+                           reinterpret_cast<const float2 *>(iq_dev), dfirst.p, dcount.p, ncol, dai.p, daq.p);
+        ok = hipGetLastError() == hipSuccess &&
+             hipMemcpy(avgi_host, dai.p, sizeof(float) * ncol, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(avgq_host, daq.p, sizeof(float) * ncol, hipMemcpyDeviceToHost) == hipSuccess;
     }
-    dfirst.release();
-    dcount.release();
-    dai.release();
-    daq.release();
-    if (rc == JSDR_OK) memcpy(pix_host, pix.data(), sizeof(int) * ncol);
-    return rc;
+    if (!ok) {
+        set_error("jsdr_phase_columns: transfer or kernel failed");
+        return JSDR_ERR;
+    }
+    memcpy(pix_host, pix.data(), sizeof(int) * ncol);
+    return JSDR_OK;
 }
 
 // ---- phase.java as a handle (the IAudioHandler drop-in: one frame in per receive(), the two reductions of
@@ -378,8 +353,6 @@ int jsdr_phase_create(jsdr_phase **out, int n)
     h->n = n;
     if (h->dpy.alloc(2 * (size_t)n) != JSDR_OK || h->dmax.alloc(1) != JSDR_OK ||
         hipMemset(h->dpy.p, 0, sizeof(float) * 2 * (size_t)n) != hipSuccess) {  // `new float[...]` is zero-filled (:23)
-        h->dpy.release();
-        h->dmax.release();
         delete h;
         set_error("jsdr_phase_create: no HIP device or out of device memory");
         return JSDR_ERR;
@@ -390,9 +363,6 @@ int jsdr_phase_create(jsdr_phase **out, int n)
 
 int jsdr_phase_destroy(jsdr_phase *h)
 {
-    if (!h) return JSDR_OK;
-    h->dpy.release();
-    h->dmax.release();
     delete h;
     return JSDR_OK;
 }

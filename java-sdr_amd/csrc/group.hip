@@ -89,10 +89,10 @@ struct Rank {
     char err[512] = "";
     jsdr_bpsk *dem = nullptr;
     jsdr_fft *fft = nullptr;
-    hipStream_t main = nullptr, psd = nullptr, gather = nullptr;
-    uint8_t *slots = nullptr, *gathered = nullptr;
+    Stream main, psd, gather;
+    DevBuf<uint8_t> slots, gathered;
     int64_t slot_bytes = 0;
-    hipEvent_t ev_packed = nullptr, ev_pulled = nullptr;
+    Event ev_packed, ev_pulled;
     bool pulled_once = false;
     ncclComm_t comm = nullptr;
 };
@@ -181,7 +181,7 @@ static void run_batch(Rank *r, const Job &j)
     }
     // the packing waits (on the gather stream) for the side-stream tail / FEC of this call; the next call's front end on
     // the main stream is not serialised behind it
-    if (!failed && jsdr_bpsk_pack_slots(r->dem, r->slots, r->gather) != JSDR_OK) {
+    if (!failed && jsdr_bpsk_pack_slots(r->dem, r->slots.p, r->gather) != JSDR_OK) {
         rank_fail(r, "jsdr_bpsk_pack_slots");
         failed = true;
     }
@@ -205,7 +205,7 @@ static void run_batch(Rank *r, const Job &j)
         // communicator in a communicator clique ... each call has to be done from a different thread or process, or need to
         // use Group Semantics", rccl.h:522-529; the group calls are for "managing multiple GPUs from a single thread", :899) --
         // one thread per communicator is the first alternative, the rendezvous above guarantees every thread gets here.
-        const int rc = g_rccl.AllGather(r->slots, r->gathered, seg, NCCL_UINT8, r->comm, r->gather);
+        const int rc = g_rccl.AllGather(r->slots.p, r->gathered.p, seg, NCCL_UINT8, r->comm, r->gather);
         if (rc != 0) {
             r->status = JSDR_ERR;
             snprintf(r->err, sizeof(r->err), "jsdr_group rank %d: ncclAllGather: %s", r->index, g_rccl.GetErrorString(rc));
@@ -219,7 +219,7 @@ static void run_batch(Rank *r, const Job &j)
         for (Rank *o : g->ranks) {
             hipError_t e = hipStreamWaitEvent(r->gather, o->ev_packed, 0);
             if (e == hipSuccess)
-                e = hipMemcpyAsync(r->gathered + (size_t)o->index * seg, o->slots, seg, hipMemcpyDeviceToDevice, r->gather);
+                e = hipMemcpyAsync(r->gathered.p + (size_t)o->index * seg, o->slots.p, seg, hipMemcpyDeviceToDevice, r->gather);
             if (e != hipSuccess) {
                 r->status = JSDR_ERR;
                 snprintf(r->err, sizeof(r->err), "jsdr_group rank %d: copy gather from rank %d: %s", r->index, o->index, hipGetErrorString(e));
@@ -325,14 +325,13 @@ static int rank_create(void *p, int index)
     CreateArgs *a = static_cast<CreateArgs *>(p);
     Group *g = a->g;
     Rank *r = g->ranks[index];
-    JSDR_HIP_TRY(hipStreamCreateWithFlags(&r->main, hipStreamNonBlocking));
-    JSDR_HIP_TRY(hipStreamCreateWithFlags(&r->gather, hipStreamNonBlocking));
-    JSDR_HIP_TRY(hipEventCreateWithFlags(&r->ev_packed, hipEventDisableTiming));
-    JSDR_HIP_TRY(hipEventCreateWithFlags(&r->ev_pulled, hipEventDisableTiming));
+    if (r->main.create(hipStreamNonBlocking) != JSDR_OK || r->gather.create(hipStreamNonBlocking) != JSDR_OK ||
+        r->ev_packed.create(hipEventDisableTiming) != JSDR_OK || r->ev_pulled.create(hipEventDisableTiming) != JSDR_OK)
+        return JSDR_ERR;
     if (jsdr_bpsk_create(&r->dem, a->rate, a->frame, a->tuning, a->do_fft, a->do_up, g->streams_per_dev, a->max_batch) != JSDR_OK)
         return JSDR_ERR;
     if (g->with_psd) {
-        JSDR_HIP_TRY(hipStreamCreateWithFlags(&r->psd, hipStreamNonBlocking));
+        if (r->psd.create(hipStreamNonBlocking) != JSDR_OK) return JSDR_ERR;
         if (jsdr_fft_create(&r->fft, a->frame, a->rate) != JSDR_OK) return JSDR_ERR;
     }
     // fft.receive and FUNcubeBPSKDemod.receive over the same batch: where the library says the CU split pays (jsdr_bpsk_pair_shares:
@@ -347,10 +346,10 @@ static int rank_create(void *p, int index)
     if (jsdr_bpsk_slot_info(r->dem, &sb, nullptr, nullptr, nullptr, nullptr) != JSDR_OK) return JSDR_ERR;
     r->slot_bytes = sb;  // (the creating thread copies rank 0's into the group once every rank is done: no shared write here)
     const size_t seg = (size_t)g->streams_per_dev * (size_t)sb;
-    JSDR_HIP_TRY(hipMalloc((void **)&r->slots, seg > 64 ? seg : 64));
+    if (r->slots.alloc(seg > 64 ? seg : 64) != JSDR_OK) return JSDR_ERR;
     const size_t gbytes = (seg > 64 ? seg : 64) * (size_t)g->ndev;
-    JSDR_HIP_TRY(hipMalloc((void **)&r->gathered, gbytes));
-    JSDR_HIP_TRY(hipMemset(r->gathered, 0, gbytes));
+    if (r->gathered.alloc(gbytes) != JSDR_OK) return JSDR_ERR;
+    JSDR_HIP_TRY(hipMemset(r->gathered.p, 0, gbytes));
     if (g->copy_gather) {
         for (Rank *o : g->ranks)
             if (o->dev != r->dev) {
@@ -376,7 +375,7 @@ static int rank_selftest(void *p, int index)
     uint8_t mine[64];
     for (int i = 0; i < 64; i++) mine[i] = (uint8_t)(0xA5 ^ (index * 37 + i));
     bool failed = false;
-    if (hipMemcpy(r->slots, mine, seg, hipMemcpyHostToDevice) != hipSuccess) failed = true;
+    if (hipMemcpy(r->slots.p, mine, seg, hipMemcpyHostToDevice) != hipSuccess) failed = true;
     if (!failed && g->copy_gather && hipEventRecord(r->ev_packed, r->gather) != hipSuccess) failed = true;
     if (failed) {
         set_error("copying the test pattern to the device failed");
@@ -390,7 +389,7 @@ static int rank_selftest(void *p, int index)
         return r->status;
     }
     if (!g->copy_gather) {
-        const int rc = g_rccl.AllGather(r->slots, r->gathered, seg, NCCL_UINT8, r->comm, r->gather);
+        const int rc = g_rccl.AllGather(r->slots.p, r->gathered.p, seg, NCCL_UINT8, r->comm, r->gather);
         if (rc != 0) {
             set_error("ncclAllGather: %s", g_rccl.GetErrorString(rc));
             rank_fail(r, "self-test");
@@ -406,7 +405,7 @@ static int rank_selftest(void *p, int index)
     } else {
         for (Rank *o : g->ranks) {
             hipError_t e = hipStreamWaitEvent(r->gather, o->ev_packed, 0);
-            if (e == hipSuccess) e = hipMemcpyAsync(r->gathered + (size_t)o->index * seg, o->slots, seg, hipMemcpyDeviceToDevice, r->gather);
+            if (e == hipSuccess) e = hipMemcpyAsync(r->gathered.p + (size_t)o->index * seg, o->slots.p, seg, hipMemcpyDeviceToDevice, r->gather);
             if (e != hipSuccess) {
                 set_error("copy gather from rank %d: %s", o->index, hipGetErrorString(e));
                 rank_fail(r, "self-test");
@@ -416,7 +415,7 @@ static int rank_selftest(void *p, int index)
     }
     std::vector<uint8_t> got(seg * (size_t)g->ndev);
     bool ok = r->status == JSDR_OK && hipStreamSynchronize(r->gather) == hipSuccess &&
-              hipMemcpy(got.data(), r->gathered, got.size(), hipMemcpyDeviceToHost) == hipSuccess;
+              hipMemcpy(got.data(), r->gathered.p, got.size(), hipMemcpyDeviceToHost) == hipSuccess;
     if (g->copy_gather) step_barrier(g, false);  // nobody overwrites its 64 bytes while another rank may still pull them
     if (r->status != JSDR_OK) return JSDR_ERR;
     if (!ok) {
@@ -432,7 +431,7 @@ static int rank_selftest(void *p, int index)
                 rank_fail(r, "self-test");
                 return JSDR_ERR;
             }
-    (void)hipMemset(r->gathered, 0, got.size());
+    (void)hipMemset(r->gathered.p, 0, got.size());
     return JSDR_OK;
 }
 
@@ -459,14 +458,7 @@ static void group_free(Group *g)
         else if (r->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(r->comm);
         if (r->dem) (void)jsdr_bpsk_destroy(r->dem);
         if (r->fft) (void)jsdr_fft_destroy(r->fft);
-        if (r->slots) (void)hipFree(r->slots);
-        if (r->gathered) (void)hipFree(r->gathered);
-        if (r->ev_packed) (void)hipEventDestroy(r->ev_packed);
-        if (r->ev_pulled) (void)hipEventDestroy(r->ev_pulled);
-        if (r->main) (void)hipStreamDestroy(r->main);
-        if (r->psd) (void)hipStreamDestroy(r->psd);
-        if (r->gather) (void)hipStreamDestroy(r->gather);
-        delete r;
+        delete r;  // (its buffers, events and streams, on its device)
     }
     delete g;
 }
@@ -639,7 +631,7 @@ int jsdr_group_sync(jsdr_group *h)
 int jsdr_group_gathered(jsdr_group *h, int index, const uint8_t **slots_dev, int64_t *bytes)
 {
     JSDR_REQUIRE(h && index >= 0 && index < h->g->ndev && slots_dev, "jsdr_group_gathered: bad argument");
-    *slots_dev = h->g->ranks[index]->gathered;
+    *slots_dev = h->g->ranks[index]->gathered.p;
     if (bytes) *bytes = (int64_t)h->g->total_streams * h->g->slot_bytes;
     return JSDR_OK;
 }
@@ -654,7 +646,7 @@ int jsdr_group_read_slot(jsdr_group *h, int index, int stream, uint8_t *slot_hos
     JSDR_HIP_TRY(hipGetDevice(&prev));
     Rank *r = g->ranks[index];
     JSDR_HIP_TRY(hipSetDevice(r->dev));
-    const hipError_t e = hipMemcpy(slot_host, r->gathered + (size_t)stream * (size_t)g->slot_bytes, (size_t)g->slot_bytes, hipMemcpyDeviceToHost);
+    const hipError_t e = hipMemcpy(slot_host, r->gathered.p + (size_t)stream * (size_t)g->slot_bytes, (size_t)g->slot_bytes, hipMemcpyDeviceToHost);
     (void)hipSetDevice(prev);
     JSDR_HIP_TRY(e);
     return JSDR_OK;

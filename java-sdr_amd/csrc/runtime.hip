@@ -34,7 +34,7 @@ int ensure_dynamic_lds(const void *kernel, size_t bytes)
 }
 
 struct Timer {
-    hipEvent_t a, b;
+    Event a, b;
 };
 
 // one thread per sample frame: 4 B (or 2 B mono) in, 8 B out
@@ -112,6 +112,17 @@ int jsdr_free(void *dev)
     return JSDR_OK;
 }
 
+// what the library's own handles and calls hold at the moment (common.h: the owning types count for themselves; free device
+// memory as the runtime reports it says nothing on a card that others use)
+int jsdr_live_resources(int64_t *device_buffers, int64_t *device_bytes, int64_t *pinned_buffers, int64_t *streams_and_events)
+{
+    if (device_buffers) *device_buffers = live_dev_bufs.load();
+    if (device_bytes) *device_bytes = live_dev_bytes.load();
+    if (pinned_buffers) *pinned_buffers = live_pinned.load();
+    if (streams_and_events) *streams_and_events = live_objects.load();
+    return JSDR_OK;
+}
+
 int jsdr_memset(void *dev, int value, size_t bytes)
 {
     JSDR_HIP_TRY(hipMemset(dev, value, bytes));
@@ -155,19 +166,17 @@ int jsdr_timer_create(void **timer)
 {
     JSDR_REQUIRE(timer, "jsdr_timer_create: null argument");
     Timer *t = new Timer();
-    JSDR_HIP_TRY(hipEventCreate(&t->a));
-    JSDR_HIP_TRY(hipEventCreate(&t->b));
+    if (t->a.create() != JSDR_OK || t->b.create() != JSDR_OK) {
+        delete t;
+        return JSDR_ERR;
+    }
     *timer = t;
     return JSDR_OK;
 }
 
 int jsdr_timer_destroy(void *timer)
 {
-    Timer *t = (Timer *)timer;
-    if (!t) return JSDR_OK;
-    (void)hipEventDestroy(t->a);
-    (void)hipEventDestroy(t->b);
-    delete t;
+    delete (Timer *)timer;
     return JSDR_OK;
 }
 
