@@ -161,7 +161,7 @@ int jsdr_bpsk_create(jsdr_bpsk **h, int rate, int nsamples_per_frame, int tuning
                      int do_up, int nstreams, int64_t max_batch_samples);
 int jsdr_bpsk_destroy(jsdr_bpsk *h);
 /* the constant tables as the library holds them (host side): which = 0 dsFilter[27] (:27-55), 1 dmFilter[65] (:58-77),
- * 2 SYNC_VECTOR[65] (:79-81) as +1/-1 */
+ * 2 SYNC_VECTOR[65] (:79-81) as +1/-1, 3 cosTab[256] and 4 sinTab[256] (:159-162) of the tuner and the VCO */
 int jsdr_bpsk_table(int which, double *out, int cap);
 /* arithmetic of the demodulator (before the first sample): EXACT = every double product and sum rounded separately in
  * the reference's order (bits, bytes AND doubles identical to the Java arithmetic); FAST = fused multiply-adds in the
@@ -447,6 +447,12 @@ int jsdr_bpsk_set_cu_share(jsdr_bpsk *h, int wgs_per_cu); /* see jsdr_fft_set_cu
 int jsdr_bpsk_pair_shares(jsdr_bpsk *h, int *fft_wgs_per_cu, int *bpsk_wgs_per_cu);
 /* diagnostics: tiles x streams of the last tune-mode front-end launch (k_fm, k_fm_f32) and the workgroups that strode over them */
 int jsdr_bpsk_last_launch(jsdr_bpsk *h, int64_t *work_items, int64_t *workgroups);
+/* diagnostics: which form of k_fm the last call took.  *specialised 1: the form with the 8-phase tuner's exact factors built in
+ * (tuning an eighth of the rate, exact variant, decimation 10, int16 batches of more than FM_THREADS outputs), *phase the tuner
+ * phase (0 .. 7, table index 32 * phase) of the first window sample of the call's first tile; its other tiles alternate
+ * between that phase and the one four further.  0 and -1: the generic form, or a call that did not take k_fm.  The results are
+ * bit-identical either way. */
+int jsdr_bpsk_fm_form(jsdr_bpsk *h, int *specialised, int *phase);
 /* wait until every kernel of the calls made so far has finished (the 9600 Hz tail and the FEC decoder run on
  * an internal side stream so that they overlap the next call's front end; the getters below call this). */
 int jsdr_bpsk_sync(jsdr_bpsk *h);

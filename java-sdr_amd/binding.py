@@ -422,9 +422,9 @@ class BpskSnapshot(C.Structure):
 
 
 def bpsk_table(which):
-    out = np.empty(65, np.float64)
-    _check(lib().jsdr_bpsk_table(which, _addr(out), 65), "jsdr_bpsk_table")
-    return out[:27 if which == 0 else 65].copy()
+    out = np.empty(256, np.float64)
+    _check(lib().jsdr_bpsk_table(which, _addr(out), 256), "jsdr_bpsk_table")
+    return out[:{0: 27, 1: 65, 2: 65}.get(which, 256)].copy()
 
 
 class Bpsk:
@@ -529,6 +529,12 @@ class Bpsk:
         a, b = C.c_int64(), C.c_int64()
         _check(lib().jsdr_bpsk_last_launch(self.h, C.byref(a), C.byref(b)), "jsdr_bpsk_last_launch")
         return a.value, b.value
+
+    def fm_form(self):
+        """(specialised, phase) of the last call's k_fm: (True, 0..7) for the 8-phase tuner's form, (False, -1) otherwise"""
+        a, b = C.c_int(), C.c_int()
+        _check(lib().jsdr_bpsk_fm_form(self.h, C.byref(a), C.byref(b)), "jsdr_bpsk_fm_form")
+        return bool(a.value), b.value
 
     def sync(self):
         _check(lib().jsdr_bpsk_sync(self.h), "jsdr_bpsk_sync")

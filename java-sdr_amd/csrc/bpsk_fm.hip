@@ -11,7 +11,9 @@
 // of the last).  Compiled with -ffp-contract=off.  Reads dm_taps of its copy of the tables (matched_block, k_fm's
 // short-call matched half).
 #include "bpsk_units.h"
+#include "bpsk_tuner.h"  // the 8-phase tuner's factor classes (k_fm's PH forms)
 #include <math.h>
+#include <type_traits>
 #include <stddef.h>
 #include <stdlib.h>
 
@@ -214,7 +216,33 @@ __global__ void k_fm_prep(EdgeArgs e, HistArgs hi, ScatterArgs sc)
 // SMALL: the instantiation for SHORT calls (at most FM_THREADS outputs: the receive() form) -- the matched half as one
 // output per thread; a kernel of its own so that its loop does not sit in the batch kernel's register allocation (as a
 // run-time branch it cost the batch kernel its fourth wave per SIMD: 123 -> 131 VGPRs, 16.8 -> 20.1 ms at 8192 streams)
-template <int D, int R, bool MIX, bool DC, bool FAST, bool SMALL = false>
+//
+// PH >= 0: the form for the 8-PHASE TUNER (12 kHz / 96 kHz: an exact 8-cycle over table entries of which five are 1.0, -1.0 or
+// 0.0; bpsk_tuner.h).  Window sample m of a tile whose sample 0 is at phase p has the factors of phase p + m, and the front
+// loop is unrolled over m, so with p known at compile time the class of every factor is a constant:
+//   +-1.0 : no tuner product (d * +-1.0 is +-d), and EVERY tap of that sample and rail is one fma with +-tap.  d is a float and
+//           has at most 24 significant bits, a tap is k 2^-15 with |k| < 2^14 (ds_taps_are_short below): d * tap is exact in
+//           double, so fma(d, +-tap, acc) rounds once what acc + RN(RN(d * +-1.0) * tap) rounds once -- the same double.
+//   0.0   : nothing at all for that rail of that sample.  The int16 sample is finite, so its product is +-0 and so is every tap
+//           product; an accumulator starts at +0.0 and never becomes -0 (a rounded sum is -0 only when both terms are), so
+//           adding +-0 leaves it as it is.  (The float kernel, whose input may be NaN or Inf, has no such form.)
+//   other : as in the generic form.
+// Tiles are 65 FM_NB D samples apart, which is 4 mod 8: one launch sees the phases p and p + 4, whose classes differ (sin is 0.0
+// at phase 0 and 1.2e-16 at phase 4).  The instantiation PH = p mod 4 holds both bodies and a tile branches to its own.  The
+// launcher takes this form only where the host has found exactly these classes in the schedule's table, by bit pattern
+// (Schedule::trot); every other call takes PH = -1: the class tests below fold away and leave the generic arithmetic,
+// operation for operation.
+constexpr bool ds_taps_are_short()
+{
+    for (int n = 0; n < 14; n++) {
+        const float k = kDsHalf[n] * 32768.0f;
+        if (k != (float)(int)k || k >= 16384.0f || k <= -16384.0f) return false;
+    }
+    return true;
+}
+static_assert(ds_taps_are_short(), "dsFilter: every tap times 2^15 is an integer of magnitude below 2^14 (k_fm's +-1.0 fmas are exact)");
+
+template <int D, int R, bool MIX, bool DC, bool FAST, bool SMALL = false, int PH = -1>
 #ifndef JSDR_FM_MINWAVES
 #define JSDR_FM_MINWAVES 2
 #endif
@@ -222,6 +250,8 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
 {
     constexpr int RD = D * R, NS = RD - D + 27, NSQ = (NS + 3) / 4;
     constexpr int JOBS = (FM_NT + R - 1) / R, ROUNDS = (JOBS + FM_THREADS - 1) / FM_THREADS;
+    static_assert(PH < 0 || (MIX && !FAST && PH < 4 && (D * R) % 8 == 0 && (65 * FM_NB * D) % 8 == 4),
+                  "k_fm<PH>: the lane span is whole periods and a tile is half a period past the one before");
     extern __shared__ __align__(16) unsigned char smem[];
     double2 *X = reinterpret_cast<double2 *>(smem);                    // [FM_NT]: X[t] = sample G - 64 + t
     double *sc = reinterpret_cast<double *>(smem + FM_NT * sizeof(double2));  // [512]
@@ -264,6 +294,9 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
     clk_last_ = __builtin_amdgcn_s_memtime();
 #endif
     // ================================================================================ front half
+    // (a generic lambda: the round loop's text once, instantiated for the phases of this kernel; PHC < 0: the generic arithmetic)
+    auto front = [&](auto phc) __attribute__((always_inline)) {
+    constexpr int PHC = decltype(phc)::value;
 #ifdef JSDR_X_NOFRONT
     if (a.nds < 0)
 #endif
@@ -336,9 +369,11 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
                         const int w = (t == 0) ? w4.x : (t == 1) ? w4.y : (t == 2) ? w4.z : w4.w;
                         double di, dq;
                         fm_convert_2p15(w, a.ic, a.qc, DC, di, dq, FAST ? &amx : nullptr);  // 2^15 x the reference's (HOWARD)
+                        // the factors' classes: constants once the loops are unrolled
+                        const int ci = PHC >= 0 ? tuner8_class(PHC + m, 0) : TC_GEN, cq = PHC >= 0 ? tuner8_class(PHC + m, 1) : TC_GEN;
                         if constexpr (MIX) {  // :388-390 component-wise, not a complex multiply
-                            di = di * tb[2 * m];
-                            dq = dq * tb[2 * m + 1];
+                            if (ci == TC_GEN) di = di * tb[2 * m];
+                            if (cq == TC_GEN) dq = dq * tb[2 * m + 1];
                         }
 #pragma unroll
                         for (int r = 0; r < R; r++) {
@@ -349,11 +384,16 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
                                 // the output's first tap (the sum is +0.0: a product of either sign of zero gives +0
                                 // both ways) and a tap that is a power of two (the product is exact)
                                 const bool same = age == 0 || ((kDsPow2Mask >> age) & 1);
-                                if (FAST || same) {
-                                    ai[r] = __builtin_fma(di, tp, ai[r]);
-                                    aq[r] = __builtin_fma(dq, tp, aq[r]);
+                                // ... and every tap of a sample whose tuner factor is +-1.0 (the sign goes to the tap); none
+                                // where it is 0.0
+                                if (FAST || same || ci != TC_GEN) {
+                                    if (ci != TC_ZERO) ai[r] = __builtin_fma(di, ci == TC_MONE ? -tp : tp, ai[r]);
                                 } else {
                                     ai[r] += di * tp;
+                                }
+                                if (FAST || same || cq != TC_GEN) {
+                                    if (cq != TC_ZERO) aq[r] = __builtin_fma(dq, cq == TC_MONE ? -tp : tp, aq[r]);
+                                } else {
                                     aq[r] += dq * tp;
                                 }
                             }
@@ -402,6 +442,13 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
                 if (t < FM_NT) X[t] = val;
             }
         }
+    }
+    };
+    if constexpr (PH < 0) {
+        front(std::integral_constant<int, -1>{});
+    } else {  // tile-uniform: the phase of the tile's window sample 0 is PH or PH + 4
+        if (((e0 + a.trot) & 7) == PH) front(std::integral_constant<int, PH>{});
+        else front(std::integral_constant<int, PH + 4>{});
     }
     if constexpr (FAST) {  // non-negative floats order like their bit patterns
 #pragma unroll
@@ -565,8 +612,10 @@ int launch_fm_prep(const EdgeArgs &ea, const HistArgs &ha, const ScatterArgs &sc
 }
 
 template <int D, int R>
-static int launch_fm_t(const FmArgs &a_in, bool mix, bool dc, bool fast, int nstreams, hipStream_t st, long long *items, long long *grid_out)
+static int launch_fm_t(const FmArgs &a_in, bool mix, bool dc, bool fast, int nstreams, hipStream_t st, long long *items, long long *grid_out,
+                       int *phase)
 {
+    *phase = -1;
     const size_t lds = (size_t)FM_NT * sizeof(double2) + 512 * sizeof(double);
     const long long span = 65LL * FM_NB;
     const long long ntiles = (a_in.g_first + a_in.nds - a_in.tile0 + span - 1) / span;
@@ -583,12 +632,29 @@ static int launch_fm_t(const FmArgs &a_in, bool mix, bool dc, bool fast, int nst
     *items = ntiles * nstreams;
     *grid_out = gx;
     const dim3 grid((unsigned)gx), block(FM_THREADS);
-#define JSDR_FM_LAUNCH(MIX, DC, FAST, SMALL)                                                                    \
+#define JSDR_FM_LAUNCH_PH(MIX, DC, FAST, SMALL, PH)                                                             \
     do {                                                                                                        \
-        JSDR_LDS_ATTR((k_fm<D, R, MIX, DC, FAST, SMALL>), lds);                                                 \
-        hipLaunchKernelGGL((k_fm<D, R, MIX, DC, FAST, SMALL>), grid, block, lds, st, a);                        \
+        JSDR_LDS_ATTR((k_fm<D, R, MIX, DC, FAST, SMALL, PH>), lds);                                             \
+        hipLaunchKernelGGL((k_fm<D, R, MIX, DC, FAST, SMALL, PH>), grid, block, lds, st, a);                    \
     } while (0)
-    if (!fast && a.nds <= FM_THREADS && ntiles == 1) {  // a short call (receive()): the one-output-per-thread matched half
+#define JSDR_FM_LAUNCH(MIX, DC, FAST, SMALL) JSDR_FM_LAUNCH_PH(MIX, DC, FAST, SMALL, -1)
+    const bool small = !fast && a.nds <= FM_THREADS && ntiles == 1;
+    if constexpr (D == 10) {
+        // the 8-phase tuner's form (k_fm<PH>): exact variant, the batch kernel, a table whose factors the host has classified
+        if (mix && !fast && !small && a.trot >= 0 && a.tper == 8) {
+            const long long v = (long long)a.first_out + (long long)D * (a.tile0 - 64 - a.g_first);  // k_fm's e0 of tile 0
+            const int p0 = (int)((((v % 8) + 8) % 8 + a.trot) & 7);
+            *phase = p0;
+            switch (p0 & 3) {
+                case 0: if (dc) JSDR_FM_LAUNCH_PH(true, true, false, false, 0); else JSDR_FM_LAUNCH_PH(true, false, false, false, 0); break;
+                case 1: if (dc) JSDR_FM_LAUNCH_PH(true, true, false, false, 1); else JSDR_FM_LAUNCH_PH(true, false, false, false, 1); break;
+                case 2: if (dc) JSDR_FM_LAUNCH_PH(true, true, false, false, 2); else JSDR_FM_LAUNCH_PH(true, false, false, false, 2); break;
+                default: if (dc) JSDR_FM_LAUNCH_PH(true, true, false, false, 3); else JSDR_FM_LAUNCH_PH(true, false, false, false, 3); break;
+            }
+            return launched();
+        }
+    }
+    if (small && a.nds <= FM_THREADS && ntiles == 1) {  // a short call (receive()): the one-output-per-thread matched half
         if (mix) { if (dc) JSDR_FM_LAUNCH(true, true, false, true); else JSDR_FM_LAUNCH(true, false, false, true); }
         else { if (dc) JSDR_FM_LAUNCH(false, true, false, true); else JSDR_FM_LAUNCH(false, false, false, true); }
     } else if (fast) {
@@ -599,16 +665,18 @@ static int launch_fm_t(const FmArgs &a_in, bool mix, bool dc, bool fast, int nst
         else { if (dc) JSDR_FM_LAUNCH(false, true, false, false); else JSDR_FM_LAUNCH(false, false, false, false); }
     }
 #undef JSDR_FM_LAUNCH
+#undef JSDR_FM_LAUNCH_PH
     return launched();
 }
 
-int launch_fm(const FmArgs &a, int decim, bool mix, bool dc, bool fast, int nstreams, hipStream_t st, long long *items, long long *grid)
+int launch_fm(const FmArgs &a, int decim, bool mix, bool dc, bool fast, int nstreams, hipStream_t st, long long *items, long long *grid,
+              int *phase)
 {
     switch (decim) {
-        case 4: return launch_fm_t<4, 5>(a, mix, dc, fast, nstreams, st, items, grid);
-        case 5: return launch_fm_t<5, 4>(a, mix, dc, fast, nstreams, st, items, grid);
-        case 10: return launch_fm_t<10, 4>(a, mix, dc, fast, nstreams, st, items, grid);
-        case 20: return launch_fm_t<20, 4>(a, mix, dc, fast, nstreams, st, items, grid);
+        case 4: return launch_fm_t<4, 5>(a, mix, dc, fast, nstreams, st, items, grid, phase);
+        case 5: return launch_fm_t<5, 4>(a, mix, dc, fast, nstreams, st, items, grid, phase);
+        case 10: return launch_fm_t<10, 4>(a, mix, dc, fast, nstreams, st, items, grid, phase);
+        case 20: return launch_fm_t<20, 4>(a, mix, dc, fast, nstreams, st, items, grid, phase);
     }
     set_error("bpsk: unsupported decimation %d", decim);
     return JSDR_ERR;

@@ -115,6 +115,7 @@ struct jsdr_bpsk {
     bool halo_in_dmh = false;      // where the last call left the 64 VCO-mixed history samples (dm[s][0..63] or dmh)
     bool use_fm = true;            // JSDR_FM=0: always the three-kernel path
     long long last_fm_items = 0, last_fm_grid = 0;  // jsdr_bpsk_last_launch
+    int last_fm_phase = -1;                         // jsdr_bpsk_fm_form: the last call's k_fm form (-1: generic, or another kernel)
     int share_wgs_per_cu = 0;      // jsdr_bpsk_set_cu_share: workgroups per CU k_fm is held to (0: one per tile, all the chip takes)
     int num_cu = 0;                // CUs of the device (device_cus: asked at the first use, 0 until then)
     int variant = 0;               // 0 exact-order FP64, 1 fast (FMA-contracted FP64, margin-certified decisions)
@@ -1213,6 +1214,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
     unsigned char kh0[26], mh0[26];  // the tuner indices / mix flags of the 26 samples before the call (build_schedule moves them on)
     memcpy(kh0, h->h_khist, 26);
     memcpy(mh0, h->h_mhist, 26);
+    h->last_fm_phase = -1;  // (until this call's k_fm says otherwise)
     const long long nds = build_schedule(h, L);
     JSDR_REQUIRE(nds <= h->max_ds, "bpsk: internal: %lld decimated samples exceed capacity %lld", nds, h->max_ds);
     // after a retune the call's samples, or the 26 history samples its first windows reach into, may lie on both sides of
@@ -1442,6 +1444,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         ma.first_out = first_out;
         ma.amax = h->amax.p;
         ma.grid_limit = h->share_wgs_per_cu * h->num_cu;  // (jsdr_bpsk_set_cu_share has asked for the CU count)
+        ma.trot = h->cur.mix == 1 ? h->cur.trot : -1;
         if (rawf_dev) {
             EdgeF32Args ea;
             ea.rawf = fa.rawf;
@@ -1481,7 +1484,8 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
             if (launch_fm_f32(mf, h->decim, h->cur.mix != 0, S, st, &h->last_fm_items, &h->last_fm_grid) != JSDR_OK) return JSDR_ERR;
         } else {
         h->front_name = "k_fm";
-        if (launch_fm(ma, h->decim, h->cur.mix != 0, (ic != 0) || (qc != 0), h->variant != 0, S, st, &h->last_fm_items, &h->last_fm_grid) != JSDR_OK)
+        if (launch_fm(ma, h->decim, h->cur.mix != 0, (ic != 0) || (qc != 0), h->variant != 0, S, st, &h->last_fm_items, &h->last_fm_grid,
+                      &h->last_fm_phase) != JSDR_OK)
             return JSDR_ERR;
         }
         h->dmh_cur ^= 1;
@@ -1649,6 +1653,10 @@ static void bpsk_phase_clocks_report(const jsdr_bpsk *h)
 
 extern "C" {
 
+// entry n of the tuner's and the VCO's tables (:159-162): double argument as in Java, correctly rounded function value
+static double table_cos(int n) { return (double)cosl((long double)(n * 2.0 * TUNER_PI / 256)); }
+static double table_sin(int n) { return (double)sinl((long double)(n * 2.0 * TUNER_PI / 256)); }
+
 int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuning_hz, int do_fft, int do_up,
                      int nstreams, int64_t max_batch_samples)
 {
@@ -1750,10 +1758,9 @@ int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuni
     }
     // tables (:159-162): Math.sin/cos are allowed 1 ulp; the host libm stands in (DESIGN.md "tables")
     std::vector<double> sc(512);
-    for (int n = 0; n < 256; n++) {  // double argument as in Java, correctly rounded function value
-        double arg = n * 2.0 * TUNER_PI / 256;
-        sc[n] = (double)cosl((long double)arg);
-        sc[256 + n] = (double)sinl((long double)arg);
+    for (int n = 0; n < 256; n++) {
+        sc[n] = table_cos(n);
+        sc[256 + n] = table_sin(n);
     }
     BpskConst bc;  // the kernels' constant tables: dsFilter, dmFilter, SYNC_VECTOR (jsdr_bpsk_table has them)
     memset(&bc, 0, sizeof(bc));
@@ -1960,6 +1967,14 @@ int jsdr_bpsk_last_launch(jsdr_bpsk *h, int64_t *work_items, int64_t *workgroups
     JSDR_REQUIRE(h && work_items && workgroups, "jsdr_bpsk_last_launch: null argument");
     *work_items = h->last_fm_items;
     *workgroups = h->last_fm_grid;
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_fm_form(jsdr_bpsk *h, int *specialised, int *phase)
+{
+    JSDR_REQUIRE(h && specialised && phase, "jsdr_bpsk_fm_form: null argument");
+    *specialised = h->last_fm_phase >= 0;
+    *phase = h->last_fm_phase;
     return JSDR_OK;
 }
 
@@ -2323,9 +2338,11 @@ int jsdr_bpsk_profile_enable(jsdr_bpsk *h, int on)
 int jsdr_bpsk_table(int which, double *out, int cap)
 {
     JSDR_REQUIRE(out, "jsdr_bpsk_table: null argument");
-    const int n = which == 0 ? 27 : ((which == 1 || which == 2) ? 65 : 0);
+    const int n = which == 0 ? 27 : ((which == 1 || which == 2) ? 65 : ((which == 3 || which == 4) ? 256 : 0));
     JSDR_REQUIRE(n > 0 && cap >= n, "jsdr_bpsk_table: table %d needs room for %d values", which, n);
-    if (which == 0) {
+    if (which >= 3) {
+        for (int i = 0; i < 256; i++) out[i] = which == 3 ? table_cos(i) : table_sin(i);
+    } else if (which == 0) {
         for (int i = 0; i < 14; i++) out[i] = out[26 - i] = (double)h_ds_half[i];
     } else if (which == 1) {
         for (int i = 0; i < 33; i++) out[i] = out[64 - i] = (double)h_dm_half[i];

@@ -115,6 +115,8 @@ struct FmArgs {
     int *amax;                  // FAST: [S] running maximum of |int16 sample| per stream, float bits (never reset)
     int ntiles, nstreams;       // work items = ntiles x nstreams, stream-major; the grid strides over them
     int grid_limit;             // > 0: at most that many workgroups, striding over the work items (jsdr_bpsk_set_cu_share)
+    int trot;                   // >= 0: tper == 8 and entry e of tcs is phase e + trot of the 8-phase tuner, whose exact factors k_fm
+                                // has a form for (Schedule::trot, bpsk_tuner.h); -1: any other table, the generic form
 };
 
 // k_fm_prep: the stream's edge images for k_fm ...
@@ -206,8 +208,10 @@ int launch_hist_convert(int2 *hist, int nstreams, int to_float, int *bad, hipStr
 int launch_matched(const MatchedArgs &ma, int nstreams, hipStream_t st);
 int launch_dm_history(double2 *dm, long long dm_stride, long long nds, int nstreams, hipStream_t st);
 int launch_fm_prep(const EdgeArgs &ea, const HistArgs &ha, const ScatterArgs &sc, hipStream_t st);
-// *items, *grid: the work items (tiles x streams) of the launch and the workgroups that stride over them
-int launch_fm(const FmArgs &a, int decim, bool mix, bool dc, bool fast, int nstreams, hipStream_t st, long long *items, long long *grid);
+// *items, *grid: the work items (tiles x streams) of the launch and the workgroups that stride over them; *phase: the tuner phase
+// (0 .. 7) of tile 0's window sample 0 where the launch took the 8-phase tuner's form, -1 where it took the generic one
+int launch_fm(const FmArgs &a, int decim, bool mix, bool dc, bool fast, int nstreams, hipStream_t st, long long *items, long long *grid,
+              int *phase);
 int launch_fm_prep_f32(const EdgeF32Args &ea, const HistArgs &ha, hipStream_t st);
 int launch_fm_f32(const FmF32Args &a, int decim, bool mix, int nstreams, hipStream_t st, long long *items, long long *grid);
 const char *launch_tail(const TailArgs &ta, bool cert, hipStream_t st);

@@ -59,6 +59,8 @@ struct Schedule {
     int f0 = 1;        // sample 0 of the call is mixed ...
     long long n0 = 0;  // ... and so is every sample before n0, none from it on (f0 == 0: the other way round; n0 = L: no crossing)
     int tper = 0;      // > 0: the tuner index is periodic in the sample number with this period; 0: no period <= 256
+    int trot = -1;     // tper == 8 and the factors of tcs[0 .. 8) have the 8-phase tuner's exact classes (bpsk_tuner.h): entry e is
+                       // phase e + trot; -1: any other table
     long long nds = 0;
     std::vector<unsigned char> ktu;  // [26 history + L] tuner index (0 where the sample is passed through)
     std::vector<unsigned char> kvco; // [nds]

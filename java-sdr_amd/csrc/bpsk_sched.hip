@@ -116,6 +116,7 @@ void compute_schedule(Schedule &sc, const double *sincos)
     // the table repeats with is the one candidate; it counts if it holds over EVERY sample of the call, history included -- at
     // the start of a stream the 26 history samples are zeros, whose table entry does not matter.
     sc.tper = 0;
+    sc.trot = -1;
     if (!key.do_fft && sc.mix == 1) {
         const long long off = key.first ? SCHED_HIST : 0;  // k[i] is the index of sample n = i + off - 26
         const unsigned char *k = sc.ktu.data() + off;
@@ -132,6 +133,7 @@ void compute_schedule(Schedule &sc, const double *sincos)
                     const int kk = k[i];
                     sc.tcs[(size_t)e] = make_double2(sincos[kk], sincos[256 + kk]);
                 }
+                if (p == 8) sc.trot = tuner8_rotation(sc.tcs.data());  // (every entry beyond the first period repeats it)
             }
             break;
         }

@@ -11,6 +11,7 @@
 // unmixed (tuPhase <= 0, :388 / :395) -- entry 256 of the kernels' table is (1.0, 1.0).
 #pragma once
 #include "common.h"
+#include <string.h>
 
 namespace jsdr {
 
@@ -39,6 +40,37 @@ __host__ __device__ inline int tuner_step(double &tu, double inc)
 {
     tuner_advance(tu, inc);
     return tuner_k9(tu);
+}
+
+// ------------------------------------------------------------------------------------------- the 8-phase tuner's exact factors
+// At a tuning of an eighth of the rate (12 kHz / 96 kHz) the index walks 32, 64, .., 224, 0: phase ph <-> table index 32 ph.  Five
+// of the sixteen (phase, rail) factors are exact -- cos: 1.0 at phase 0, -1.0 at 4; sin: 0.0 at 0, 1.0 at 2, -1.0 at 6 -- and the
+// rest are whatever Math.cos / Math.sin gave (cos at 2 is 6.1e-17, not 0).  A product with +-1.0 is +-the sample and a product
+// with 0.0 of a FINITE sample is +-0, which k_fm's specialised form builds in (bpsk_fm.hip).  The host finds the classes by bit
+// pattern, from the table the schedule was built with; nothing here assumes what a libm returns.
+enum { TC_GEN = 0, TC_ONE = 1, TC_MONE = 2, TC_ZERO = 3 };
+constexpr int tuner8_class(int ph, int rail)  // rail 0: cos, 1: sin
+{
+    return rail == 0 ? ((ph & 7) == 0 ? TC_ONE : (ph & 7) == 4 ? TC_MONE : TC_GEN)
+                     : ((ph & 7) == 0 ? TC_ZERO : (ph & 7) == 2 ? TC_ONE : (ph & 7) == 6 ? TC_MONE : TC_GEN);
+}
+inline int tuner_factor_class(double v)
+{
+    unsigned long long b;
+    memcpy(&b, &v, sizeof(b));
+    return b == 0x3ff0000000000000ULL ? TC_ONE : b == 0xbff0000000000000ULL ? TC_MONE : (b << 1) == 0 ? TC_ZERO : TC_GEN;
+}
+// tab[0 .. 8): one period of (cos, sin) factors.  The rotation r (0 .. 7) with class(tab[e]) == tuner8_class(e + r) for both rails
+// of every entry -- the pattern has one ZERO, so there is at most one -- or -1 where the classes are not that pattern.
+inline int tuner8_rotation(const double2 *tab)
+{
+    for (int r = 0; r < 8; r++) {
+        bool ok = true;
+        for (int e = 0; e < 8 && ok; e++)
+            ok = tuner_factor_class(tab[e].x) == tuner8_class(e + r, 0) && tuner_factor_class(tab[e].y) == tuner8_class(e + r, 1);
+        if (ok) return r;
+    }
+    return -1;
 }
 
 // one decimated sample of the VCO: vcoPhase += VCO_PHASE_INC; if (vcoPhase > 2 pi) vcoPhase -= 2 pi; the table index of the
