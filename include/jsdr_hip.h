@@ -345,6 +345,40 @@ int jsdr_bpsk_get_stream_tuning(jsdr_bpsk *h, int stream, double *tuning_hz);
  * tu_inc -- k9_out[i]: the table index of sample i, 0 .. 255, or 256 where the sample passes through unmixed; *tu_end: tuPhase
  * after the last one (may be NULL) */
 int jsdr_bpsk_tuner_walk_host(double tu0, double tu_inc, int64_t n, uint16_t *k9_out, double *tu_end);
+/* Tuning plans: retunes INSIDE the next batch call of a tuned handle, each stream at samples of its own -- what two thousand
+ * signals on two thousand Doppler curves need, which do not retune at the same instants and not only where a call ends.
+ *   Entry i = (stream[i], at_sample[i], tuning_hz[i]): from sample at_sample of the NEXT batch call on, that stream has
+ *     tuning = tuning_hz and tuPhaseInc = 2 pi tuning_hz / rate; the tuner's advance of sample at_sample is the first at the new
+ *     increment -- exactly what cutting the call in front of that sample and changing the tuning between the two pieces does.
+ *     The change is the configuration path's, setup (:192-209), as jsdr_bpsk_reconfigure states it: tuPhase, all histories, the bit
+ *     clock, the FEC register, the counters and dmMaxCorr carry on.  dmMaxCorr is NOT zeroed: a plan is not the button, and the
+ *     bookkeeping of the sync stage runs over the call's bits and has no sample positions to reset at.
+ *   Result: stream s is bit-identical to a one-stream handle of jsdr_bpsk_create fed the same samples in pieces cut at stream s's
+ *     own entries, with jsdr_bpsk_reconfigure(tuning, 0, 0) between the pieces: bits, FEC results, counters, state, trace.
+ *   Order: entries go by stream, within a stream by strictly ascending at_sample >= 0; any number per stream, consecutive samples
+ *     included; streams without entries are ordinary streams of that call.  Tunings as for jsdr_bpsk_create_tuned.
+ *   Lifetime: one-shot.  The next batch call that succeeds (batch_i16 or batch_f32) consumes the plan, and the call after it runs
+ *     with the tunings the plan left: get_stream_tuning, get_control (stream 0) and a saved record show each stream's last entry,
+ *     state double 0 is the stream's own tuPhase, and the last 26 samples keep the factors they were mixed with.  A later plan
+ *     replaces a pending one; n = 0 clears it.  set_stream_tuning(s), set_tuning, reconfigure and jsdr_bpsk_restore between the
+ *     plan and the call act before sample 0, as they do without a plan; the entries come after them in sample order.  A plan is
+ *     not state: jsdr_bpsk_save does not carry it (the blob format stays at version 1).
+ *   On the device: a planned call runs the planned forms of the walk and of the front end ("k_front_pst_plan" from
+ *     jsdr_bpsk_front_kernel; the profile slots are the same two); a call without a plan runs exactly the kernels it ran before.
+ *     The plan is copied to the device when it is given (16 bytes an entry); the first plan adds 4 bytes per 64 samples and
+ *     stream of max_batch_samples to the handle.
+ * JSDR_ERR, the handle AND a pending plan unchanged, each checked before any device work: a handle that is null or not from
+ * jsdr_bpsk_create_tuned, n < 0, a null array with n > 0, a stream out of range, entries out of order or duplicated, a negative
+ * at_sample, a tuning that is not finite or >= rate.  A batch call whose nsamples does not exceed every pending at_sample is
+ * refused, the handle unchanged, and the plan stays pending.  planned_tunings: the entries pending (0 after the call that took
+ * them).  Not built: plans on ordinary or channel handles, JNI / Java classes, jsdr_group_*, the FAST variant, FFT-acquire. */
+int jsdr_bpsk_plan_stream_tunings(jsdr_bpsk *h, const int32_t *stream, const int64_t *at_sample, const double *tuning_hz, int64_t n);
+int jsdr_bpsk_planned_tunings(jsdr_bpsk *h, int64_t *n);
+/* host only, no device (CPU tests): jsdr_bpsk_tuner_walk_host with a plan for one stream -- from sample at_sample[e] on
+ * tuPhaseInc is inc_at[e], e = 0 .. nev - 1, at_sample >= 0 and strictly ascending (entries at or behind n are not reached);
+ * nev = 0 with null arrays is jsdr_bpsk_tuner_walk_host */
+int jsdr_bpsk_tuner_walk_plan_host(double tu0, double tu_inc, int64_t n, const int64_t *at_sample, const double *inc_at, int64_t nev,
+                                   uint16_t *k9_out, double *tu_end);
 /* Checkpoints: the state of a range of streams out of a handle and into one -- across a restart, a library upgrade, another
  * machine, or between handles (a split is two saves with ranges, a merge two restores at offsets).  A blob is self-contained,
  * versioned (format 1) and position-independent: little-endian fixed-width fields, a 192-byte header with the sizes and a

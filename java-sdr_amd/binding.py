@@ -682,6 +682,24 @@ class BpskTuned(Bpsk):
         _check(lib().jsdr_bpsk_get_stream_tuning(self.h, int(stream), C.byref(t)), "jsdr_bpsk_get_stream_tuning")
         return t.value
 
+    def plan_tunings(self, streams, at_samples, tunings):
+        """retunes inside the next batch call (jsdr_bpsk_plan_stream_tunings): stream streams[i] takes tunings[i] from sample
+        at_samples[i] of that call on; entries by stream, then by ascending sample.  No entries: a pending plan is cleared."""
+        st = np.ascontiguousarray(streams, np.int32)
+        at = np.ascontiguousarray(at_samples, np.int64)
+        tu = np.ascontiguousarray(tunings, np.float64)
+        if not (st.ndim == at.ndim == tu.ndim == 1 and st.size == at.size == tu.size):
+            raise ValueError("plan_tunings: streams, at_samples and tunings are three lists of one length")
+        n = st.size
+        _check(lib().jsdr_bpsk_plan_stream_tunings(self.h, _addr(st) if n else None, _addr(at) if n else None, _addr(tu) if n else None,
+                                                   C.c_int64(n)), "jsdr_bpsk_plan_stream_tunings")
+
+    def planned(self):
+        """entries of a tuning plan waiting for the next batch call"""
+        n = C.c_int64()
+        _check(lib().jsdr_bpsk_planned_tunings(self.h, C.byref(n)), "jsdr_bpsk_planned_tunings")
+        return n.value
+
 
 class BpskBlobInfo(C.Structure):
     _fields_ = [("version", C.c_int32), ("kind", C.c_int32), ("rate", C.c_int32), ("nsamples_per_frame", C.c_int32),
@@ -705,6 +723,21 @@ def tuner_walk_host(tu0, inc, n):
     end = C.c_double()
     _check(lib().jsdr_bpsk_tuner_walk_host(C.c_double(tu0), C.c_double(inc), C.c_int64(int(n)), _addr(k9), C.byref(end)),
            "jsdr_bpsk_tuner_walk_host")
+    return k9[:int(n)], end.value
+
+
+def tuner_walk_plan_host(tu0, inc, n, at_samples=(), incs=()):
+    """tuner_walk_host with a plan for one stream (no device): from sample at_samples[e] on the increment is incs[e]
+    -> (9-bit table index per sample, tuPhase at the end)"""
+    at = np.ascontiguousarray(at_samples, np.int64)
+    ia = np.ascontiguousarray(incs, np.float64)
+    if at.size != ia.size:
+        raise ValueError("tuner_walk_plan_host: one increment per position")
+    k9 = np.empty(max(int(n), 1), np.uint16)
+    end = C.c_double()
+    _check(lib().jsdr_bpsk_tuner_walk_plan_host(C.c_double(tu0), C.c_double(inc), C.c_int64(int(n)), _addr(at) if at.size else None,
+                                                _addr(ia) if ia.size else None, C.c_int64(at.size), _addr(k9), C.byref(end)),
+           "jsdr_bpsk_tuner_walk_plan_host")
     return k9[:int(n)], end.value
 
 

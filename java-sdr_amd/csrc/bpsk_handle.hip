@@ -234,6 +234,15 @@ struct jsdr_bpsk {
     DevBuf<unsigned short> pst_kh[2];  // [S][32] the 9-bit indices of the 26 samples before the next call, double-buffered like hist_in
     int pst_kh_cur = 0;
     DevBuf<int> pst_ids;               // [S] the streams an action zeroes dmMaxCorr in (k_reset_maxcorr_list)
+    // a tuning plan (jsdr_bpsk_plan_stream_tunings): retunes inside the next call, copied to the device when it is given.  The
+    // call that takes it clears pst_plan_n; the device copy stays until the next plan replaces it, a plan of 0 entries or destroy.
+    long long pst_plan_n = 0;                            // entries pending
+    long long pst_plan_max_at = -1;                      // the largest at_sample among them
+    std::vector<std::pair<int, double>> pst_plan_last;   // (stream, the tuning of its last entry): pst_tuning after the call
+    DevBuf<long long> pst_plan_off, pst_plan_pos;        // [S + 1], [n]  (PstPlanArgs)
+    DevBuf<double> pst_plan_inc;                         // [n]
+    DevBuf<double> pst_inc0;                             // [S], with the first plan
+    DevBuf<int> pst_ckpt_e;                              // [S][pst_ckpt_stride], with the first plan
     // checkpoints (jsdr_bpsk_save / jsdr_bpsk_restore): the records' staging image, allocated at the first use
     DevBuf<unsigned char> state_img;
     bool restored = false;                   // a blob has been restored: the handle is no longer free to adopt a shared block
@@ -1127,6 +1136,9 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
     JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nstreams == 1 || stride_i16 >= 2 * L),
                  "bpsk: stream stride %lld too small for %lld samples", stride_i16, L);
     // the previous call may have come through the other input form (before anything moves on: the conversion can refuse)
+    const bool planned = h->pst_plan_n > 0;
+    JSDR_REQUIRE(!planned || L > h->pst_plan_max_at, "bpsk: the pending tuning plan has an entry at sample %lld, the call has %lld samples; the "
+                 "handle is unchanged and the plan stays pending", h->pst_plan_max_at, L);
     if (hist_form(h, rawf_dev != nullptr, h->nstreams, st) != JSDR_OK) return JSDR_ERR;
     const int S = h->nstreams;
     const int first_out = h->decim - 1 - h->dsCnt;
@@ -1144,6 +1156,9 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
     const int *raw = reinterpret_cast<const int *>(raw_dev);
     const float2 *rawf = reinterpret_cast<const float2 *>(rawf_dev);
     const long long stride_pairs = stride_i16 / 2;
+    // the plan was copied when it was given: the planned forms of the two kernels read it where it lies
+    const PstPlanArgs pa = {h->pst_plan_off.p, h->pst_plan_pos.p, h->pst_plan_inc.p, h->pst_inc0.p, h->pst_ckpt_e.p, h->pst_inc.p};
+    const PstPlanArgs *plan = planned ? &pa : nullptr;
     {
         TunerWalkArgs wa;
         wa.tu = h->pst_tu.p;
@@ -1155,7 +1170,7 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
         wa.kh_new = h->pst_kh[h->pst_kh_cur ^ 1].p;
         wa.nstreams = S;
         ProfScope ps(h, PK_TWALK, st);
-        if (launch_tuner_walk(wa, st) != JSDR_OK) return JSDR_ERR;
+        if (launch_tuner_walk(wa, plan, st) != JSDR_OK) return JSDR_ERR;
     }
     if (nds > 0) {
         PstFrontArgs fa;
@@ -1178,15 +1193,22 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
         fa.first_out = first_out;
         fa.decim = h->decim;
         ProfScope ps(h, PK_FRONT, st);
-        h->front_name = "k_front_pst";
-        if (launch_front_pst(fa, S, rawf != nullptr, st) != JSDR_OK) return JSDR_ERR;
+        h->front_name = planned ? "k_front_pst_plan" : "k_front_pst";
+        if (launch_front_pst(fa, S, rawf != nullptr, plan, st) != JSDR_OK) return JSDR_ERR;
     }
     h->pst_kh_cur ^= 1;
     if (run_hist_in(h, hist_args(h, raw, rawf, stride_pairs, L, ic, qc, S), st) != JSDR_OK) return JSDR_ERR;
     const int yb = h->y_cur;
     if (wait_tail(h, yb, st) != JSDR_OK) return JSDR_ERR;
     if (nds > 0 && run_matched(h, yb, nds, g_first, st) != JSDR_OK) return JSDR_ERR;
-    return finish_call(h, yb, L, nds, g_first, first_out, ic, qc, raw, stride_pairs, kvco_p, tcs_p, st);
+    if (finish_call(h, yb, L, nds, g_first, first_out, ic, qc, raw, stride_pairs, kvco_p, tcs_p, st) != JSDR_OK) return JSDR_ERR;
+    if (planned) {  // one-shot: the streams it named stand at their last entries (the walk left their tuPhaseInc on the device)
+        for (const auto &sl : h->pst_plan_last) h->pst_tuning[(size_t)sl.first] = sl.second;
+        h->pst_plan_n = 0;
+        h->pst_plan_max_at = -1;
+        h->pst_plan_last.clear();
+    }
+    return JSDR_OK;
 }
 
 static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, long long stride_i16, long long L,
@@ -2908,6 +2930,113 @@ int jsdr_bpsk_get_stream_tuning(jsdr_bpsk *h, int stream, double *tuning_hz)
     JSDR_REQUIRE(stream >= 0 && stream < h->nstreams, "jsdr_bpsk_get_stream_tuning: stream %d out of range (the handle has %d)", stream,
                  h->nstreams);
     *tuning_hz = h->pst_tuning[(size_t)stream];
+    return JSDR_OK;
+}
+
+// A tuning plan: entry i says "from sample at_sample[i] of the NEXT batch call on, stream stream[i] has tuning tuning_hz[i]" --
+// setup()'s tuning change (:192-209, what jsdr_bpsk_reconfigure applies between calls) at a sample of the stream's own.  Every
+// check comes before any device work; then the handle's pending work is waited for (the call before may still read the plan it
+// took) and the plan goes to the device in buffers of its own, which take the old ones' place only once all of it is there.
+int jsdr_bpsk_plan_stream_tunings(jsdr_bpsk *h, const int32_t *stream, const int64_t *at_sample, const double *tuning_hz, int64_t n)
+{
+    static const char *who = "jsdr_bpsk_plan_stream_tunings";
+    JSDR_REQUIRE(h, "%s: null handle", who);
+    JSDR_REQUIRE(h->pst, "%s: the handle was not made by jsdr_bpsk_create_tuned (its streams share one tuning: jsdr_bpsk_reconfigure between "
+                 "calls); the handle is unchanged", who);
+    JSDR_REQUIRE(n >= 0, "%s: %lld entries; the handle and its pending plan are unchanged", who, (long long)n);
+    JSDR_REQUIRE(n == 0 || (stream && at_sample && tuning_hz), "%s: null array with %lld entries; the handle and its pending plan are unchanged",
+                 who, (long long)n);
+    const int S = h->nstreams;
+    for (int64_t i = 0; i < n; i++) {
+        JSDR_REQUIRE(stream[i] >= 0 && stream[i] < S, "%s: entry %lld: stream %d out of range (the handle has %d); the handle and its pending "
+                     "plan are unchanged", who, (long long)i, (int)stream[i], S);
+        JSDR_REQUIRE(at_sample[i] >= 0, "%s: entry %lld: at_sample %lld is negative; the handle and its pending plan are unchanged", who,
+                     (long long)i, (long long)at_sample[i]);
+        JSDR_REQUIRE(i == 0 || stream[i] > stream[i - 1] || (stream[i] == stream[i - 1] && at_sample[i] > at_sample[i - 1]),
+                     "%s: entry %lld (stream %d, sample %lld) is out of order: entries go by stream, and within a stream by strictly ascending "
+                     "at_sample; the handle and its pending plan are unchanged", who, (long long)i, (int)stream[i], (long long)at_sample[i]);
+        JSDR_REQUIRE(std::isfinite(tuning_hz[i]) && tuning_hz[i] < (double)h->rate, "%s: entry %lld: tuning %g Hz of stream %d is not a finite "
+                     "value below the rate (%d Hz); the handle and its pending plan are unchanged", who, (long long)i, tuning_hz[i],
+                     (int)stream[i], h->rate);
+    }
+    std::vector<long long> off((size_t)S + 1, 0), pos((size_t)n);
+    std::vector<double> inc((size_t)n);
+    std::vector<std::pair<int, double>> last;
+    for (int64_t i = 0; i < n; i++) {
+        off[(size_t)stream[i] + 1]++;
+        pos[(size_t)i] = at_sample[i];
+        inc[(size_t)i] = tuner_inc(tuning_hz[i], h->rate);  // :196, the double pst_apply writes
+        if (!last.empty() && last.back().first == stream[i])
+            last.back().second = tuning_hz[i];
+        else
+            last.emplace_back((int)stream[i], tuning_hz[i]);
+    }
+    for (int s = 0; s < S; s++) {
+        JSDR_REQUIRE(off[(size_t)s + 1] <= 0x7fffffffLL, "%s: %lld entries for stream %d; the handle and its pending plan are unchanged", who,
+                     off[(size_t)s + 1], s);
+        off[(size_t)s + 1] += off[(size_t)s];
+    }
+    if (sync_last(h) != JSDR_OK) return JSDR_ERR;
+    if (n == 0) {  // no plan: the next call is an ordinary one
+        h->pst_plan_off.release();
+        h->pst_plan_pos.release();
+        h->pst_plan_inc.release();
+        h->pst_plan_n = 0;
+        h->pst_plan_max_at = -1;
+        h->pst_plan_last.clear();
+        return JSDR_OK;
+    }
+    DevBuf<long long> d_off, d_pos;
+    DevBuf<double> d_inc, d_inc0;
+    DevBuf<int> d_cke;
+    const bool first = !h->pst_inc0.p;  // (what the planned walk leaves for the planned front end: with the first plan)
+    if (d_off.alloc(off.size()) != JSDR_OK || d_pos.alloc(pos.size()) != JSDR_OK || d_inc.alloc(inc.size()) != JSDR_OK) return JSDR_ERR;
+    if (first && (d_inc0.alloc((size_t)S) != JSDR_OK || d_cke.alloc((size_t)S * (size_t)h->pst_ckpt_stride) != JSDR_OK)) return JSDR_ERR;
+    JSDR_HIP_TRY(hipMemcpy(d_off.p, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
+    JSDR_HIP_TRY(hipMemcpy(d_pos.p, pos.data(), sizeof(long long) * pos.size(), hipMemcpyHostToDevice));
+    JSDR_HIP_TRY(hipMemcpy(d_inc.p, inc.data(), sizeof(double) * inc.size(), hipMemcpyHostToDevice));
+    std::swap(h->pst_plan_off, d_off);  // (the old plan's buffers go with the locals)
+    std::swap(h->pst_plan_pos, d_pos);
+    std::swap(h->pst_plan_inc, d_inc);
+    if (first) {
+        std::swap(h->pst_inc0, d_inc0);
+        std::swap(h->pst_ckpt_e, d_cke);
+    }
+    h->pst_plan_n = n;
+    h->pst_plan_max_at = -1;
+    for (int64_t i = 0; i < n; i++)
+        if (at_sample[i] > h->pst_plan_max_at) h->pst_plan_max_at = at_sample[i];
+    h->pst_plan_last.swap(last);
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_planned_tunings(jsdr_bpsk *h, int64_t *n)
+{
+    JSDR_REQUIRE(h && n, "jsdr_bpsk_planned_tunings: null argument");
+    JSDR_REQUIRE(h->pst, "jsdr_bpsk_planned_tunings: the handle was not made by jsdr_bpsk_create_tuned");
+    *n = h->pst_plan_n;
+    return JSDR_OK;
+}
+
+// host only, no device: jsdr_bpsk_tuner_walk_host with a plan for one stream -- from sample at_sample[e] on the increment is
+// inc_at[e] (the advance of that sample is the first at it); entries at or behind sample n are not reached
+int jsdr_bpsk_tuner_walk_plan_host(double tu0, double tu_inc, int64_t n, const int64_t *at_sample, const double *inc_at, int64_t nev,
+                                   uint16_t *k9_out, double *tu_end)
+{
+    static const char *who = "jsdr_bpsk_tuner_walk_plan_host";
+    JSDR_REQUIRE(n >= 0 && (k9_out || n == 0), "%s: %lld samples, index buffer %s", who, (long long)n, k9_out ? "given" : "null");
+    JSDR_REQUIRE(nev >= 0 && (nev == 0 || (at_sample && inc_at)), "%s: %lld entries, arrays %s", who, (long long)nev,
+                 at_sample && inc_at ? "given" : "null");
+    for (int64_t e = 0; e < nev; e++)
+        JSDR_REQUIRE(at_sample[e] >= 0 && (e == 0 || at_sample[e] > at_sample[e - 1]), "%s: entry %lld (sample %lld) is negative or out of order",
+                     who, (long long)e, (long long)at_sample[e]);
+    double tu = tu0, inc = tu_inc;
+    int64_t e = 0;
+    for (int64_t i = 0; i < n; i++) {
+        if (e < nev && at_sample[e] == i) inc = inc_at[e++];
+        k9_out[i] = (uint16_t)tuner_step(tu, inc);
+    }
+    if (tu_end) *tu_end = tu;
     return JSDR_OK;
 }
 

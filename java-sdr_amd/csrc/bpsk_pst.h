@@ -41,8 +41,21 @@ struct PstFrontArgs {
     int nout;                      // outputs per workgroup (set by the launcher)
 };
 
-int launch_tuner_walk(const TunerWalkArgs &a, hipStream_t st);
-int launch_front_pst(const PstFrontArgs &a, int nstreams, bool f32in, hipStream_t st);
+// A tuning plan on the device (jsdr_bpsk_plan_stream_tunings), as the planned forms k_tuner_walk_plan / k_front_pst_plan read it:
+// stream s's entries are off[s] .. off[s + 1] - 1; entry e says "from sample pos[e] of the call on, tuPhaseInc = inc[e]" (the
+// advance of sample pos[e] is the first at it); pos ascends strictly within a stream and every pos lies inside the call.
+struct PstPlanArgs {
+    const long long *off;  // [S + 1]
+    const long long *pos;  // [off[S]]
+    const double *inc;     // [off[S]] 2 pi tuning / rate, the double the host writes for a tuning set between calls
+    double *inc0;          // [S] the walk leaves tuPhaseInc as the stream came into the call (before its first entry)
+    int *ckpt_e;           // [S][ckpt_stride] the walk leaves the number of the stream's entries before sample c * PST_C
+    double *inc_out;       // [S] the walk leaves tuPhaseInc as the stream goes out of the call (the handle's tuPhaseInc array)
+};
+
+// plan: null for a call without one (the kernels of such a call do not know of plans)
+int launch_tuner_walk(const TunerWalkArgs &a, const PstPlanArgs *plan, hipStream_t st);
+int launch_front_pst(const PstFrontArgs &a, int nstreams, bool f32in, const PstPlanArgs *plan, hipStream_t st);
 // dmMaxCorr = 0 (:190) in the n streams ids[] names
 int launch_reset_maxcorr_list(TailState *st, const int *ids, int n, hipStream_t stream);
 

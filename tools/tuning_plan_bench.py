@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""What a tuning plan costs (jsdr_bpsk_plan_stream_tunings: retunes inside a batch call of a tuned handle); prints one JSON line.
+
+The shape of tools/stream_tuning_bench.py: 2048 streams x 2^20 samples a call at 96 kHz, distinct non-periodic tunings, wall time
+of a call plus a sync of the handle, median of --steps after --warmup, all in one run:
+
+  (d) the tuned call without a plan (the kernels a plan does not touch)
+  (f) a planned call: every stream one entry every 38 400 samples (27 entries, +10 Hz each), staggered by stream so that no two
+      streams of a wave retune at the same sample.  f_plan_ms: giving the plan (validation, copy to the device), not in f_call_ms
+  (g) the same retunes the only way there is without a plan: the call cut into 28 pieces with set_stream_tunings between them
+      (which lines the instants up; the plan does not need that)
+  and, from the profile slots of one more call each, k_tuner_walk and k_front for (d) and (f)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import java_sdr_amd as J  # noqa: E402
+from stream_tuning_bench import RATE, distinct, fill, slots  # noqa: E402
+
+EVERY = 38400
+
+
+def median_ms(fn, warmup, steps, before=None):
+    ts = []
+    for k in range(warmup + steps):
+        if before:
+            before()
+        t0 = time.perf_counter()
+        fn()
+        if k >= warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=2048)
+    ap.add_argument("--samples", type=int, default=1 << 20)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3)
+    a = ap.parse_args()
+    N, L = a.streams, a.samples
+    tun = distinct(N)
+    nent = (L - 1) // EVERY
+    room = L - nent * EVERY  # the stagger stays inside the call
+    stagger = [(5 * s) % max(room, 1) for s in range(N)]
+    st = np.repeat(np.arange(N, dtype=np.int32), nent)
+    at = np.array([k * EVERY + stagger[s] for s in range(N) for k in range(1, nent + 1)], np.int64)
+    tu = np.array([tun[s] + 10.0 * k for s in range(N) for k in range(1, nent + 1)], np.float64)
+    out = {"streams": N, "samples_per_call": L, "rate": RATE, "entries_per_stream": nent, "entries": int(st.size)}
+    buf = fill(N, L)
+    d = J.BpskTuned(RATE, 8192, tun, max_batch_samples=L)
+
+    def call():
+        d.batch_i16(buf.ptr, 2 * L, L)
+        d.sync()
+
+    def reset():
+        d.set_stream_tunings(0, tun)
+
+    out["d_unplanned_ms"] = round(median_ms(call, a.warmup, a.steps, reset), 3)
+    out["d_front"] = d.front_kernel_name()
+    reset()
+    out["d_walk_ms"], out["d_front_ms"] = slots(d, buf, L)
+
+    def give():
+        reset()
+        d.plan_tunings(st, at, tu)
+
+    out["f_planned_ms"] = round(median_ms(call, a.warmup, a.steps, give), 3)
+    out["f_front"] = d.front_kernel_name()
+    reset()
+    out["f_plan_ms"] = round(median_ms(lambda: d.plan_tunings(st, at, tu), 0, a.steps), 3)
+    out["f_walk_ms"], out["f_front_ms"] = slots(d, buf, L)
+    assert d.planned() == 0 and d.stream_tuning(N - 1) == tun[N - 1] + 10.0 * nent
+
+    def pieces():
+        for k in range(nent + 1):
+            if k:
+                d.set_stream_tunings(0, [t + 10.0 * k for t in tun])
+            a0, a1 = k * EVERY, (L if k == nent else (k + 1) * EVERY)
+            d.batch_i16(buf.ptr + 4 * a0, 2 * L, a1 - a0)
+        d.sync()
+
+    out["g_pieces_ms"] = round(median_ms(pieces, a.warmup, a.steps, reset), 3)
+    out["g_pieces"] = nent + 1
+    out["f_over_d"] = round(out["f_planned_ms"] / out["d_unplanned_ms"], 3)
+    out["g_over_d"] = round(out["g_pieces_ms"] / out["d_unplanned_ms"], 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
