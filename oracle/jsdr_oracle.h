@@ -129,6 +129,8 @@ void jo_bpsk_decision_margins(const jo_bpsk_t *d, double *out /* [8] */);
 void jo_bpsk_set_sincos(jo_bpsk_t *d, const double sin_tab[256], const double cos_tab[256]);
 void jo_bpsk_declog_enable(jo_bpsk_t *d, int64_t cap);
 int64_t jo_bpsk_declog(const jo_bpsk_t *d, int which, double *out, int64_t cap);
+/* the detector instants with their place: g[n] = the 9600 Hz sample number of decision n, out = {di, energy2} as above */
+int64_t jo_bpsk_declog_pos(const jo_bpsk_t *d, int64_t *g, double *out, int64_t cap);
 int64_t jo_bpsk_trace(const jo_bpsk_t *d, double *out, int64_t cap_pairs);
 /* optional trace of down-sampler outputs (after x HOWARD_FUDGE_FACTOR)           */
 int64_t jo_bpsk_trace_ds(const jo_bpsk_t *d, double *out, int64_t cap_pairs);

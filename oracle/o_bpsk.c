@@ -171,6 +171,7 @@ struct jo_bpsk {
     /* round 6: a plain log of the quantities RxDemodulate decides on (both modes; instruments only): per detector instant
      * {di, energy2}, per bit clock {dmEnergy[dmNewPeak] - runner-up, dmNewPeak} -- for the table-perturbation measurement */
     double *dlog_det, *dlog_peak;
+    int64_t *dlog_g;        /* the 9600 Hz sample number (cntDS) of every detector instant of dlog_det */
     int64_t ndet, npeak, capdlog;
 };
 
@@ -203,6 +204,7 @@ void jo_bpsk_free(jo_bpsk_t *d)
     free(d->probe);
     free(d->dlog_det);
     free(d->dlog_peak);
+    free(d->dlog_g);
     free(d);
 }
 
@@ -281,6 +283,7 @@ static void RxDemodulate(jo_bpsk_t *d, double i, double q)
         if (d->dlog_det && d->ndet < d->capdlog) {
             d->dlog_det[2 * d->ndet] = di;
             d->dlog_det[2 * d->ndet + 1] = d->energy2;
+            d->dlog_g[d->ndet] = d->cntDS;
             d->ndet++;
         }
         if (d->probe) {
@@ -592,6 +595,8 @@ void jo_bpsk_declog_enable(jo_bpsk_t *d, int64_t cap)
 {
     free(d->dlog_det);
     free(d->dlog_peak);
+    free(d->dlog_g);
+    d->dlog_g = (int64_t *)calloc((size_t)cap, sizeof(int64_t));
     d->dlog_det = (double *)calloc((size_t)cap * 2, sizeof(double));
     d->dlog_peak = (double *)calloc((size_t)cap * 2, sizeof(double));
     d->capdlog = cap;
@@ -605,6 +610,18 @@ int64_t jo_bpsk_declog(const jo_bpsk_t *d, int which, double *out, int64_t cap)
     const int64_t m = n < cap ? n : cap;
     if (out && src && m > 0) memcpy(out, src, sizeof(double) * 2 * (size_t)m);
     return n;
+}
+
+/* per detector instant: g[n] = the 9600 Hz sample number of the decision (0-based count of RxDemodulate calls before it),
+ * out[2n..2n+1] = (di, energy2) as jo_bpsk_declog(d, 0, ..) gives them */
+int64_t jo_bpsk_declog_pos(const jo_bpsk_t *d, int64_t *g, double *out, int64_t cap)
+{
+    const int64_t m = d->ndet < cap ? d->ndet : cap;
+    if (d->dlog_det && m > 0) {
+        if (g) memcpy(g, d->dlog_g, sizeof(int64_t) * (size_t)m);
+        if (out) memcpy(out, d->dlog_det, sizeof(double) * 2 * (size_t)m);
+    }
+    return d->ndet;
 }
 
 void jo_bpsk_fft_perturb(jo_bpsk_t *d, double scale, uint64_t seed)

@@ -72,6 +72,8 @@ def _proto(L):
     L.jo_bpsk_trace.argtypes = [vp, vp, C.c_int64]
     L.jo_bpsk_trace_ds.restype = C.c_int64
     L.jo_bpsk_trace_ds.argtypes = [vp, vp, C.c_int64]
+    L.jo_bpsk_declog_pos.restype = C.c_int64
+    L.jo_bpsk_declog_pos.argtypes = [vp, vp, vp, C.c_int64]
     L.jo_bpsk_state.argtypes = [vp, vp]
     L.jo_bpsk_istate.argtypes = [vp, vp]
     L.jo_bpsk_table.argtypes = [C.c_int, vp, C.c_int]
@@ -436,6 +438,15 @@ class Bpsk:
         out = np.empty((max(n, 1), 2), np.float64)
         lib().jo_bpsk_declog(self.h, which, ptr(out), n)
         return out[:n]
+
+    def declog_pos(self):
+        """(declog_enable first) per detector instant: g [n] int64, the 9600 Hz sample number of the decision, and [n, 2] (di, energy2)"""
+        f = lib().jo_bpsk_declog_pos
+        n = f(self.h, None, None, 0)
+        g = np.empty(max(n, 1), np.int64)
+        out = np.empty((max(n, 1), 2), np.float64)
+        f(self.h, ptr(g), ptr(out), n)
+        return g[:n], out[:n]
 
     def fft_perturb(self, scale, seed):
         lib().jo_bpsk_fft_perturb.argtypes = [C.c_void_p, C.c_double, C.c_uint64]
