@@ -731,7 +731,13 @@ def test_bpsk_any_audio_rate_takes_the_generic_front_end(rate, tuning):
 def test_bpsk_suite_with_the_eight_streams_per_wave_tail():
     """k_tail8 (eight streams per wave) serves handles of 2048 streams and more; the parity tests use a few streams.  The same
     tests once more in a child process with JSDR_TAIL8=2, which makes every handle take k_tail8 (ragged calls, surplus lane
-    groups shadowing the last stream, acquisition and fades through the general path, FFT-acquire frame seams)."""
+    groups shadowing the last stream, FFT-acquire frame seams).  What its tune-mode inputs do to the peak machine, counted on the
+    oracle (peak_walk.census): the synthetic signals start symbol 0 at sample 0, so the locked path runs at v = 4 at 96 kHz, and at 3,
+    5 or 6 at the other rates and tunings -- never at 0, 1, 2 or 7; the signals hold a handful of moves during acquisition each, and
+    the uniform-noise streams beside them 51 of the 56 moves dmPeakPos -> dmPeakPos' between them (1 -> 5, 1 -> 6, 2 -> 6, 4 -> 1 and
+    6 -> 1 never occur), wherever the calls' seams happen to fall; these handles hold two streams, so six of a wave's eight lane
+    groups are shadows.  test_gpu_peak_walk.py has the counted cases: every locked position in one wave, every move, call seams
+    inside the bit period of a hand-over of every move, results compared after every call."""
     if os.environ.get("JSDR_TAIL8") == "2":
         return
     import subprocess
