@@ -379,6 +379,47 @@ int jsdr_bpsk_planned_tunings(jsdr_bpsk *h, int64_t *n);
  * nev = 0 with null arrays is jsdr_bpsk_tuner_walk_host */
 int jsdr_bpsk_tuner_walk_plan_host(double tu0, double tu_inc, int64_t n, const int64_t *at_sample, const double *inc_at, int64_t nev,
                                    uint16_t *k9_out, double *tu_end);
+/* Ramp plans: a tuning plan whose entries move -- one entry follows a stretch of a Doppler curve where steps need one entry per
+ * tolerated error.  Everything said of tuning plans above holds (tuned handles only, one-shot, order, replacement, n = 0, what
+ * acts before sample 0, refusals, the two profile slots); an entry gains a slope.
+ *   Entry i = (stream[i], at_sample[i], tuning_hz[i], slope_hz_per_sample[i]), in effect from sample at_sample of the NEXT batch
+ *     call until the stream's next entry or the call's last sample.  Sample n of that span has
+ *         k        = n - at_sample                      (exact in a double)
+ *         tuning_n = tuning_hz + (double)k * slope      one product, one sum, each rounded by itself
+ *         inc_n    = 2 pi tuning_n / rate               left to right, as tuPhaseInc always is
+ *     and the tuner's advance of sample n uses inc_n.  That is, by definition, a jsdr_bpsk_plan_stream_tunings plan with one entry
+ *     per sample n at tuning_n computed in doubles by those two operations -- so stream s is bit-identical to a one-stream handle
+ *     of jsdr_bpsk_create fed the samples one at a time with jsdr_bpsk_reconfigure(tuning_n, 0, 0) in front of each: bits, FEC
+ *     results, counters, state, decoded[], trace.  dmMaxCorr is not zeroed.
+ *   Zero slope: the entry takes tuning_hz itself, with no arithmetic, and means what it means in jsdr_bpsk_plan_stream_tunings.  A
+ *     plan whose slopes are ALL zero is a step plan and runs as one ("k_front_pst_plan").  Before its first entry a stream runs at
+ *     the increment it came into the call with, which is not recomputed.
+ *   After the call: a stream whose last entry is a ramp holds the tuning of the call's LAST sample, tuning_hz +
+ *     (double)(nsamples - 1 - at_sample) * slope, computed by the host at the call by the same two operations: get_stream_tuning,
+ *     get_control (stream 0) and a saved record show it, and the device's tuPhaseInc is 2 pi / rate of exactly that double (what
+ *     jsdr_bpsk_restore checks).  A ramp does not outlive its call.  To continue it, give the next call an entry at sample 0 with
+ *     tuning_hz' = tuning_hz + (double)(nsamples - at_sample) * slope and the same slope (k restarts at 0 there: the curve is the
+ *     same line, its roundings are the new entry's).
+ *   Tunings: every tuning_n must be finite and below the rate.  They are monotone in k, so the two ends of a span decide: the one
+ *     in front of the stream's next entry is checked when the plan is given; the one at the call's last sample is checked by the
+ *     call, with "every at_sample inside the call" -- such a call is refused, the handle unchanged, and the plan stays pending.
+ *     A slope that is not finite is refused when the plan is given.  Every refusal names the entry, leaves the handle AND a
+ *     pending plan unchanged and comes before any device work.
+ *   On the device: a call with a ramp plan runs the ramp forms of the walk and of the front end ("k_front_pst_ramp" from
+ *     jsdr_bpsk_front_kernel).  Under a slope every sample costs an FP64 division in both kernels; samples under no slope cost
+ *     what they cost a step plan.  The plan is copied when it is given: 24 bytes an entry (position, tuning, slope) and 8 per
+ *     stream; the per-handle 4 bytes per 64 samples and stream are the step plans'.  jsdr_bpsk_planned_tunings counts ramp entries
+ *     too.
+ * Not built: ramps on ordinary or channel handles, JNI / Java classes, jsdr_group_*, the FAST variant, FFT-acquire, ramps that
+ * outlive a call. */
+int jsdr_bpsk_plan_stream_ramps(jsdr_bpsk *h, const int32_t *stream, const int64_t *at_sample, const double *tuning_hz,
+                                const double *slope_hz_per_sample, int64_t n);
+/* host only, no device (CPU tests): jsdr_bpsk_tuner_walk_plan_host with ramp entries -- from sample at_sample[e] on, sample i has
+ * the tuning tuning_at[e] + (double)(i - at_sample[e]) * slope_at[e] (slope 0: tuning_at[e] itself) and tuPhaseInc 2 pi tuning /
+ * rate; before the first entry tuPhaseInc is tu_inc.  *tu_end / *inc_end: tuPhase and tuPhaseInc after the last sample (may be
+ * NULL).  nev = 0 with null arrays is jsdr_bpsk_tuner_walk_host */
+int jsdr_bpsk_tuner_walk_ramp_host(double tu0, double tu_inc, int64_t n, int rate, const int64_t *at_sample, const double *tuning_at,
+                                   const double *slope_at, int64_t nev, uint16_t *k9_out, double *tu_end, double *inc_end);
 /* Checkpoints: the state of a range of streams out of a handle and into one -- across a restart, a library upgrade, another
  * machine, or between handles (a split is two saves with ranges, a merge two restores at offsets).  A blob is self-contained,
  * versioned (format 1) and position-independent: little-endian fixed-width fields, a 192-byte header with the sizes and a

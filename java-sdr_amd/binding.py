@@ -694,6 +694,20 @@ class BpskTuned(Bpsk):
         _check(lib().jsdr_bpsk_plan_stream_tunings(self.h, _addr(st) if n else None, _addr(at) if n else None, _addr(tu) if n else None,
                                                    C.c_int64(n)), "jsdr_bpsk_plan_stream_tunings")
 
+    def plan_ramps(self, streams, at_samples, tunings, slopes):
+        """plan_tunings with moving entries (jsdr_bpsk_plan_stream_ramps): from sample at_samples[i] of the next batch call on, sample n
+        of stream streams[i] has the tuning tunings[i] + float(n - at_samples[i]) * slopes[i] (Hz, Hz per sample), until the stream's
+        next entry or the call's end.  A slope of zero is a step; no entries: a pending plan is cleared."""
+        st = np.ascontiguousarray(streams, np.int32)
+        at = np.ascontiguousarray(at_samples, np.int64)
+        tu = np.ascontiguousarray(tunings, np.float64)
+        sl = np.ascontiguousarray(slopes, np.float64)
+        if not (st.ndim == at.ndim == tu.ndim == sl.ndim == 1 and st.size == at.size == tu.size == sl.size):
+            raise ValueError("plan_ramps: streams, at_samples, tunings and slopes are four lists of one length")
+        n = st.size
+        _check(lib().jsdr_bpsk_plan_stream_ramps(self.h, _addr(st) if n else None, _addr(at) if n else None, _addr(tu) if n else None,
+                                                 _addr(sl) if n else None, C.c_int64(n)), "jsdr_bpsk_plan_stream_ramps")
+
     def planned(self):
         """entries of a tuning plan waiting for the next batch call"""
         n = C.c_int64()
@@ -739,6 +753,24 @@ def tuner_walk_plan_host(tu0, inc, n, at_samples=(), incs=()):
                                                 _addr(ia) if ia.size else None, C.c_int64(at.size), _addr(k9), C.byref(end)),
            "jsdr_bpsk_tuner_walk_plan_host")
     return k9[:int(n)], end.value
+
+
+def tuner_walk_ramp_host(tu0, inc, n, rate, at_samples=(), tunings=(), slopes=()):
+    """tuner_walk_plan_host with ramp entries (no device): from sample at_samples[e] on, sample i has the tuning tunings[e] +
+    float(i - at_samples[e]) * slopes[e] and the increment 2 pi tuning / rate -> (9-bit table index per sample, tuPhase at the end,
+    tuPhaseInc at the end)"""
+    at = np.ascontiguousarray(at_samples, np.int64)
+    ta = np.ascontiguousarray(tunings, np.float64)
+    sa = np.ascontiguousarray(slopes, np.float64)
+    if not at.size == ta.size == sa.size:
+        raise ValueError("tuner_walk_ramp_host: one tuning and one slope per position")
+    k9 = np.empty(max(int(n), 1), np.uint16)
+    end, inc_end = C.c_double(), C.c_double()
+    _check(lib().jsdr_bpsk_tuner_walk_ramp_host(C.c_double(tu0), C.c_double(inc), C.c_int64(int(n)), C.c_int(int(rate)),
+                                                _addr(at) if at.size else None, _addr(ta) if ta.size else None,
+                                                _addr(sa) if sa.size else None, C.c_int64(at.size), _addr(k9), C.byref(end),
+                                                C.byref(inc_end)), "jsdr_bpsk_tuner_walk_ramp_host")
+    return k9[:int(n)], end.value, inc_end.value
 
 
 class BpskChannels(Bpsk):

@@ -62,6 +62,13 @@ struct BpskChan {
     DevBuf<unsigned short> dev;      // the device copy of sched.tab
 };
 
+// the last entry a pending tuning plan has for a stream: what the stream's tuning is after the call (a ramp: at its last sample)
+struct PstPlanLast {
+    int stream;
+    long long entry, at;  // its number in the plan, its at_sample
+    double tuning, slope;
+};
+
 struct SideJob;
 struct jsdr_bpsk {
     double tuning = 0.0;  // FUNcubeBPSKDemod.tuning (a double: freqDialog may give what +-10 never reaches)
@@ -234,13 +241,16 @@ struct jsdr_bpsk {
     DevBuf<unsigned short> pst_kh[2];  // [S][32] the 9-bit indices of the 26 samples before the next call, double-buffered like hist_in
     int pst_kh_cur = 0;
     DevBuf<int> pst_ids;               // [S] the streams an action zeroes dmMaxCorr in (k_reset_maxcorr_list)
-    // a tuning plan (jsdr_bpsk_plan_stream_tunings): retunes inside the next call, copied to the device when it is given.  The
-    // call that takes it clears pst_plan_n; the device copy stays until the next plan replaces it, a plan of 0 entries or destroy.
+    // a tuning plan (jsdr_bpsk_plan_stream_tunings, jsdr_bpsk_plan_stream_ramps): retunes inside the next call, copied to the device
+    // when it is given.  The call that takes it clears pst_plan_n; the device copy stays until the next plan replaces it, a plan of 0
+    // entries or destroy.
     long long pst_plan_n = 0;                            // entries pending
     long long pst_plan_max_at = -1;                      // the largest at_sample among them
-    std::vector<std::pair<int, double>> pst_plan_last;   // (stream, the tuning of its last entry): pst_tuning after the call
+    std::vector<PstPlanLast> pst_plan_last;              // every planned stream's last entry: pst_tuning after the call
+    bool pst_plan_ramp = false;                          // given by jsdr_bpsk_plan_stream_ramps with a slope that is not zero
     DevBuf<long long> pst_plan_off, pst_plan_pos;        // [S + 1], [n]  (PstPlanArgs)
-    DevBuf<double> pst_plan_inc;                         // [n]
+    DevBuf<double> pst_plan_inc;                         // [n], a step plan's
+    DevBuf<double> pst_plan_tun, pst_plan_slope;         // [n], [n], a ramp plan's  (PstRampArgs)
     DevBuf<double> pst_inc0;                             // [S], with the first plan
     DevBuf<int> pst_ckpt_e;                              // [S][pst_ckpt_stride], with the first plan
     // checkpoints (jsdr_bpsk_save / jsdr_bpsk_restore): the records' staging image, allocated at the first use
@@ -259,6 +269,14 @@ static bool stream_fft(const jsdr_bpsk *h, int stream)
 static size_t fft_state_at(const jsdr_bpsk *h, int stream)
 {
     return h->nch > 0 ? (size_t)(stream % h->nch) * (size_t)h->nin + (size_t)(stream / h->nch) : (size_t)stream;
+}
+
+static void pst_plan_clear(jsdr_bpsk *h)  // no plan pends (the device copy stays until a plan replaces it)
+{
+    h->pst_plan_n = 0;
+    h->pst_plan_max_at = -1;
+    h->pst_plan_ramp = false;
+    h->pst_plan_last.clear();
 }
 
 enum { PK_FRONT = 0, PK_HIST, PK_MATCHED, PK_DMHIST, PK_TAIL, PK_SYNC, PK_SYNCFIN, PK_FEC, PK_FM, PK_SYNCT, PK_PREP,
@@ -1139,6 +1157,14 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
     const bool planned = h->pst_plan_n > 0;
     JSDR_REQUIRE(!planned || L > h->pst_plan_max_at, "bpsk: the pending tuning plan has an entry at sample %lld, the call has %lld samples; the "
                  "handle is unchanged and the plan stays pending", h->pst_plan_max_at, L);
+    const bool ramp = planned && h->pst_plan_ramp;
+    if (ramp)  // a ramp that runs to the call's end: its last sample's tuning (the other end was checked with the plan)
+        for (const PstPlanLast &pl : h->pst_plan_last) {
+            const double t_end = tuner_ramp_tuning(pl.tuning, pl.slope, L - 1 - pl.at);
+            JSDR_REQUIRE(std::isfinite(t_end) && t_end < (double)h->rate, "bpsk: entry %lld of the pending ramp plan (stream %d, from sample %lld) "
+                         "reaches %g Hz at the call's last sample (%lld), not a finite value below the rate (%d Hz); the handle is unchanged and "
+                         "the plan stays pending", pl.entry, pl.stream, pl.at, t_end, L - 1, h->rate);
+        }
     if (hist_form(h, rawf_dev != nullptr, h->nstreams, st) != JSDR_OK) return JSDR_ERR;
     const int S = h->nstreams;
     const int first_out = h->decim - 1 - h->dsCnt;
@@ -1159,6 +1185,8 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
     // the plan was copied when it was given: the planned forms of the two kernels read it where it lies
     const PstPlanArgs pa = {h->pst_plan_off.p, h->pst_plan_pos.p, h->pst_plan_inc.p, h->pst_inc0.p, h->pst_ckpt_e.p, h->pst_inc.p};
     const PstPlanArgs *plan = planned ? &pa : nullptr;
+    const PstRampArgs ra = {h->pst_plan_tun.p, h->pst_plan_slope.p, (double)h->rate};
+    const PstRampArgs *rplan = ramp ? &ra : nullptr;
     {
         TunerWalkArgs wa;
         wa.tu = h->pst_tu.p;
@@ -1170,7 +1198,7 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
         wa.kh_new = h->pst_kh[h->pst_kh_cur ^ 1].p;
         wa.nstreams = S;
         ProfScope ps(h, PK_TWALK, st);
-        if (launch_tuner_walk(wa, plan, st) != JSDR_OK) return JSDR_ERR;
+        if (launch_tuner_walk(wa, plan, rplan, st) != JSDR_OK) return JSDR_ERR;
     }
     if (nds > 0) {
         PstFrontArgs fa;
@@ -1193,8 +1221,8 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
         fa.first_out = first_out;
         fa.decim = h->decim;
         ProfScope ps(h, PK_FRONT, st);
-        h->front_name = planned ? "k_front_pst_plan" : "k_front_pst";
-        if (launch_front_pst(fa, S, rawf != nullptr, plan, st) != JSDR_OK) return JSDR_ERR;
+        h->front_name = ramp ? "k_front_pst_ramp" : planned ? "k_front_pst_plan" : "k_front_pst";
+        if (launch_front_pst(fa, S, rawf != nullptr, plan, rplan, st) != JSDR_OK) return JSDR_ERR;
     }
     h->pst_kh_cur ^= 1;
     if (run_hist_in(h, hist_args(h, raw, rawf, stride_pairs, L, ic, qc, S), st) != JSDR_OK) return JSDR_ERR;
@@ -1202,11 +1230,10 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
     if (wait_tail(h, yb, st) != JSDR_OK) return JSDR_ERR;
     if (nds > 0 && run_matched(h, yb, nds, g_first, st) != JSDR_OK) return JSDR_ERR;
     if (finish_call(h, yb, L, nds, g_first, first_out, ic, qc, raw, stride_pairs, kvco_p, tcs_p, st) != JSDR_OK) return JSDR_ERR;
-    if (planned) {  // one-shot: the streams it named stand at their last entries (the walk left their tuPhaseInc on the device)
-        for (const auto &sl : h->pst_plan_last) h->pst_tuning[(size_t)sl.first] = sl.second;
-        h->pst_plan_n = 0;
-        h->pst_plan_max_at = -1;
-        h->pst_plan_last.clear();
+    if (planned) {  // one-shot: the streams it named stand at their last entries, a ramp at the call's last sample (the walk left
+                    // their tuPhaseInc on the device: tuner_inc of these)
+        for (const PstPlanLast &pl : h->pst_plan_last) h->pst_tuning[(size_t)pl.stream] = tuner_ramp_tuning(pl.tuning, pl.slope, L - 1 - pl.at);
+        pst_plan_clear(h);
     }
     return JSDR_OK;
 }
@@ -2934,19 +2961,22 @@ int jsdr_bpsk_get_stream_tuning(jsdr_bpsk *h, int stream, double *tuning_hz)
 }
 
 // A tuning plan: entry i says "from sample at_sample[i] of the NEXT batch call on, stream stream[i] has tuning tuning_hz[i]" --
-// setup()'s tuning change (:192-209, what jsdr_bpsk_reconfigure applies between calls) at a sample of the stream's own.  Every
+// setup()'s tuning change (:192-209, what jsdr_bpsk_reconfigure applies between calls) at a sample of the stream's own -- and,
+// given with slopes (jsdr_bpsk_plan_stream_ramps), "... moving on by slope_hz_per_sample[i] a sample" (tuner_ramp_tuning).  Every
 // check comes before any device work; then the handle's pending work is waited for (the call before may still read the plan it
 // took) and the plan goes to the device in buffers of its own, which take the old ones' place only once all of it is there.
-int jsdr_bpsk_plan_stream_tunings(jsdr_bpsk *h, const int32_t *stream, const int64_t *at_sample, const double *tuning_hz, int64_t n)
+// slope: null for steps.  Slopes that are all zero are steps too, and go the steps' way.
+static int pst_plan_give(jsdr_bpsk *h, const char *who, const int32_t *stream, const int64_t *at_sample, const double *tuning_hz,
+                         const double *slope, bool with_slopes, int64_t n)
 {
-    static const char *who = "jsdr_bpsk_plan_stream_tunings";
     JSDR_REQUIRE(h, "%s: null handle", who);
     JSDR_REQUIRE(h->pst, "%s: the handle was not made by jsdr_bpsk_create_tuned (its streams share one tuning: jsdr_bpsk_reconfigure between "
                  "calls); the handle is unchanged", who);
     JSDR_REQUIRE(n >= 0, "%s: %lld entries; the handle and its pending plan are unchanged", who, (long long)n);
-    JSDR_REQUIRE(n == 0 || (stream && at_sample && tuning_hz), "%s: null array with %lld entries; the handle and its pending plan are unchanged",
-                 who, (long long)n);
+    JSDR_REQUIRE(n == 0 || (stream && at_sample && tuning_hz && (slope || !with_slopes)), "%s: null array with %lld entries; the handle and its "
+                 "pending plan are unchanged", who, (long long)n);
     const int S = h->nstreams;
+    bool ramp = false;
     for (int64_t i = 0; i < n; i++) {
         JSDR_REQUIRE(stream[i] >= 0 && stream[i] < S, "%s: entry %lld: stream %d out of range (the handle has %d); the handle and its pending "
                      "plan are unchanged", who, (long long)i, (int)stream[i], S);
@@ -2958,18 +2988,33 @@ int jsdr_bpsk_plan_stream_tunings(jsdr_bpsk *h, const int32_t *stream, const int
         JSDR_REQUIRE(std::isfinite(tuning_hz[i]) && tuning_hz[i] < (double)h->rate, "%s: entry %lld: tuning %g Hz of stream %d is not a finite "
                      "value below the rate (%d Hz); the handle and its pending plan are unchanged", who, (long long)i, tuning_hz[i],
                      (int)stream[i], h->rate);
+        if (!with_slopes) continue;
+        JSDR_REQUIRE(std::isfinite(slope[i]), "%s: entry %lld: slope %g Hz per sample of stream %d is not finite; the handle and its pending "
+                     "plan are unchanged", who, (long long)i, slope[i], (int)stream[i]);
+        ramp = ramp || slope[i] != 0.0;
+        // the tunings of a ramp are monotone in the sample (rounding is), and its first is the entry's: the one in front of the
+        // stream's next entry decides here; a ramp that runs to the call's end is checked at the call, which knows where that is
+        if (i > 0 && stream[i] == stream[i - 1]) {
+            const double t_end = tuner_ramp_tuning(tuning_hz[i - 1], slope[i - 1], (long long)(at_sample[i] - 1 - at_sample[i - 1]));
+            JSDR_REQUIRE(std::isfinite(t_end) && t_end < (double)h->rate, "%s: entry %lld: the ramp of stream %d reaches %g Hz at sample %lld, in "
+                         "front of its next entry, not a finite value below the rate (%d Hz); the handle and its pending plan are unchanged", who,
+                         (long long)(i - 1), (int)stream[i], t_end, (long long)(at_sample[i] - 1), h->rate);
+        }
     }
     std::vector<long long> off((size_t)S + 1, 0), pos((size_t)n);
-    std::vector<double> inc((size_t)n);
-    std::vector<std::pair<int, double>> last;
+    std::vector<double> inc((size_t)(ramp ? 0 : n));
+    std::vector<PstPlanLast> last;
+    long long max_at = -1;
     for (int64_t i = 0; i < n; i++) {
         off[(size_t)stream[i] + 1]++;
         pos[(size_t)i] = at_sample[i];
-        inc[(size_t)i] = tuner_inc(tuning_hz[i], h->rate);  // :196, the double pst_apply writes
-        if (!last.empty() && last.back().first == stream[i])
-            last.back().second = tuning_hz[i];
+        if (!ramp) inc[(size_t)i] = tuner_inc(tuning_hz[i], h->rate);  // :196, the double pst_apply writes
+        if (at_sample[i] > max_at) max_at = at_sample[i];
+        const PstPlanLast pl = {(int)stream[i], (long long)i, (long long)at_sample[i], tuning_hz[i], ramp ? slope[i] : 0.0};
+        if (!last.empty() && last.back().stream == stream[i])
+            last.back() = pl;
         else
-            last.emplace_back((int)stream[i], tuning_hz[i]);
+            last.push_back(pl);
     }
     for (int s = 0; s < S; s++) {
         JSDR_REQUIRE(off[(size_t)s + 1] <= 0x7fffffffLL, "%s: %lld entries for stream %d; the handle and its pending plan are unchanged", who,
@@ -2977,37 +3022,49 @@ int jsdr_bpsk_plan_stream_tunings(jsdr_bpsk *h, const int32_t *stream, const int
         off[(size_t)s + 1] += off[(size_t)s];
     }
     if (sync_last(h) != JSDR_OK) return JSDR_ERR;
-    if (n == 0) {  // no plan: the next call is an ordinary one
-        h->pst_plan_off.release();
-        h->pst_plan_pos.release();
-        h->pst_plan_inc.release();
-        h->pst_plan_n = 0;
-        h->pst_plan_max_at = -1;
-        h->pst_plan_last.clear();
-        return JSDR_OK;
-    }
     DevBuf<long long> d_off, d_pos;
-    DevBuf<double> d_inc, d_inc0;
+    DevBuf<double> d_inc, d_tun, d_slope, d_inc0;
     DevBuf<int> d_cke;
-    const bool first = !h->pst_inc0.p;  // (what the planned walk leaves for the planned front end: with the first plan)
-    if (d_off.alloc(off.size()) != JSDR_OK || d_pos.alloc(pos.size()) != JSDR_OK || d_inc.alloc(inc.size()) != JSDR_OK) return JSDR_ERR;
-    if (first && (d_inc0.alloc((size_t)S) != JSDR_OK || d_cke.alloc((size_t)S * (size_t)h->pst_ckpt_stride) != JSDR_OK)) return JSDR_ERR;
-    JSDR_HIP_TRY(hipMemcpy(d_off.p, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
-    JSDR_HIP_TRY(hipMemcpy(d_pos.p, pos.data(), sizeof(long long) * pos.size(), hipMemcpyHostToDevice));
-    JSDR_HIP_TRY(hipMemcpy(d_inc.p, inc.data(), sizeof(double) * inc.size(), hipMemcpyHostToDevice));
-    std::swap(h->pst_plan_off, d_off);  // (the old plan's buffers go with the locals)
+    const bool first = n > 0 && !h->pst_inc0.p;  // (what the planned walk leaves for the planned front end: with the first plan)
+    if (n > 0) {  // (none: the next call is an ordinary one, and the old plan's buffers go)
+        if (d_off.alloc(off.size()) != JSDR_OK || d_pos.alloc(pos.size()) != JSDR_OK) return JSDR_ERR;
+        if (ramp ? d_tun.alloc((size_t)n) != JSDR_OK || d_slope.alloc((size_t)n) != JSDR_OK : d_inc.alloc(inc.size()) != JSDR_OK) return JSDR_ERR;
+        if (first && (d_inc0.alloc((size_t)S) != JSDR_OK || d_cke.alloc((size_t)S * (size_t)h->pst_ckpt_stride) != JSDR_OK)) return JSDR_ERR;
+        JSDR_HIP_TRY(hipMemcpy(d_off.p, off.data(), sizeof(long long) * off.size(), hipMemcpyHostToDevice));
+        JSDR_HIP_TRY(hipMemcpy(d_pos.p, pos.data(), sizeof(long long) * pos.size(), hipMemcpyHostToDevice));
+        if (ramp) {
+            JSDR_HIP_TRY(hipMemcpy(d_tun.p, tuning_hz, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+            JSDR_HIP_TRY(hipMemcpy(d_slope.p, slope, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+        } else {
+            JSDR_HIP_TRY(hipMemcpy(d_inc.p, inc.data(), sizeof(double) * inc.size(), hipMemcpyHostToDevice));
+        }
+    }
+    std::swap(h->pst_plan_off, d_off);  // (the old plan's buffers go with the locals, those of the other kind for empty ones)
     std::swap(h->pst_plan_pos, d_pos);
     std::swap(h->pst_plan_inc, d_inc);
+    std::swap(h->pst_plan_tun, d_tun);
+    std::swap(h->pst_plan_slope, d_slope);
     if (first) {
         std::swap(h->pst_inc0, d_inc0);
         std::swap(h->pst_ckpt_e, d_cke);
     }
+    pst_plan_clear(h);
     h->pst_plan_n = n;
-    h->pst_plan_max_at = -1;
-    for (int64_t i = 0; i < n; i++)
-        if (at_sample[i] > h->pst_plan_max_at) h->pst_plan_max_at = at_sample[i];
+    h->pst_plan_max_at = max_at;
+    h->pst_plan_ramp = ramp;
     h->pst_plan_last.swap(last);
     return JSDR_OK;
+}
+
+int jsdr_bpsk_plan_stream_tunings(jsdr_bpsk *h, const int32_t *stream, const int64_t *at_sample, const double *tuning_hz, int64_t n)
+{
+    return pst_plan_give(h, "jsdr_bpsk_plan_stream_tunings", stream, at_sample, tuning_hz, nullptr, false, n);
+}
+
+int jsdr_bpsk_plan_stream_ramps(jsdr_bpsk *h, const int32_t *stream, const int64_t *at_sample, const double *tuning_hz,
+                                const double *slope_hz_per_sample, int64_t n)
+{
+    return pst_plan_give(h, "jsdr_bpsk_plan_stream_ramps", stream, at_sample, tuning_hz, slope_hz_per_sample, true, n);
 }
 
 int jsdr_bpsk_planned_tunings(jsdr_bpsk *h, int64_t *n)
@@ -3037,6 +3094,33 @@ int jsdr_bpsk_tuner_walk_plan_host(double tu0, double tu_inc, int64_t n, const i
         k9_out[i] = (uint16_t)tuner_step(tu, inc);
     }
     if (tu_end) *tu_end = tu;
+    return JSDR_OK;
+}
+
+// host only, no device: jsdr_bpsk_tuner_walk_plan_host with ramp entries -- from sample at_sample[e] on, sample i has the tuning
+// tuner_ramp_tuning(tuning_at[e], slope_at[e], i - at_sample[e]) and advances by tuner_inc of it, as the ramp forms of the two
+// kernels step it; tu_end / inc_end: tuPhase and tuPhaseInc after sample n - 1
+int jsdr_bpsk_tuner_walk_ramp_host(double tu0, double tu_inc, int64_t n, int rate, const int64_t *at_sample, const double *tuning_at,
+                                   const double *slope_at, int64_t nev, uint16_t *k9_out, double *tu_end, double *inc_end)
+{
+    static const char *who = "jsdr_bpsk_tuner_walk_ramp_host";
+    JSDR_REQUIRE(n >= 0 && (k9_out || n == 0), "%s: %lld samples, index buffer %s", who, (long long)n, k9_out ? "given" : "null");
+    JSDR_REQUIRE(rate >= 1, "%s: rate %d", who, rate);
+    JSDR_REQUIRE(nev >= 0 && (nev == 0 || (at_sample && tuning_at && slope_at)), "%s: %lld entries, arrays %s", who, (long long)nev,
+                 at_sample && tuning_at && slope_at ? "given" : "null");
+    for (int64_t e = 0; e < nev; e++)
+        JSDR_REQUIRE(at_sample[e] >= 0 && (e == 0 || at_sample[e] > at_sample[e - 1]), "%s: entry %lld (sample %lld) is negative or out of order",
+                     who, (long long)e, (long long)at_sample[e]);
+    double tu = tu0, inc = tu_inc;
+    int64_t e = 0;
+    bool on = false;  // an entry is in effect: e - 1
+    for (int64_t i = 0; i < n; i++) {
+        if (e < nev && at_sample[e] == i) on = true, e++;
+        if (on) inc = tuner_ramp_inc(tuning_at[e - 1], slope_at[e - 1], (long long)(i - at_sample[e - 1]), (double)rate);
+        k9_out[i] = (uint16_t)tuner_step(tu, inc);
+    }
+    if (tu_end) *tu_end = tu;
+    if (inc_end) *inc_end = inc;
     return JSDR_OK;
 }
 

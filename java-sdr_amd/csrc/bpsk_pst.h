@@ -53,9 +53,18 @@ struct PstPlanArgs {
     double *inc_out;       // [S] the walk leaves tuPhaseInc as the stream goes out of the call (the handle's tuPhaseInc array)
 };
 
-// plan: null for a call without one (the kernels of such a call do not know of plans)
-int launch_tuner_walk(const TunerWalkArgs &a, const PstPlanArgs *plan, hipStream_t st);
-int launch_front_pst(const PstFrontArgs &a, int nstreams, bool f32in, const PstPlanArgs *plan, hipStream_t st);
+// A ramp plan (jsdr_bpsk_plan_stream_ramps), beside PstPlanArgs, as the ramp forms k_tuner_walk_ramp / k_front_pst_ramp read it:
+// entry e says "sample n >= pos[e] of the call has tuning tuning[e] + (double)(n - pos[e]) * slope[e]" (tuner_ramp_tuning; a slope
+// of zero: tuning[e] itself) until the stream's next entry, and tuPhaseInc is tuner_inc of it.  PstPlanArgs::inc is not read.
+struct PstRampArgs {
+    const double *tuning;  // [off[S]] Hz
+    const double *slope;   // [off[S]] Hz per sample
+    double rate;           // the sample rate, as the double tuPhaseInc is divided by
+};
+
+// plan: null for a call without one (the kernels of such a call do not know of plans); ramp: null, or with plan for a ramp plan
+int launch_tuner_walk(const TunerWalkArgs &a, const PstPlanArgs *plan, const PstRampArgs *ramp, hipStream_t st);
+int launch_front_pst(const PstFrontArgs &a, int nstreams, bool f32in, const PstPlanArgs *plan, const PstRampArgs *ramp, hipStream_t st);
 // dmMaxCorr = 0 (:190) in the n streams ids[] names
 int launch_reset_maxcorr_list(TailState *st, const int *ids, int n, hipStream_t stream);
 

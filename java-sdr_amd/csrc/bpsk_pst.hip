@@ -30,6 +30,13 @@
 // Beside each checkpoint it leaves the number of the stream's entries before the block's first sample (4 bytes), and the
 // increment the stream came into the call with; phase 1 of the planned front end starts a block from those and switches at the
 // entries inside it, as the walk did.  Nothing is kept per sample.
+//
+// A call with a ramp plan (jsdr_bpsk_plan_stream_ramps, PstRampArgs: from its sample on an entry's tuning moves by its slope a
+// sample) runs the third forms k_tuner_walk_ramp and k_front_pst_ramp<F32IN>, the same bodies with RAMP = true.  Under a slope
+// tuPhaseInc is the sample's own -- tuner_ramp_inc (bpsk_tuner.h): a product, a sum and tuner_inc's true FP64 division, none of
+// which waits for the tuPhase chain -- so a block takes the per-sample loop where it holds an entry OR lies under a slope (in the
+// walk: in some lane of the wave; lanes under no slope keep their increment).  The checkpoints say as much as for steps: the
+// entry count before a block names the entry in effect, whose position gives the block's first k.  Nothing more is stored.
 #include "common.h"
 #include "bpsk_tuner.h"
 #include "bpsk_pst.h"
@@ -41,18 +48,36 @@ enum { PST_THREADS = 256, PST_WALK_THREADS = 64 };
 constexpr long long PST_NO_ENTRY = 0x7fffffffffffffffLL;  // the position of "no further entry"
 
 // The two kernels' bodies are stated once each, in bpsk_pst_walk_body.h and bpsk_pst_front_body.h, and included between the braces
-// of the plain and the planned form with PLAN set: a body handed its kernel's argument struct as a function argument compiles to
+// of the plain, the planned and the ramp form with PLAN and RAMP set: a body handed its kernel's argument struct as a function argument compiles to
 // other (equivalent) code than one that reads it in place, and the plain forms' code objects are pinned (tools/kernel_asm_diff.py).
+// RAMP: the entry in effect in the walk's lane -- its tuning, slope and position; no slope: the lane's increment stands.  (Declared by
+// the three forms in front of the body: a local the body declares itself moves the planned form's instructions about.)
+struct PstRampAt {
+    double t = 0.0, s = 0.0;
+    long long at = 0;
+};
+
 __global__ __launch_bounds__(PST_WALK_THREADS) void k_tuner_walk(TunerWalkArgs a)
 {
-    constexpr bool PLAN = false;
+    constexpr bool PLAN = false, RAMP = false;
     const PstPlanArgs p{};
+    const PstRampArgs r{};
+    PstRampAt ra;
 #include "bpsk_pst_walk_body.h"
 }
 
 __global__ __launch_bounds__(PST_WALK_THREADS) void k_tuner_walk_plan(TunerWalkArgs a, PstPlanArgs p)
 {
-    constexpr bool PLAN = true;
+    constexpr bool PLAN = true, RAMP = false;
+    const PstRampArgs r{};
+    PstRampAt ra;
+#include "bpsk_pst_walk_body.h"
+}
+
+__global__ __launch_bounds__(PST_WALK_THREADS) void k_tuner_walk_ramp(TunerWalkArgs a, PstPlanArgs p, PstRampArgs r)
+{
+    constexpr bool PLAN = true, RAMP = true;
+    PstRampAt ra;
 #include "bpsk_pst_walk_body.h"
 }
 
@@ -63,15 +88,24 @@ __device__ __forceinline__ int pst_slot(int e) { return e + (e >> 6); }
 template <bool F32IN>
 __global__ __launch_bounds__(PST_THREADS) void k_front_pst(PstFrontArgs a)
 {
-    constexpr bool PLAN = false;
+    constexpr bool PLAN = false, RAMP = false;
     const PstPlanArgs p{};
+    const PstRampArgs r{};
 #include "bpsk_pst_front_body.h"
 }
 
 template <bool F32IN>
 __global__ __launch_bounds__(PST_THREADS) void k_front_pst_plan(PstFrontArgs a, PstPlanArgs p)
 {
-    constexpr bool PLAN = true;
+    constexpr bool PLAN = true, RAMP = false;
+    const PstRampArgs r{};
+#include "bpsk_pst_front_body.h"
+}
+
+template <bool F32IN>
+__global__ __launch_bounds__(PST_THREADS) void k_front_pst_ramp(PstFrontArgs a, PstPlanArgs p, PstRampArgs r)
+{
+    constexpr bool PLAN = true, RAMP = true;
 #include "bpsk_pst_front_body.h"
 }
 
@@ -82,10 +116,12 @@ __global__ void k_reset_maxcorr_list(TailState *st, const int *ids, int n)
     if (i < n) st[ids[i]].dmMaxCorr = 0;
 }
 
-int launch_tuner_walk(const TunerWalkArgs &a, const PstPlanArgs *plan, hipStream_t st)
+int launch_tuner_walk(const TunerWalkArgs &a, const PstPlanArgs *plan, const PstRampArgs *ramp, hipStream_t st)
 {
     const dim3 grid((unsigned)((a.nstreams + PST_WALK_THREADS - 1) / PST_WALK_THREADS));
-    if (plan)
+    if (plan && ramp)
+        hipLaunchKernelGGL(k_tuner_walk_ramp, grid, dim3(PST_WALK_THREADS), 0, st, a, *plan, *ramp);
+    else if (plan)
         hipLaunchKernelGGL(k_tuner_walk_plan, grid, dim3(PST_WALK_THREADS), 0, st, a, *plan);
     else
         hipLaunchKernelGGL(k_tuner_walk, grid, dim3(PST_WALK_THREADS), 0, st, a);
@@ -93,7 +129,7 @@ int launch_tuner_walk(const TunerWalkArgs &a, const PstPlanArgs *plan, hipStream
     return JSDR_OK;
 }
 
-int launch_front_pst(const PstFrontArgs &a_in, int nstreams, bool f32in, const PstPlanArgs *plan, hipStream_t st)
+int launch_front_pst(const PstFrontArgs &a_in, int nstreams, bool f32in, const PstPlanArgs *plan, const PstRampArgs *ramp, hipStream_t st)
 {
     PstFrontArgs a = a_in;
     // outputs per workgroup: 256, fewer where a tile's samples (16 bytes of mixed doubles and 2 of index each) would not fit
@@ -110,7 +146,13 @@ int launch_front_pst(const PstFrontArgs &a_in, int nstreams, bool f32in, const P
     const size_t lds = fixed + ((size_t)(nout - 1) * a.decim + 27) * per;
     const long long gx = (a.nds + nout - 1) / nout;
     const dim3 grid((unsigned)gx, (unsigned)nstreams);
-    if (plan && f32in) {
+    if (plan && ramp && f32in) {
+        JSDR_LDS_ATTR((k_front_pst_ramp<true>), lds);
+        hipLaunchKernelGGL((k_front_pst_ramp<true>), grid, dim3(PST_THREADS), lds, st, a, *plan, *ramp);
+    } else if (plan && ramp) {
+        JSDR_LDS_ATTR((k_front_pst_ramp<false>), lds);
+        hipLaunchKernelGGL((k_front_pst_ramp<false>), grid, dim3(PST_THREADS), lds, st, a, *plan, *ramp);
+    } else if (plan && f32in) {
         JSDR_LDS_ATTR((k_front_pst_plan<true>), lds);
         hipLaunchKernelGGL((k_front_pst_plan<true>), grid, dim3(PST_THREADS), lds, st, a, *plan);
     } else if (plan) {

@@ -1,5 +1,6 @@
-// bpsk_pst_front_body.h -- the body of k_front_pst<F32IN> and k_front_pst_plan<F32IN> (bpsk_pst.hip), included between their
-// braces.  In scope: PstFrontArgs a, PstPlanArgs p, constexpr bool F32IN, PLAN (phase 1 switches tuPhaseInc at the plan's entries).
+// bpsk_pst_front_body.h -- the body of k_front_pst<F32IN>, k_front_pst_plan<F32IN> and k_front_pst_ramp<F32IN> (bpsk_pst.hip),
+// included between their braces.  In scope: PstFrontArgs a, PstPlanArgs p, PstRampArgs r, constexpr bool F32IN, PLAN (phase 1
+// switches tuPhaseInc at the plan's entries), RAMP (PLAN, and the entries are ramps: under a slope tuPhaseInc is the sample's own).
     extern __shared__ __align__(16) unsigned char smem[];
     double *sc = reinterpret_cast<double *>(smem);            // [514] cos[0..256], sin[0..256]
     double *taps = sc + 514;                                  // [27]
@@ -27,23 +28,46 @@
         if constexpr (PLAN) {  // ... with a plan: of the entry in effect there; then through the entries inside the block
             const long long e0 = p.off[s], e_end = p.off[s + 1];
             long long e = e0 + p.ckpt_e[(long long)s * a.ckpt_stride + c];
-            inc_c = e > e0 ? p.inc[e - 1] : p.inc0[s];
+            double rt = 0.0, rs = 0.0;  // RAMP: the tuning and the slope of the entry in effect (no slope: inc_c stands), at sample rat
+            long long rat = 0;
+            if constexpr (RAMP) {
+                inc_c = p.inc0[s];
+                if (e > e0) {
+                    rt = r.tuning[e - 1];
+                    rs = r.slope[e - 1];
+                    rat = p.pos[e - 1];
+                    if (rs == 0.0) inc_c = tuner_ramp_inc(rt, rs, 0, r.rate);
+                }
+            } else {
+                inc_c = e > e0 ? p.inc[e - 1] : p.inc0[s];
+            }
             long long next = e < e_end ? p.pos[e] : PST_NO_ENTRY;
-            if (next < nb + PST_C) {
+            bool slow = next < nb + PST_C;
+            if constexpr (RAMP) slow = slow || rs != 0.0;
+            if (slow) {
                 for (int i = 0; i < PST_C; i++) {
                     const long long n = nb + i;
                     if (n == next) {
-                        inc_c = p.inc[e];
+                        if constexpr (RAMP) {
+                            rt = r.tuning[e];
+                            rs = r.slope[e];
+                            rat = n;
+                            if (rs == 0.0) inc_c = tuner_ramp_inc(rt, rs, 0, r.rate);
+                        } else {
+                            inc_c = p.inc[e];
+                        }
                         e++;
                         next = e < e_end ? p.pos[e] : PST_NO_ENTRY;
                     }
+                    if constexpr (RAMP)
+                        if (rs != 0.0) inc_c = tuner_ramp_inc(rt, rs, n - rat, r.rate);
                     tuner_advance(tu, inc_c);
                     if (n >= n_first && n <= n_last) tus[pst_slot((int)(n - n_lo))] = tu;
                 }
                 continue;
             }
         }
-        for (int i = 0; i < PST_C; i++) {  // (a block without an entry: the plain loop)
+        for (int i = 0; i < PST_C; i++) {  // (a block without an entry and under no slope: the plain loop)
             tuner_advance(tu, inc_c);
             const long long n = nb + i;
             if (n >= n_first && n <= n_last) tus[pst_slot((int)(n - n_lo))] = tu;

@@ -1,5 +1,6 @@
-// bpsk_pst_walk_body.h -- the body of k_tuner_walk and k_tuner_walk_plan (bpsk_pst.hip), included between their braces: the walk
-// of one stream.  In scope: TunerWalkArgs a, PstPlanArgs p, constexpr bool PLAN (with the stream's entries of the call's plan).
+// bpsk_pst_walk_body.h -- the body of k_tuner_walk, k_tuner_walk_plan and k_tuner_walk_ramp (bpsk_pst.hip), included between their
+// braces: the walk of one stream.  In scope: TunerWalkArgs a, PstPlanArgs p, PstRampArgs r, PstRampAt ra, constexpr bool PLAN (with the stream's
+// entries of the call's plan), RAMP (PLAN, and the entries are ramps: under a slope tuPhaseInc is the sample's own).
     const int s = blockIdx.x * PST_WALK_THREADS + threadIdx.x;
     if (s >= a.nstreams) return;
     const long long L = a.nsamples;
@@ -25,13 +26,23 @@
         const long long n1 = (c + 1) * PST_C < L ? (c + 1) * PST_C : L;
         if constexpr (PLAN) {
             cke[c] = (int)(e - e0);
-            if (__any(next < n1)) {  // an entry in this block, in some lane of the wave
+            // an entry in this block, in some lane of the wave; RAMP: or the block lies under a slope in one
+            if (__any(RAMP ? (next < n1 || ra.s != 0.0) : (next < n1))) {
                 for (long long n = c * PST_C; n < n1; n++) {
                     if (n == next) {  // the advance of sample `next` is the first at the new increment
-                        inc = p.inc[e];
+                        if constexpr (RAMP) {
+                            ra.t = r.tuning[e];
+                            ra.s = r.slope[e];
+                            ra.at = n;
+                            if (ra.s == 0.0) inc = tuner_ramp_inc(ra.t, ra.s, 0, r.rate);
+                        } else {
+                            inc = p.inc[e];
+                        }
                         e++;
                         next = e < e_end ? p.pos[e] : PST_NO_ENTRY;
                     }
+                    if constexpr (RAMP)
+                        if (ra.s != 0.0) inc = tuner_ramp_inc(ra.t, ra.s, n - ra.at, r.rate);  // (a lane under no slope keeps its increment)
                     tuner_advance(tu, inc);
                     if (n >= nmain) kn[26 - (L - n)] = (unsigned short)tuner_k9(tu);
                 }
@@ -44,4 +55,4 @@
         }
     }
     a.tu[s] = tu;
-    if constexpr (PLAN) p.inc_out[s] = inc;  // (every entry lies inside the call: the last one's)
+    if constexpr (PLAN) p.inc_out[s] = inc;  // (every entry lies inside the call: the last one's, a ramp's of the last sample)

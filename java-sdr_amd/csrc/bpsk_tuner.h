@@ -20,6 +20,19 @@ constexpr double TUNER_PI = 3.14159265358979323846;  // Math.PI
 // tuPhaseInc = 2 pi tuning / rate, evaluated left to right   (:189 / :196)
 inline double tuner_inc(double tuning, int rate) { return 2.0 * TUNER_PI * tuning / (double)rate; }
 
+// Sample k of a ramp entry (jsdr_bpsk_plan_stream_ramps): its tuning -- one product and one sum, each rounded by itself; a slope of
+// zero takes the entry's tuning itself, with no arithmetic -- and its tuPhaseInc: tuner_inc of that tuning, the division a true
+// division by the rate (as a double), never a product with a reciprocal.  The host mirror, the handle's end-of-call tuning and
+// the ramp forms of the two kernels of a tuned handle all step a ramp through these two.
+__host__ __device__ inline double tuner_ramp_tuning(double tuning, double slope, long long k)
+{
+    return slope == 0.0 ? tuning : tuning + (double)k * slope;
+}
+__host__ __device__ inline double tuner_ramp_inc(double tuning, double slope, long long k, double rate)
+{
+    return 2.0 * TUNER_PI * tuner_ramp_tuning(tuning, slope, k) / rate;
+}
+
 // tuPhase += tuPhaseInc; if (tuPhase > 2 pi) tuPhase -= 2 pi   (:384-385)
 __host__ __device__ inline void tuner_advance(double &tu, double inc)
 {

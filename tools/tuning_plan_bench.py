@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""What a tuning plan costs (jsdr_bpsk_plan_stream_tunings: retunes inside a batch call of a tuned handle); prints one JSON line.
+"""What a tuning plan costs (jsdr_bpsk_plan_stream_tunings, jsdr_bpsk_plan_stream_ramps: retunes inside a batch call of a tuned
+handle); prints one JSON line.
 
 The shape of tools/stream_tuning_bench.py: 2048 streams x 2^20 samples a call at 96 kHz, distinct non-periodic tunings, wall time
 of a call plus a sync of the handle, median of --steps after --warmup, all in one run:
@@ -9,7 +10,11 @@ of a call plus a sync of the handle, median of --steps after --warmup, all in on
       streams of a wave retune at the same sample.  f_plan_ms: giving the plan (validation, copy to the device), not in f_call_ms
   (g) the same retunes the only way there is without a plan: the call cut into 28 pieces with set_stream_tunings between them
       (which lines the instants up; the plan does not need that)
-  and, from the profile slots of one more call each, k_tuner_walk and k_front for (d) and (f)."""
+  (h) a ramp plan (jsdr_bpsk_plan_stream_ramps): (f)'s 27 entries a stream at (f)'s samples, each with the slope that reaches the next
+      one's tuning (+10 Hz in 38 400 samples): every sample behind a stream's first entry lies under a slope
+  (i) the same curves as a step plan: one entry every 256 samples from each stream's first entry on (0.07 Hz a step)
+  and, from the profile slots of one more call each, k_tuner_walk and k_front for (d), (f), (h) and (i); for (h) and (i) the time
+  of giving the plan and the bytes it takes on the device.  (d) and (f) are measured in the same run: compare with them alone."""
 import argparse
 import json
 import os
@@ -25,6 +30,7 @@ import java_sdr_amd as J  # noqa: E402
 from stream_tuning_bench import RATE, distinct, fill, slots  # noqa: E402
 
 EVERY = 38400
+FINE = 256  # (i): samples between two step entries that follow (h)'s curves
 
 
 def median_ms(fn, warmup, steps, before=None):
@@ -93,6 +99,36 @@ def main():
     out["g_pieces"] = nent + 1
     out["f_over_d"] = round(out["f_planned_ms"] / out["d_unplanned_ms"], 3)
     out["g_over_d"] = round(out["g_pieces_ms"] / out["d_unplanned_ms"], 3)
+
+    # (h): (f)'s entries with slopes; (i): the curves of (h) sampled every FINE samples
+    slope = np.full(st.size, 10.0 / EVERY)
+    sg = np.asarray(stagger, np.int64)
+    i_st, i_at, i_tu = [], [], []
+    for s in range(N):
+        ns = np.arange(EVERY + sg[s], L, FINE, dtype=np.int64)
+        k = (ns - sg[s]) // EVERY  # the entry of (h) in effect: 1 .. nent
+        i_st.append(np.full(ns.size, s, np.int32))
+        i_at.append(ns)
+        i_tu.append(tun[s] + 10.0 * k + (ns - (k * EVERY + sg[s])).astype(np.float64) * (10.0 / EVERY))
+    i_st, i_at, i_tu = np.concatenate(i_st), np.concatenate(i_at), np.concatenate(i_tu)
+    for key, give_plan, nentries, per in (("h", lambda: d.plan_ramps(st, at, tu, slope), int(st.size), 24),
+                                          ("i", lambda: d.plan_tunings(i_st, i_at, i_tu), int(i_st.size), 16)):
+        def give_it():
+            reset()
+            give_plan()
+
+        out[key + "_ms"] = round(median_ms(call, a.warmup, a.steps, give_it), 3)
+        out[key + "_front"] = d.front_kernel_name()
+        reset()
+        out[key + "_plan_ms"] = round(median_ms(give_plan, 0, a.steps), 3)
+        out[key + "_walk_ms"], out[key + "_front_ms"] = slots(d, buf, L)
+        out[key + "_entries"] = nentries
+        out[key + "_plan_bytes"] = nentries * per + 8 * (N + 1)
+        assert d.planned() == 0
+    assert d.stream_tuning(N - 1) == i_tu[-1]  # ((i) ran last: its last entry)
+    out["h_over_d"] = round(out["h_ms"] / out["d_unplanned_ms"], 3)
+    out["h_over_f"] = round(out["h_ms"] / out["f_planned_ms"], 3)
+    out["i_over_d"] = round(out["i_ms"] / out["d_unplanned_ms"], 3)
     print(json.dumps(out))
 
 
