@@ -23,8 +23,9 @@ SOURCES = {
     #  The tune-mode pipeline is cut by kernel family -- bpsk_front_reg / bpsk_fm / bpsk_fm_f32 / bpsk_front / bpsk_tail -- so that none of them is the
     #  whole build)
     "bpsk_front_reg.hip": ["-ffp-contract=off"],
-    "bpsk_fm.hip": ["-ffp-contract=off"],
-    "bpsk_fm_f32.hip": ["-ffp-contract=off"],
+    # (no atomic optimiser, as for bpsk_acq.hip below: k_fm's and k_fm_f32's ticket is wanted a front half after it is asked for)
+    "bpsk_fm.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+    "bpsk_fm_f32.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
     "bpsk_front.hip": ["-ffp-contract=off"],
     "bpsk_tail.hip": ["-ffp-contract=off"],
     "runtime.hip": [],

@@ -139,6 +139,12 @@ __device__ unsigned long long g_fm_clk[256][64];  // [blockIdx & 255][phase]: sa
 #define FM_CLK(i) do {} while (0)
 #endif
 
+#ifdef JSDR_X_WGCLK  // timing probe: every workgroup's first and last s_memrealtime tick (10 ns, one clock for the chip) and its tiles, a row per launch
+constexpr int WGCLK_SLOTS = 128, WGCLK_WGS = 1024;
+__device__ unsigned long long g_fm_wgclk[WGCLK_SLOTS][WGCLK_WGS][3];
+static long long g_wgclk_log[WGCLK_SLOTS][4];  // per launch row: tiles, grid, ticket form, launch number
+#endif
+
 // The stream's edge images for k_fm: E[0 .. 2*FM_EDGE) = samples -FM_EDGE .. FM_EDGE-1, E[2*FM_EDGE .. 4*FM_EDGE) = samples
 // L-FM_EDGE .. L+FM_EDGE-1 as raw int16 pairs: the previous call's 26 samples before sample 0 (kept DC-corrected: the
 // correction is taken off again, k_fm's conversion re-applies it -- 16-bit wrap-around both ways, so exactly the stored
@@ -259,9 +265,25 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
 #ifdef JSDR_X_CLK
     unsigned long long clk_acc_[6] = {0, 0, 0, 0, 0, 0}, clk_last_ = 0;
 #endif
+#ifdef JSDR_X_WGCLK
+    const unsigned long long wgclk0 = __builtin_amdgcn_s_memrealtime();
+    unsigned long long wgclk_n = 0;
+#endif
     const long long nwork = (long long)a.ntiles * a.nstreams;
+    // The TICKET form (a.tickets: the launch is held to a CU share, jsdr_bpsk_set_cu_share -- persistent workgroups beside another
+    // kernel's): a statically shared launch lasts as long as its slowest workgroup, and here a workgroup's pace depends on whom it
+    // shares its CU with and on when it was placed, so the tiles are handed out as the workgroups get through them.  Work item
+    // blockIdx.x first, then gridDim.x + ticket: one atomicAdd of thread 0 on the launch's counter (zeroed on the stream in front of
+    // the launch), taken behind the front half and handed round through LDS at the tile's last barrier -- a whole matched half after
+    // the request, so nobody waits for its round trip.  (Taken at the top of the tile its answer is one register more where the
+    // kernel has most alive, in the front half: 113-115 VGPRs against 111-113.)  Measured at the headline step, beside k_fft and
+    // k_tail8 (profiles/r09_ticket_handout.md): the workgroups of a launch used to end between 24.1 and 27.6 ms, and end within 25 us
+    // of each other at 27.0 ms; the step went from 33.26-33.34 to 32.98-33.03 ms on one part and from 36.2-36.4 to 34.0-34.1 on a
+    // slower one.  (k_fft keeps its fixed stride: its ticket form -- alone or together with this one -- made the step slower.)
+    const bool tickets = a.tickets != nullptr;
+    int *tkL = reinterpret_cast<int *>(sc + 512);  // [1]
 #pragma unroll 1
-    for (long long work = blockIdx.x; work < nwork; work += gridDim.x) {
+    for (long long work = blockIdx.x; work < nwork; work = tickets ? (long long)gridDim.x + (unsigned)__builtin_amdgcn_readfirstlane(tkL[0]) : work + gridDim.x) {
     const int s = (int)(work / a.ntiles);
     const long long G = a.tile0 + (long long)(65 * FM_NB) * (work % a.ntiles);
     const int jrel0 = (int)(G - 64 - a.g_first);  // call-relative output index of X[0] (negative in the first tile)
@@ -458,6 +480,8 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
     FM_CLK(1);  // front half
     __syncthreads();
     FM_CLK(3);  // barrier after the front half
+    unsigned tk = 0;
+    if (tickets && threadIdx.x == 0) tk = atomicAdd(a.tickets, 1u);
     // ---- the call's last 64 VCO-mixed samples are the next call's halo; every sample is owned by one tile
     if (jrel0 + FM_NT > nds - 64) {  // uniform
         double2 *dmh_new = a.dmh_new + (long long)s * 64;
@@ -570,9 +594,27 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
 #endif
     }
     FM_CLK(4);  // matched half
-    __syncthreads();  // the next work item reuses the image
-    FM_CLK(5);  // barrier after the matched half
+    {
+        // (pinned here by an opaque zero: left alone the compiler moves this store up beside the atomic -- same condition -- and
+        //  waits for the ticket's round trip on the spot, as in bpsk_acq.hip)
+        int zlate = 0;
+        asm volatile("" : "+v"(zlate));
+        if (tickets && threadIdx.x == 0) tkL[0] = (int)tk + zlate;
     }
+    __syncthreads();  // the next work item reuses the image, and takes its number from tkL (written next behind the next matched half)
+    FM_CLK(5);  // barrier after the matched half
+#ifdef JSDR_X_WGCLK
+    wgclk_n++;
+#endif
+    }
+#ifdef JSDR_X_WGCLK
+    if (threadIdx.x == 0 && blockIdx.x < WGCLK_WGS) {
+        unsigned long long *c = g_fm_wgclk[a.wgclk_slot][blockIdx.x];
+        c[0] = wgclk0;
+        c[1] = __builtin_amdgcn_s_memrealtime();
+        c[2] = wgclk_n;
+    }
+#endif
 #ifdef JSDR_X_CLK
     if ((threadIdx.x & 63) == 0)
         for (int i = 0; i < 6; i++) atomicAdd(&g_fm_clk[blockIdx.x & 255][(threadIdx.x >> 6) * 8 + i], clk_acc_[i]);
@@ -616,7 +658,7 @@ static int launch_fm_t(const FmArgs &a_in, bool mix, bool dc, bool fast, int nst
                        int *phase)
 {
     *phase = -1;
-    const size_t lds = (size_t)FM_NT * sizeof(double2) + 512 * sizeof(double);
+    const size_t lds = (size_t)FM_NT * sizeof(double2) + 512 * sizeof(double) + sizeof(double);  // image, sin / cos table, ticket
     const long long span = 65LL * FM_NB;
     const long long ntiles = (a_in.g_first + a_in.nds - a_in.tile0 + span - 1) / span;
     FmArgs a = a_in;
@@ -631,6 +673,21 @@ static int launch_fm_t(const FmArgs &a_in, bool mix, bool dc, bool fast, int nst
     if (a.grid_limit > 0 && gx > a.grid_limit) gx = a.grid_limit;
     *items = ntiles * nstreams;
     *grid_out = gx;
+    // held to a share, the workgroups take their tiles by ticket (k_fm); a launch with a workgroup per tile has nothing to hand out
+    if (!(a.grid_limit > 0 && gx < ntiles * nstreams && ntiles * nstreams + gx < 0x7fffffffLL)) a.tickets = nullptr;
+#ifdef JSDR_X_WGCLK
+    {
+        static int wgclk_seq = 0;
+        static const bool wgclk_static = getenv("JSDR_X_WGCLK_STATIC") != nullptr;  // the probe's "before": the share without tickets
+        if (wgclk_static) a.tickets = nullptr;
+        a.wgclk_slot = wgclk_seq % WGCLK_SLOTS;
+        g_wgclk_log[a.wgclk_slot][0] = ntiles * nstreams;
+        g_wgclk_log[a.wgclk_slot][1] = gx;
+        g_wgclk_log[a.wgclk_slot][2] = a.tickets != nullptr;
+        g_wgclk_log[a.wgclk_slot][3] = wgclk_seq++;
+    }
+#endif
+    if (a.tickets) JSDR_HIP_TRY(hipMemsetAsync(a.tickets, 0, sizeof(unsigned), st));
     const dim3 grid((unsigned)gx), block(FM_THREADS);
 #define JSDR_FM_LAUNCH_PH(MIX, DC, FAST, SMALL, PH)                                                             \
     do {                                                                                                        \
@@ -684,6 +741,21 @@ int launch_fm(const FmArgs &a, int decim, bool mix, bool dc, bool fast, int nstr
 
 void bpsk_fm_clocks_report()
 {
+#ifdef JSDR_X_WGCLK
+    {
+        const char *path = getenv("JSDR_X_WGCLK_OUT_FM");
+        FILE *f = fopen(path ? path : "wgclk_fm.csv", "w");
+        static unsigned long long cc[WGCLK_SLOTS][WGCLK_WGS][3];
+        if (f && hipMemcpyFromSymbol(cc, HIP_SYMBOL(g_fm_wgclk), sizeof(cc)) == hipSuccess) {
+            fprintf(f, "launch,items,grid,ticket,wg,t0,t1,n\n");
+            for (int sl = 0; sl < WGCLK_SLOTS; sl++)
+                for (int w = 0; w < WGCLK_WGS && w < g_wgclk_log[sl][1]; w++)
+                    fprintf(f, "%lld,%lld,%lld,%lld,%d,%llu,%llu,%llu\n", g_wgclk_log[sl][3], g_wgclk_log[sl][0], g_wgclk_log[sl][1],
+                            g_wgclk_log[sl][2], w, cc[sl][w][0], cc[sl][w][1], cc[sl][w][2]);
+        }
+        if (f) fclose(f);
+    }
+#endif
 #ifdef JSDR_X_CLK
     {
         static unsigned long long cc[256][64];

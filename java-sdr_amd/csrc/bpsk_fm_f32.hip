@@ -82,8 +82,12 @@ __global__ __launch_bounds__(FM_THREADS, 2) void k_fm_f32(FmF32Args fa)
     double *sc = reinterpret_cast<double *>(smem + FM_NT * sizeof(double2));  // [512]
     for (int i = threadIdx.x; i < 512; i += FM_THREADS) sc[i] = a.sincos[i];
     const long long nwork = (long long)a.ntiles * a.nstreams;
+    // the ticket form of a launch held to a CU share, as k_fm's: item blockIdx.x first, then gridDim.x + ticket; thread 0 takes the
+    // ticket behind the front half and hands it round through LDS at the tile's last barrier
+    const bool tickets = a.tickets != nullptr;
+    int *tkL = reinterpret_cast<int *>(sc + 512);  // [1]
 #pragma unroll 1
-    for (long long work = blockIdx.x; work < nwork; work += gridDim.x) {
+    for (long long work = blockIdx.x; work < nwork; work = tickets ? (long long)gridDim.x + (unsigned)__builtin_amdgcn_readfirstlane(tkL[0]) : work + gridDim.x) {
     const int s = (int)(work / a.ntiles);
     const long long G = a.tile0 + (long long)(65 * FM_NB) * (work % a.ntiles);
     const int jrel0 = (int)(G - 64 - a.g_first);  // call-relative output index of X[0] (negative in the first tile)
@@ -235,6 +239,8 @@ __global__ __launch_bounds__(FM_THREADS, 2) void k_fm_f32(FmF32Args fa)
         }
     }
     __syncthreads();
+    unsigned tk = 0;
+    if (tickets && threadIdx.x == 0) tk = atomicAdd(a.tickets, 1u);
     // ---- the call's last 64 VCO-mixed samples are the next call's halo; every sample is owned by one tile
     if (jrel0 + FM_NT > nds - 64) {  // uniform
         double2 *dmh_new = a.dmh_new + (long long)s * 64;
@@ -303,7 +309,12 @@ __global__ __launch_bounds__(FM_THREADS, 2) void k_fm_f32(FmF32Args fa)
             if (rel >= 0 && rel < nds) y[rel] = X[o];
         }
     }
-    __syncthreads();  // the next work item reuses the image
+    {
+        int zlate = 0;  // (pinned here, behind the matched half: see k_fm)
+        asm volatile("" : "+v"(zlate));
+        if (tickets && threadIdx.x == 0) tkL[0] = (int)tk + zlate;
+    }
+    __syncthreads();  // the next work item reuses the image, and takes its number from tkL
     }
 }
 
@@ -323,7 +334,7 @@ int launch_fm_prep_f32(const EdgeF32Args &ea, const HistArgs &ha, hipStream_t st
 template <int D, int R>
 static int launch_fm_f32_t(const FmF32Args &a_in, bool mix, int nstreams, hipStream_t st, long long *items, long long *grid_out)
 {
-    const size_t lds = (size_t)FM_NT * sizeof(double2) + 512 * sizeof(double);
+    const size_t lds = (size_t)FM_NT * sizeof(double2) + 512 * sizeof(double) + sizeof(double);  // image, sin / cos table, ticket
     const long long span = 65LL * FM_NB;
     const long long ntiles = (a_in.a.g_first + a_in.a.nds - a_in.a.tile0 + span - 1) / span;
     FmF32Args a = a_in;
@@ -333,6 +344,9 @@ static int launch_fm_f32_t(const FmF32Args &a_in, bool mix, int nstreams, hipStr
     if (a.a.grid_limit > 0 && gx > a.a.grid_limit) gx = a.a.grid_limit;
     *items = ntiles * nstreams;
     *grid_out = gx;
+    // held to a share, the workgroups take their tiles by ticket; a launch with a workgroup per tile has nothing to hand out
+    if (!(a.a.grid_limit > 0 && gx < ntiles * nstreams && ntiles * nstreams + gx < 0x7fffffffLL)) a.a.tickets = nullptr;
+    if (a.a.tickets) JSDR_HIP_TRY(hipMemsetAsync(a.a.tickets, 0, sizeof(unsigned), st));
     const dim3 grid((unsigned)gx), block(FM_THREADS);
 #define JSDR_FM32_LAUNCH(MIX, SMALL)                                              \
     do {                                                                          \

@@ -108,6 +108,7 @@ struct jsdr_bpsk {
     DevBuf<int> hist_bad;          // k_hist_convert's "not an int16 sample" flag
     DevBuf<int> amax;              // fast variant: [S] running maximum of |int16 sample| (float bits)
     DevBuf<SnapPack> snap_dev;     // receive(): the packed results of the call, fetched in one copy (k_snapshot_pack)
+    DevBuf<unsigned> fm_tickets;   // [1] k_fm / k_fm_f32 held to a CU share: the launch's tile counter (zeroed on the stream by the launcher)
     DevBuf<int> fm_edges;          // k_fm: [S][4 * FM_EDGE] the stream around sample 0 and around the last sample (k_fm_edges)
     DevBuf<float2> fm_edges_f32;   // k_fm_f32: the same images as float pairs (k_fm_prep_f32); allocated by the first jsdr_bpsk_batch_f32
     bool f32_batch = false;        // the call in progress is a jsdr_bpsk_batch_f32: float input may take the fused kernel (receive_f32's
@@ -1493,6 +1494,7 @@ static int bpsk_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev,
         ma.first_out = first_out;
         ma.amax = h->amax.p;
         ma.grid_limit = h->share_wgs_per_cu * h->num_cu;  // (jsdr_bpsk_set_cu_share has asked for the CU count)
+        ma.tickets = h->fm_tickets.p;
         ma.trot = h->cur.mix == 1 ? h->cur.trot : -1;
         if (rawf_dev) {
             EdgeF32Args ea;
@@ -1792,7 +1794,7 @@ int jsdr_bpsk_create(jsdr_bpsk **out, int rate, int nsamples_per_frame, int tuni
               // (one frame; a 1-stream handle's receive() sends the schedule's tables behind it in the same copy)
               h->stage_raw.alloc((size_t)nsamples_per_frame * 2 + (nstreams == 1 ? ((do_fft ? sizeof(double2) : 1) * (size_t)h->max_ds + sizeof(double2) * (256 + FM_TABLE_SLACK) + 256) / 4 : 0)) == JSDR_OK &&
               h->ds_taps_dev.alloc(32) == JSDR_OK &&
-              h->dmh[0].alloc(S * 64) == JSDR_OK && h->dmh[1].alloc(S * 64) == JSDR_OK && h->hist_bad.alloc(1) == JSDR_OK && h->amax.alloc(S) == JSDR_OK && h->fm_edges.alloc(S * 4 * FM_EDGE) == JSDR_OK && h->snap_dev.alloc(1) == JSDR_OK && h->tcs.alloc(2 * (256 + FM_TABLE_SLACK)) == JSDR_OK;
+              h->dmh[0].alloc(S * 64) == JSDR_OK && h->dmh[1].alloc(S * 64) == JSDR_OK && h->hist_bad.alloc(1) == JSDR_OK && h->amax.alloc(S) == JSDR_OK && h->fm_tickets.alloc(1) == JSDR_OK && h->fm_edges.alloc(S * 4 * FM_EDGE) == JSDR_OK && h->snap_dev.alloc(1) == JSDR_OK && h->tcs.alloc(2 * (256 + FM_TABLE_SLACK)) == JSDR_OK;
     if (ok && nstreams == 1) {
         // [frame | ktu | kvco | vco_cs | tcs] + alignment slack, then the SnapPack slot (not handed out by h2d_call)
         const size_t need = sizeof(float) * 2 * (size_t)nsamples_per_frame + ((size_t)h->max_batch + 26) + (size_t)h->max_ds +

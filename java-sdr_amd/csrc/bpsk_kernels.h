@@ -115,6 +115,11 @@ struct FmArgs {
     int *amax;                  // FAST: [S] running maximum of |int16 sample| per stream, float bits (never reset)
     int ntiles, nstreams;       // work items = ntiles x nstreams, stream-major; the grid strides over them
     int grid_limit;             // > 0: at most that many workgroups, striding over the work items (jsdr_bpsk_set_cu_share)
+    unsigned *tickets;          // the handle's tile counter for such a launch, which hands the items out by ticket (k_fm, k_fm_f32; the
+                                // launcher zeroes it on the stream, and drops it where every tile has a workgroup); nullptr: none
+#ifdef JSDR_X_WGCLK
+    int wgclk_slot;             // timing probe: the launch's row of the per-workgroup start / end ticks
+#endif
     int trot;                   // >= 0: tper == 8 and entry e of tcs is phase e + trot of the 8-phase tuner, whose exact factors k_fm
                                 // has a form for (Schedule::trot, bpsk_tuner.h); -1: any other table, the generic form
 };

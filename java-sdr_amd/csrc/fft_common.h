@@ -137,6 +137,9 @@ struct FftArgs {
     int rate;
     int ic, qc;
     int split = 0;  // 1: frame f of the kernel is the even (f&1 == 0) / odd half of input frame f>>1 (2N samples)
+#ifdef JSDR_X_WGCLK
+    int wgclk_slot = 0;  // timing probe (fft_psd.hip): the launch's row of the per-workgroup start / end ticks
+#endif
 };
 
 struct Best {

@@ -289,6 +289,13 @@ __device__ __forceinline__ void fft_frame(const FftArgs &a, long long frame, lon
     }
 }
 
+#ifdef JSDR_X_WGCLK  // timing probe (round 9, never defined in the product build): every workgroup's first and last s_memrealtime tick
+                     // (10 ns, one clock for the chip -- s_memtime counts shader clocks from a base of its own on every XCD) and its
+                     // frame groups, a row per launch; written to a file when a handle goes (profiles/r09_ticket_handout.md)
+constexpr int WGCLK_SLOTS = 128, WGCLK_WGS = 1024;
+__device__ unsigned long long g_fft_wgclk[WGCLK_SLOTS][WGCLK_WGS][3];
+#endif
+
 // TWG: the twiddle tables are read from global memory (L1 / L2) instead of a per-workgroup copy in LDS
 template <int N, int T, int FPB, int IN, int OUT, int R0, int R1, int R2, int R3, bool TWG = false>
 __global__ __launch_bounds__(T *FPB, (N == 2048 ? 4 : 1)) void k_fft(FftArgs a)
@@ -301,6 +308,10 @@ __global__ __launch_bounds__(T *FPB, (N == 2048 ? 4 : 1)) void k_fft(FftArgs a)
     float *red_val = reinterpret_cast<float *>(bufs + (size_t)FPB * FE);  // [FPB*NW]
     int *red_idx = reinterpret_cast<int *>(red_val + FPB * ((T + 63) / 64));
     const float2 *tw_lds = TWG ? a.tw : tw_own;
+#ifdef JSDR_X_WGCLK
+    const unsigned long long wgclk0 = __builtin_amdgcn_s_memrealtime();
+    unsigned long long wgclk_n = 0;
+#endif
 
     const int tid_b = threadIdx.x;
     if constexpr (!TWG) {
@@ -325,7 +336,18 @@ __global__ __launch_bounds__(T *FPB, (N == 2048 ? 4 : 1)) void k_fft(FftArgs a)
         fft_frame<N, T, IN, OUT, R0, R1, R2, R3>(a, frame_of(g), frame_of(gn < ngroups ? gn : g), tid, buf, tw_lds, red_val,
                                                  red_idx, fib, raw);
         __syncthreads();
+#ifdef JSDR_X_WGCLK
+        wgclk_n++;
+#endif
     }
+#ifdef JSDR_X_WGCLK
+    if (tid_b == 0 && blockIdx.x < WGCLK_WGS) {
+        unsigned long long *c = g_fft_wgclk[a.wgclk_slot][blockIdx.x];
+        c[0] = wgclk0;
+        c[1] = __builtin_amdgcn_s_memrealtime();
+        c[2] = wgclk_n;
+    }
+#endif
 }
 
 template <int N, int FPB, int T, int R0, int R1, int R2, int R3, bool TWG = false>
@@ -407,6 +429,24 @@ struct jsdr_fft {
     int share_wgs_per_cu = 0;  // jsdr_fft_set_cu_share: workgroups per CU the batch kernel is held to (0: all it can use)
 };
 
+#ifdef JSDR_X_WGCLK
+static long long g_wgclk_log[WGCLK_SLOTS][3];  // per launch row: frame groups, grid, launch number
+static void fft_wgclk_report()
+{
+    const char *path = getenv("JSDR_X_WGCLK_OUT");
+    FILE *f = fopen(path ? path : "wgclk_fft.csv", "w");
+    static unsigned long long cc[WGCLK_SLOTS][WGCLK_WGS][3];
+    if (f && hipMemcpyFromSymbol(cc, HIP_SYMBOL(g_fft_wgclk), sizeof(cc)) == hipSuccess) {
+        fprintf(f, "launch,items,grid,ticket,wg,t0,t1,n\n");
+        for (int sl = 0; sl < WGCLK_SLOTS; sl++)
+            for (int w = 0; w < WGCLK_WGS && w < g_wgclk_log[sl][1]; w++)
+                fprintf(f, "%lld,%lld,%lld,0,%d,%llu,%llu,%llu\n", g_wgclk_log[sl][2], g_wgclk_log[sl][0], g_wgclk_log[sl][1], w,
+                        cc[sl][w][0], cc[sl][w][1], cc[sl][w][2]);
+    }
+    if (f) fclose(f);
+}
+#endif
+
 static int fft_run(jsdr_fft *h, const void *in_dev, int in_kind, int out_kind, long long nframes, int ic, int qc,
                    float *out_dev, hipStream_t s)
 {
@@ -480,6 +520,15 @@ static int fft_run(jsdr_fft *h, const void *in_dev, int in_kind, int out_kind, l
     int grid = (int)(groups < cap ? groups : cap);
     h->last_items = groups;
     h->last_grid = grid;
+#ifdef JSDR_X_WGCLK
+    {
+        static int wgclk_seq = 0;
+        a.wgclk_slot = wgclk_seq % WGCLK_SLOTS;
+        g_wgclk_log[a.wgclk_slot][0] = groups;
+        g_wgclk_log[a.wgclk_slot][1] = grid;
+        g_wgclk_log[a.wgclk_slot][2] = wgclk_seq++;
+    }
+#endif
     l.launch(a, grid, s);
     JSDR_LAUNCH_CHECK();
     return JSDR_OK;
@@ -596,6 +645,12 @@ int jsdr_fft_create(jsdr_fft **out, int n, int rate)
 
 int jsdr_fft_destroy(jsdr_fft *h)
 {
+#ifdef JSDR_X_WGCLK
+    if (h) {
+        (void)hipDeviceSynchronize();
+        fft_wgclk_report();
+    }
+#endif
     delete h;
     return JSDR_OK;
 }
