@@ -420,6 +420,34 @@ int jsdr_bpsk_plan_stream_ramps(jsdr_bpsk *h, const int32_t *stream, const int64
  * NULL).  nev = 0 with null arrays is jsdr_bpsk_tuner_walk_host */
 int jsdr_bpsk_tuner_walk_ramp_host(double tu0, double tu_inc, int64_t n, int rate, const int64_t *at_sample, const double *tuning_at,
                                    const double *slope_at, int64_t nev, uint16_t *k9_out, double *tu_end, double *inc_end);
+/* Tuned channel handle: ninputs x nchannels lock-step demodulators in the tune mode, EVERY CHANNEL OF EVERY INPUT WITH ITS OWN
+ * TUNING, the channels of an input reading ONE input row -- several satellites inside one wideband capture, each on its own
+ * Doppler curve, without the capture repeated once per satellite in device memory.  It is a tuned handle (above) of
+ * ninputs x nchannels streams: channel c of input i is stream i * nchannels + c, as on every channel handle, and is created with
+ * tuning_hz[i * nchannels + c].  1 <= nchannels <= 16, ninputs x nchannels <= 65535.
+ *   Batch calls: jsdr_bpsk_batch_i16 (with ic, qc) and jsdr_bpsk_batch_f32 take the stride BETWEEN INPUTS, as on channel
+ *     handles; ragged call lengths as on tuned handles.  The 26-sample input history is kept per input; the two input forms may
+ *     alternate under the channel handle's rule (converted, or the int16 call refused when a float of it is no (float)s/32767f).
+ *   Result: stream i * nchannels + c is bit-identical to stream i * nchannels + c of a jsdr_bpsk_create_tuned handle of
+ *     ninputs x nchannels streams that reads a buffer in which every input is repeated nchannels times -- and so to the
+ *     one-stream handle named there: bits, FEC results, counters, the 18 state doubles, decoded[], the (fi, fq) trace.
+ *   Per-stream calls, with that stream numbering, exactly as on a jsdr_bpsk_create_tuned handle: set_stream_tuning /
+ *     set_stream_tunings / get_stream_tuning, jsdr_bpsk_plan_stream_tunings, jsdr_bpsk_plan_stream_ramps,
+ *     jsdr_bpsk_planned_tunings -- validation, messages, one-shot plans that survive a refused call, a ramp's tuning of the call's
+ *     last sample afterwards.  set_tuning, set_mode(0, do_up), reconfigure(t, 0, do_up) and get_control as on a tuned handle.
+ *     jsdr_bpsk_channel_info reports ninputs x nchannels; the per-stream getters, pack_slots, the slot layout and the profile
+ *     calls apply unchanged.
+ *   On the device: the walk is the tuned handle's ("k_tuner_walk" in the profile, over ninputs x nchannels rows); the front end
+ *     is "k_chan_front_pst", "k_chan_front_pst_plan" or "k_chan_front_pst_ramp" (jsdr_bpsk_front_kernel): a tile of an input is
+ *     read, DC-corrected and converted once, and mixed for every channel with the indices expanded from that channel's
+ *     checkpoints.  Memory per stream as a tuned handle's; the input is ninputs rows, not ninputs x nchannels.
+ * JSDR_ERR, the handle unchanged, each checked before any device work: null pointers, bad geometry, a non-finite tuning or one
+ * >= rate at create; do_fft = 1 by any route; set_variant(FAST); receive_i16 / receive_f32; the per-channel calls
+ * (set_channel_tuning, set_channel_mode, get_channel_control: the message names the per-stream call to use); jsdr_bpsk_save /
+ * _restore / _state_bytes (a record carries a per-stream input history, this handle keeps one per input).
+ * Not covered on this handle: FFT-acquire, the FAST variant, checkpoints, jsdr_group_*, receive_*, JNI / Java classes. */
+int jsdr_bpsk_create_tuned_channels(jsdr_bpsk **h, int rate, int nsamples_per_frame, int ninputs, int nchannels,
+                                    const double *tuning_hz /*[ninputs * nchannels]*/, int64_t max_batch_samples);
 /* Checkpoints: the state of a range of streams out of a handle and into one -- across a restart, a library upgrade, another
  * machine, or between handles (a split is two saves with ranges, a merge two restores at offsets).  A blob is self-contained,
  * versioned (format 1) and position-independent: little-endian fixed-width fields, a 192-byte header with the sizes and a

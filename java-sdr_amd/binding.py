@@ -715,6 +715,43 @@ class BpskTuned(Bpsk):
         return n.value
 
 
+class BpskTunedChannels(BpskTuned):
+    """`ninputs` inputs x `nchannels` FUNcubeBPSKDemod instances in the tune mode, every channel of every input with its own tuning,
+    the channels of an input reading one input row (jsdr_bpsk_create_tuned_channels).  Channel c of input i is stream
+    i * nchannels + c and is created with tunings[i * nchannels + c]; retunes, plans and getters by stream, as BpskTuned's."""
+
+    def __init__(self, rate, blen, ninputs, nchannels, tunings, max_batch_samples=None, size=4):
+        tunings = [float(t) for t in tunings]
+        if len(tunings) != int(ninputs) * int(nchannels):
+            raise ValueError("BpskTunedChannels: one tuning per channel of every input (ninputs * nchannels of them)")
+        self.samples = blen // size
+        self.ninputs = int(ninputs)
+        self.nchannels = int(nchannels)
+        self.nstreams = self.ninputs * self.nchannels
+        self.max_batch = max_batch_samples or self.samples
+        self.h = C.c_void_p()
+        tu = (C.c_double * max(self.nstreams, 1))(*tunings)
+        _check(lib().jsdr_bpsk_create_tuned_channels(C.byref(self.h), rate, self.samples, self.ninputs, self.nchannels,
+                                                     tu if tunings else None, C.c_int64(self.max_batch)),
+               "jsdr_bpsk_create_tuned_channels")
+
+    def stream(self, inp, ch):
+        return inp * self.nchannels + ch
+
+    def channel_info(self):
+        a, b = C.c_int(), C.c_int()
+        _check(lib().jsdr_bpsk_channel_info(self.h, C.byref(a), C.byref(b)), "jsdr_bpsk_channel_info")
+        return a.value, b.value
+
+    def batch_i16(self, raw_dev, input_stride_i16, nsamples, ic=0, qc=0, stream=None):
+        """input_stride_i16: between INPUTS"""
+        Bpsk.batch_i16(self, raw_dev, input_stride_i16, nsamples, ic, qc, stream)
+
+    def batch_f32(self, iq_dev, input_stride_f32, nsamples, stream=None):
+        """input_stride_f32: between INPUTS"""
+        Bpsk.batch_f32(self, iq_dev, input_stride_f32, nsamples, stream)
+
+
 class BpskBlobInfo(C.Structure):
     _fields_ = [("version", C.c_int32), ("kind", C.c_int32), ("rate", C.c_int32), ("nsamples_per_frame", C.c_int32),
                 ("nstreams", C.c_int32), ("do_fft", C.c_int32), ("do_up", C.c_int32), ("seam", C.c_int32),

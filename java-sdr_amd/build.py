@@ -53,6 +53,7 @@ SOURCES = {
     "bpsk_acqg.hip": ["-ffp-contract=off"],
     "bpsk_chan.hip": ["-ffp-contract=off"],
     "bpsk_pst.hip": ["-ffp-contract=off"],
+    "bpsk_chan_pst.hip": ["-ffp-contract=off"],
     # (checkpoints: the gather / scatter kernels do no arithmetic; the blob codec is host code only -- flagged like their neighbours)
     "bpsk_state.hip": ["-ffp-contract=off"],
     "bpsk_blob.hip": ["-ffp-contract=off"],

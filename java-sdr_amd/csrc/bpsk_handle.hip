@@ -242,6 +242,10 @@ struct jsdr_bpsk {
     DevBuf<unsigned short> pst_kh[2];  // [S][32] the 9-bit indices of the 26 samples before the next call, double-buffered like hist_in
     int pst_kh_cur = 0;
     DevBuf<int> pst_ids;               // [S] the streams an action zeroes dmMaxCorr in (k_reset_maxcorr_list)
+    // tuned channel handle (jsdr_bpsk_create_tuned_channels): a tuned handle of pst_nin x pst_nch streams whose pst_nch channels of
+    // an input read ONE input row (k_chan_front_pst, bpsk_chan_pst.hip) -- the input, its stride and its 26-sample history are per
+    // input, everything else per stream as above.  0: a tuned handle of jsdr_bpsk_create_tuned (nch stays 0 on both)
+    int pst_nin = 0, pst_nch = 0;
     // a tuning plan (jsdr_bpsk_plan_stream_tunings, jsdr_bpsk_plan_stream_ramps): retunes inside the next call, copied to the device
     // when it is given.  The call that takes it clears pst_plan_n; the device copy stays until the next plan replaces it, a plan of 0
     // entries or destroy.
@@ -270,6 +274,12 @@ static bool stream_fft(const jsdr_bpsk *h, int stream)
 static size_t fft_state_at(const jsdr_bpsk *h, int stream)
 {
     return h->nch > 0 ? (size_t)(stream % h->nch) * (size_t)h->nin + (size_t)(stream / h->nch) : (size_t)stream;
+}
+
+// the input rows of a tuned handle's call: its streams, or the inputs of a tuned channel handle
+static int pst_rows_in(const jsdr_bpsk *h)
+{
+    return h->pst_nch > 0 ? h->pst_nin : h->nstreams;
 }
 
 static void pst_plan_clear(jsdr_bpsk *h)  // no plan pends (the device copy stays until a plan replaces it)
@@ -1152,8 +1162,9 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
 {
     JSDR_REQUIRE(raw_dev || rawf_dev, "bpsk: null input");
     JSDR_REQUIRE(L > 0 && L <= h->max_batch, "bpsk: nsamples=%lld outside (0, max_batch_samples=%lld]", L, h->max_batch);
-    JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nstreams == 1 || stride_i16 >= 2 * L),
-                 "bpsk: stream stride %lld too small for %lld samples", stride_i16, L);
+    const int rows_in = pst_rows_in(h);  // (a tuned channel handle: the stride is between inputs)
+    JSDR_REQUIRE((stride_i16 & 1) == 0 && (rows_in == 1 || stride_i16 >= 2 * L),
+                 "bpsk: %s stride %lld too small for %lld samples", h->pst_nch > 0 ? "input" : "stream", stride_i16, L);
     // the previous call may have come through the other input form (before anything moves on: the conversion can refuse)
     const bool planned = h->pst_plan_n > 0;
     JSDR_REQUIRE(!planned || L > h->pst_plan_max_at, "bpsk: the pending tuning plan has an entry at sample %lld, the call has %lld samples; the "
@@ -1166,7 +1177,7 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
                          "reaches %g Hz at the call's last sample (%lld), not a finite value below the rate (%d Hz); the handle is unchanged and "
                          "the plan stays pending", pl.entry, pl.stream, pl.at, t_end, L - 1, h->rate);
         }
-    if (hist_form(h, rawf_dev != nullptr, h->nstreams, st) != JSDR_OK) return JSDR_ERR;
+    if (hist_form(h, rawf_dev != nullptr, rows_in, st) != JSDR_OK) return JSDR_ERR;
     const int S = h->nstreams;
     const int first_out = h->decim - 1 - h->dsCnt;
     const long long g_first = h->n_ds;
@@ -1201,7 +1212,31 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
         ProfScope ps(h, PK_TWALK, st);
         if (launch_tuner_walk(wa, plan, rplan, st) != JSDR_OK) return JSDR_ERR;
     }
-    if (nds > 0) {
+    if (nds > 0 && h->pst_nch > 0) {  // every input read once, its channels' rows fed from the walk's checkpoints
+        PstChanFrontArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.raw = rawf ? reinterpret_cast<const int *>(rawf) : raw;
+        fa.stride_pairs = stride_pairs;
+        fa.ic = ic;
+        fa.qc = qc;
+        fa.hist = h->hist_in[h->hist_cur].p;
+        fa.inc = h->pst_inc.p;
+        fa.ckpt = h->pst_ckpt.p;
+        fa.ckpt_stride = h->pst_ckpt_stride;
+        fa.kh_old = h->pst_kh[h->pst_kh_cur].p;
+        fa.kvco = kvco_p;
+        fa.sc9 = h->sincos9.p;
+        fa.ds_taps = h->ds_taps_dev.p;
+        fa.dm = h->dm.p;
+        fa.dm_stride = h->dm_stride;
+        fa.nds = nds;
+        fa.first_out = first_out;
+        fa.decim = h->decim;
+        fa.nch = h->pst_nch;
+        ProfScope ps(h, PK_FRONT, st);
+        h->front_name = ramp ? "k_chan_front_pst_ramp" : planned ? "k_chan_front_pst_plan" : "k_chan_front_pst";
+        if (launch_chan_front_pst(fa, h->pst_nin, rawf != nullptr, plan, rplan, st) != JSDR_OK) return JSDR_ERR;
+    } else if (nds > 0) {
         PstFrontArgs fa;
         memset(&fa, 0, sizeof(fa));
         fa.raw = rawf ? reinterpret_cast<const int *>(rawf) : raw;
@@ -1226,7 +1261,7 @@ static int pst_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
         if (launch_front_pst(fa, S, rawf != nullptr, plan, rplan, st) != JSDR_OK) return JSDR_ERR;
     }
     h->pst_kh_cur ^= 1;
-    if (run_hist_in(h, hist_args(h, raw, rawf, stride_pairs, L, ic, qc, S), st) != JSDR_OK) return JSDR_ERR;
+    if (run_hist_in(h, hist_args(h, raw, rawf, stride_pairs, L, ic, qc, rows_in), st) != JSDR_OK) return JSDR_ERR;
     const int yb = h->y_cur;
     if (wait_tail(h, yb, st) != JSDR_OK) return JSDR_ERR;
     if (nds > 0 && run_matched(h, yb, nds, g_first, st) != JSDR_OK) return JSDR_ERR;
@@ -2032,6 +2067,8 @@ int jsdr_bpsk_fm_form(jsdr_bpsk *h, int *specialised, int *phase)
 int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
 {
     JSDR_REQUIRE(h && raw_host, "jsdr_bpsk_receive_i16: null argument");
+    JSDR_REQUIRE(h->pst_nch == 0, "jsdr_bpsk_receive_i16: a tuned channel handle (jsdr_bpsk_create_tuned_channels) takes batches only "
+                 "(jsdr_bpsk_batch_i16); the handle is unchanged");
     JSDR_REQUIRE(!h->pst, "jsdr_bpsk_receive_i16: a tuned handle (jsdr_bpsk_create_tuned) takes batches only; receive() is the 1-stream "
                  "form of jsdr_bpsk_create");
     JSDR_REQUIRE(h->nstreams == 1 || (h->nch > 0 && h->nin == 1),
@@ -2060,6 +2097,8 @@ int jsdr_bpsk_receive_i16(jsdr_bpsk *h, const int16_t *raw_host, int ic, int qc)
 int jsdr_bpsk_receive_f32(jsdr_bpsk *h, const float *iq_host)
 {
     JSDR_REQUIRE(h && iq_host, "jsdr_bpsk_receive_f32: null argument");
+    JSDR_REQUIRE(h->pst_nch == 0, "jsdr_bpsk_receive_f32: a tuned channel handle (jsdr_bpsk_create_tuned_channels) takes batches only "
+                 "(jsdr_bpsk_batch_f32); the handle is unchanged");
     JSDR_REQUIRE(!h->pst, "jsdr_bpsk_receive_f32: a tuned handle (jsdr_bpsk_create_tuned) takes batches only; receive() is the 1-stream "
                  "form of jsdr_bpsk_create");
     if (h->nch > 0) {
@@ -2488,6 +2527,8 @@ int jsdr_bpsk_set_variant(jsdr_bpsk *h, int variant)
     JSDR_REQUIRE(h, "jsdr_bpsk_set_variant: null handle");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || variant == JSDR_VARIANT_FAST, "jsdr_bpsk_set_variant: unknown variant %d", variant);
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || h->nch == 0, "jsdr_bpsk_set_variant: a channel handle has no fast variant");
+    JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || h->pst_nch == 0, "jsdr_bpsk_set_variant: a tuned channel handle "
+                 "(jsdr_bpsk_create_tuned_channels) has no fast variant; the handle is unchanged");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->pst, "jsdr_bpsk_set_variant: a tuned handle has no fast variant");
     JSDR_REQUIRE(h->n_in == 0, "jsdr_bpsk_set_variant: the variant is fixed once samples have been received");
     JSDR_REQUIRE(variant == JSDR_VARIANT_EXACT || !h->do_fft, "jsdr_bpsk_set_variant: the fast variant covers the tune mode only");
@@ -2510,6 +2551,8 @@ int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who)
     JSDR_REQUIRE(h, "%s: null handle", who);
     JSDR_REQUIRE(h->variant == JSDR_VARIANT_EXACT,
                  "%s: the fast variant has no live control (jsdr_bpsk_recover_uncertified replays from creation)", who);
+    JSDR_REQUIRE(!(h->pst_nch > 0 && do_fft > 0), "%s: a tuned channel handle (jsdr_bpsk_create_tuned_channels) runs in the tune mode only; the "
+                 "handle is unchanged", who);
     JSDR_REQUIRE(!(h->pst && do_fft > 0), "%s: a tuned handle (jsdr_bpsk_create_tuned) runs in the tune mode only; the handle is unchanged", who);
     if (do_fft > 0 && !h->do_fft) {
         JSDR_REQUIRE(fft_front_kind(h->nsf, h->decim, false) != FRONT_NONE, "%s: FFT-acquire mode cannot take this handle's frame size (%d "
@@ -2842,14 +2885,16 @@ int jsdr_bpsk_acq_last_launch(jsdr_bpsk *h, int64_t *fwd_frames, int64_t *inv_fr
 int jsdr_bpsk_channel_info(jsdr_bpsk *h, int *ninputs, int *nchannels)
 {
     JSDR_REQUIRE(h && ninputs && nchannels, "jsdr_bpsk_channel_info: null argument");
-    *ninputs = h->nch > 0 ? h->nin : h->nstreams;
-    *nchannels = h->nch > 0 ? h->nch : 1;
+    *ninputs = h->nch > 0 ? h->nin : h->pst_nch > 0 ? h->pst_nin : h->nstreams;
+    *nchannels = h->nch > 0 ? h->nch : h->pst_nch > 0 ? h->pst_nch : 1;
     return JSDR_OK;
 }
 
 int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz)
 {
     JSDR_REQUIRE(h, "jsdr_bpsk_set_channel_tuning: null handle");
+    JSDR_REQUIRE(h->pst_nch == 0, "jsdr_bpsk_set_channel_tuning: the channels of a tuned channel handle (jsdr_bpsk_create_tuned_channels) are "
+                 "tuned as streams, input * nchannels + channel (jsdr_bpsk_set_stream_tuning); the handle is unchanged");
     JSDR_REQUIRE(!h->pst, "jsdr_bpsk_set_channel_tuning: a tuned handle has streams, not channels (jsdr_bpsk_set_stream_tuning); the handle is unchanged");
     if (h->nch == 0) {  // an ordinary handle is one channel
         JSDR_REQUIRE(channel == 0, "jsdr_bpsk_set_channel_tuning: channel %d out of range (the handle has 1)", channel);
@@ -2863,6 +2908,8 @@ int jsdr_bpsk_set_channel_tuning(jsdr_bpsk *h, int channel, double tuning_hz)
 int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up)
 {
     JSDR_REQUIRE(h, "jsdr_bpsk_set_channel_mode: null handle");
+    JSDR_REQUIRE(h->pst_nch == 0, "jsdr_bpsk_set_channel_mode: the channels of a tuned channel handle (jsdr_bpsk_create_tuned_channels) are "
+                 "streams in the tune mode (jsdr_bpsk_set_mode sets doUp on all of them); the handle is unchanged");
     JSDR_REQUIRE(!h->pst, "jsdr_bpsk_set_channel_mode: a tuned handle has streams, not channels (jsdr_bpsk_set_mode); the handle is unchanged");
     if (h->nch == 0) {
         JSDR_REQUIRE(channel == 0, "jsdr_bpsk_set_channel_mode: channel %d out of range (the handle has 1)", channel);
@@ -2878,6 +2925,8 @@ int jsdr_bpsk_set_channel_mode(jsdr_bpsk *h, int channel, int do_fft, int do_up)
 int jsdr_bpsk_get_channel_control(jsdr_bpsk *h, int channel, double *tuning_hz, int *do_fft, int *do_up)
 {
     JSDR_REQUIRE(h && tuning_hz && do_fft && do_up, "jsdr_bpsk_get_channel_control: null argument");
+    JSDR_REQUIRE(h->pst_nch == 0, "jsdr_bpsk_get_channel_control: the channels of a tuned channel handle (jsdr_bpsk_create_tuned_channels) "
+                 "are streams, input * nchannels + channel (jsdr_bpsk_get_stream_tuning)");
     JSDR_REQUIRE(!h->pst, "jsdr_bpsk_get_channel_control: a tuned handle has streams, not channels (jsdr_bpsk_get_stream_tuning)");
     if (h->nch == 0) {
         JSDR_REQUIRE(channel == 0, "jsdr_bpsk_get_channel_control: channel %d out of range (the handle has 1)", channel);
@@ -2924,6 +2973,31 @@ int jsdr_bpsk_create_tuned(jsdr_bpsk **out, int rate, int nsamples_per_frame, in
         jsdr_bpsk_destroy(h);
         return JSDR_ERR;
     }
+    *out = h;
+    return JSDR_OK;
+}
+
+// A tuned handle whose streams are the channels of shared inputs: jsdr_bpsk_create_tuned's handle of ninputs x nchannels streams
+// (walk, per-stream state, retunes, plans), fed by k_chan_front_pst from one row per INPUT.
+int jsdr_bpsk_create_tuned_channels(jsdr_bpsk **out, int rate, int nsamples_per_frame, int ninputs, int nchannels, const double *tuning_hz,
+                                    int64_t max_batch_samples)
+{
+    JSDR_REQUIRE(out, "jsdr_bpsk_create_tuned_channels: null handle pointer");
+    *out = nullptr;
+    // every check before any device work
+    JSDR_REQUIRE(tuning_hz, "jsdr_bpsk_create_tuned_channels: null tuning array");
+    JSDR_REQUIRE(nchannels >= 1 && nchannels <= CHAN_MAX, "jsdr_bpsk_create_tuned_channels: nchannels %d outside 1 .. %d", nchannels, (int)CHAN_MAX);
+    JSDR_REQUIRE(rate >= 1 && nsamples_per_frame > 0 && ninputs >= 1 && (long long)ninputs * nchannels <= 65535,
+                 "jsdr_bpsk_create_tuned_channels: bad geometry (rate %d, frame of %d samples, %d inputs x %d channels; at most 65535 streams)",
+                 rate, nsamples_per_frame, ninputs, nchannels);
+    const int S = ninputs * nchannels;
+    for (int s = 0; s < S; s++)
+        JSDR_REQUIRE(std::isfinite(tuning_hz[s]) && tuning_hz[s] < (double)rate, "jsdr_bpsk_create_tuned_channels: tuning %g Hz of channel %d of "
+                     "input %d is not a finite value below the rate (%d Hz)", tuning_hz[s], s % nchannels, s / nchannels, rate);
+    jsdr_bpsk *h = nullptr;
+    if (jsdr_bpsk_create_tuned(&h, rate, nsamples_per_frame, S, tuning_hz, max_batch_samples) != JSDR_OK) return JSDR_ERR;
+    h->pst_nin = ninputs;
+    h->pst_nch = nchannels;
     *out = h;
     return JSDR_OK;
 }
@@ -3221,6 +3295,8 @@ static int ckpt_check(jsdr_bpsk *h, const char *who)
     JSDR_REQUIRE(h, "%s: null handle", who);
     JSDR_REQUIRE(h->nch == 0, "%s: a channel handle (jsdr_bpsk_create_channels / _create_mode_channels / _create_live_channels) keeps "
                  "per-channel tuners and seams on the host, which the record does not carry; the handle is unchanged", who);
+    JSDR_REQUIRE(h->pst_nch == 0, "%s: a tuned channel handle (jsdr_bpsk_create_tuned_channels) keeps one input history per input, and a "
+                 "record carries a stream's own; the handle is unchanged", who);
     JSDR_REQUIRE(h->variant == JSDR_VARIANT_EXACT, "%s: a JSDR_VARIANT_FAST handle has no exact state to carry (its certification "
                  "bounds and its shadow are not part of the record); the handle is unchanged", who);
     return JSDR_OK;

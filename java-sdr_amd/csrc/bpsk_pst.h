@@ -10,6 +10,12 @@ namespace jsdr {
 // (1/8 byte a sample, against 4 of the int16 input)
 enum { PST_C = 64 };
 
+constexpr long long PST_NO_ENTRY = 0x7fffffffffffffffLL;  // the position of "no further entry"
+
+// where the phase of the tile's sample e is parked: one double of padding per 64, so that the lanes of phase 1 (64 samples
+// apart) do not all store into one LDS bank
+__device__ __forceinline__ int pst_slot(int e) { return e + (e >> 6); }
+
 struct TunerWalkArgs {
     double *tu;                    // [S] tuPhase: read at the start, the call's end value written back
     const double *inc;             // [S] tuPhaseInc
@@ -62,7 +68,31 @@ struct PstRampArgs {
     double rate;           // the sample rate, as the double tuPhaseInc is divided by
 };
 
+// The front end of a tuned channel handle (jsdr_bpsk_create_tuned_channels, bpsk_chan_pst.hip): nch channels per input, channel c
+// of input i is row i * nch + c of the walk's arrays and of dm; the input and its history are per INPUT, as k_chan_front's.
+struct PstChanFrontArgs {
+    const int *raw;                // int16 pairs as dwords, [ninputs][stride_pairs]; k_chan_front_pst<true>: float2 samples
+    long long stride_pairs;        // between inputs
+    int ic, qc;
+    const int2 *hist;              // [ninputs][32]: the 26 inputs before the call (k_hist_in)
+    const double *inc;             // [ninputs * nch]
+    const double *ckpt;            // [ninputs * nch][ckpt_stride], k_tuner_walk's
+    long long ckpt_stride;
+    const unsigned short *kh_old;  // [ninputs * nch][32]
+    const unsigned char *kvco;     // [nds] shared VCO table index
+    const double *sc9;             // cos[0..256], sin[0..256], (1.0, 1.0) at 256
+    const double *ds_taps;         // [27]
+    double2 *dm;                   // [ninputs * nch][dm_stride]: 64 history + nds VCO-mixed samples
+    long long dm_stride;
+    long long nds;
+    int first_out;                 // input index whose arrival completes output 0
+    int decim;
+    int nch;                       // channels per input
+    int nout;                      // outputs per workgroup (set by the launcher)
+};
+
 // plan: null for a call without one (the kernels of such a call do not know of plans); ramp: null, or with plan for a ramp plan
+int launch_chan_front_pst(const PstChanFrontArgs &a, int ninputs, bool f32in, const PstPlanArgs *plan, const PstRampArgs *ramp, hipStream_t st);
 int launch_tuner_walk(const TunerWalkArgs &a, const PstPlanArgs *plan, const PstRampArgs *ramp, hipStream_t st);
 int launch_front_pst(const PstFrontArgs &a, int nstreams, bool f32in, const PstPlanArgs *plan, const PstRampArgs *ramp, hipStream_t st);
 // dmMaxCorr = 0 (:190) in the n streams ids[] names

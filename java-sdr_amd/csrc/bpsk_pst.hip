@@ -45,8 +45,6 @@ namespace jsdr {
 
 enum { PST_THREADS = 256, PST_WALK_THREADS = 64 };
 
-constexpr long long PST_NO_ENTRY = 0x7fffffffffffffffLL;  // the position of "no further entry"
-
 // The two kernels' bodies are stated once each, in bpsk_pst_walk_body.h and bpsk_pst_front_body.h, and included between the braces
 // of the plain, the planned and the ramp form with PLAN and RAMP set: a body handed its kernel's argument struct as a function argument compiles to
 // other (equivalent) code than one that reads it in place, and the plain forms' code objects are pinned (tools/kernel_asm_diff.py).
@@ -80,10 +78,6 @@ __global__ __launch_bounds__(PST_WALK_THREADS) void k_tuner_walk_ramp(TunerWalkA
     PstRampAt ra;
 #include "bpsk_pst_walk_body.h"
 }
-
-// where the phase of the tile's sample e is parked: one double of padding per 64, so that the lanes of phase 1 (64 samples
-// apart) do not all store into one LDS bank
-__device__ __forceinline__ int pst_slot(int e) { return e + (e >> 6); }
 
 template <bool F32IN>
 __global__ __launch_bounds__(PST_THREADS) void k_front_pst(PstFrontArgs a)

@@ -16,70 +16,7 @@
     const long long jend = (j0 + a.nout < a.nds) ? j0 + a.nout : a.nds;
     const long long n_lo = (long long)a.first_out + (long long)D * j0 - 26;  // input index of x[0] (>= -26)
     const int cnt = (int)((jend - 1 - j0) * D + 27);                         // <= cap
-    // ---- phase 1: the phases of the tile's samples of this call, PST_C of them a lane from the checkpoint before them
-    const long long n_first = n_lo < 0 ? 0 : n_lo;
-    const long long n_last = n_lo + cnt - 1;  // the newest sample of the tile's last output: 0 <= n_last < L
-    const double inc = a.inc[s];
-    const double *ck = a.ckpt + (long long)s * a.ckpt_stride;
-    for (long long c = n_first / PST_C + threadIdx.x; c <= n_last / PST_C; c += blockDim.x) {
-        double tu = ck[c];
-        const long long nb = c * PST_C;
-        double inc_c = inc;  // the increment at the block's first sample
-        if constexpr (PLAN) {  // ... with a plan: of the entry in effect there; then through the entries inside the block
-            const long long e0 = p.off[s], e_end = p.off[s + 1];
-            long long e = e0 + p.ckpt_e[(long long)s * a.ckpt_stride + c];
-            double rt = 0.0, rs = 0.0;  // RAMP: the tuning and the slope of the entry in effect (no slope: inc_c stands), at sample rat
-            long long rat = 0;
-            if constexpr (RAMP) {
-                inc_c = p.inc0[s];
-                if (e > e0) {
-                    rt = r.tuning[e - 1];
-                    rs = r.slope[e - 1];
-                    rat = p.pos[e - 1];
-                    if (rs == 0.0) inc_c = tuner_ramp_inc(rt, rs, 0, r.rate);
-                }
-            } else {
-                inc_c = e > e0 ? p.inc[e - 1] : p.inc0[s];
-            }
-            long long next = e < e_end ? p.pos[e] : PST_NO_ENTRY;
-            bool slow = next < nb + PST_C;
-            if constexpr (RAMP) slow = slow || rs != 0.0;
-            if (slow) {
-                for (int i = 0; i < PST_C; i++) {
-                    const long long n = nb + i;
-                    if (n == next) {
-                        if constexpr (RAMP) {
-                            rt = r.tuning[e];
-                            rs = r.slope[e];
-                            rat = n;
-                            if (rs == 0.0) inc_c = tuner_ramp_inc(rt, rs, 0, r.rate);
-                        } else {
-                            inc_c = p.inc[e];
-                        }
-                        e++;
-                        next = e < e_end ? p.pos[e] : PST_NO_ENTRY;
-                    }
-                    if constexpr (RAMP)
-                        if (rs != 0.0) inc_c = tuner_ramp_inc(rt, rs, n - rat, r.rate);
-                    tuner_advance(tu, inc_c);
-                    if (n >= n_first && n <= n_last) tus[pst_slot((int)(n - n_lo))] = tu;
-                }
-                continue;
-            }
-        }
-        for (int i = 0; i < PST_C; i++) {  // (a block without an entry and under no slope: the plain loop)
-            tuner_advance(tu, inc_c);
-            const long long n = nb + i;
-            if (n >= n_first && n <= n_last) tus[pst_slot((int)(n - n_lo))] = tu;
-        }
-    }
-    __syncthreads();
-    const unsigned short *ko = a.kh_old + (long long)s * 32;
-    for (int e = threadIdx.x; e < cnt; e += blockDim.x) {
-        const long long n = n_lo + e;
-        k9[e] = n < 0 ? ko[26 + n] : (unsigned short)tuner_k9(tus[pst_slot(e)]);
-    }
-    __syncthreads();
+#include "bpsk_pst_phase1.h"
     // ---- the samples, read once, converted and mixed (:372-373, :388-390 / :395)
     const int *raw = a.raw + (long long)s * a.stride_pairs;
     const int2 *hist = a.hist + (long long)s * 32;
