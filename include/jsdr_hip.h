@@ -98,6 +98,29 @@ int jsdr_fft_batch_i16(jsdr_fft *h, const int16_t *raw_dev, int64_t nframes, int
                        float *psd_dev, void *stream);
 /* complex spectrum only (float2[n] per frame), for the 1e-5 FFT parity tests */
 int jsdr_fft_spectrum_f32(jsdr_fft *h, const float *iq_dev, int64_t nframes, float *spec_dev, void *stream);
+/* fft.receive + waterfall.paintLine in one call (fft.java:226 publishes "fft-psd", waterfall.java:28-47, 87-109 is its one
+ * consumer): pixel rows straight from IQ frames, and no PSD array in caller memory.  Defined by composition, bit for bit:
+ *   pix_dev row f  = what jsdr_waterfall_lines(psd, .., n, width, peak_rgb, ..) writes for the row psd that
+ *                    jsdr_fft_batch_i16 / _f32 of this handle writes for frame f;
+ *   max_dev[f][p]  = the pooled maximum itself, unrotated: getMax(psd, (int)(p*step), (int)step) as fft.paintComponent
+ *                    takes it (fft.java:147); with width == n the PSD row without its two trailing floats;
+ *   peak_dev[f]    = {psd[n], psd[n+1]}: Hz of the first strict maximum and its value (fft.java:138-140 prints them).
+ * Powers of two 64 .. 8192 run one fused kernel, "k_fft_pix": the batch kernel's frame loop, whose last pass leaves the dB
+ * row in the frame's LDS image, where the frame's own threads pool it.  Every other frame size runs the handle's batch kernel
+ * into PSD rows owned by the handle (at most 1024 frames at a time, allocated at the first such call, counted by
+ * jsdr_live_resources), then k_waterfall: "<kernel>+k_waterfall".  Asynchronous on `stream`; calls on one handle share
+ * those rows, so they belong on one stream at a time.  jsdr_fft_set_cu_share and jsdr_fft_last_launch apply to the fused
+ * kernel as to the batch kernel.  JSDR_ERR before any device work, the message naming the argument: a null handle, input
+ * or pix_dev; width <= 0; nframes < 0.  nframes == 0 is JSDR_OK and launches nothing. */
+int jsdr_fft_waterfall_i16(jsdr_fft *h, const int16_t *raw_dev, int64_t nframes, int ic, int qc,
+                           int width, uint32_t peak_rgb,
+                           uint32_t *pix_dev   /* [nframes][width], required                       */,
+                           float    *max_dev   /* [nframes][width], may be NULL                    */,
+                           float    *peak_dev  /* [nframes][2] = {Hz, max dB}, may be NULL         */,
+                           void *stream);
+int jsdr_fft_waterfall_f32(jsdr_fft *h, const float *iq_dev, int64_t nframes, int width, uint32_t peak_rgb,
+                           uint32_t *pix_dev, float *max_dev, float *peak_dev, void *stream);
+const char *jsdr_fft_waterfall_kernel(jsdr_fft *h);   /* what the last waterfall call launched */
 
 /* ------------------------------------------------------------------ phase.java
  * phase.java:75-80 max|x| over the 2n floats of a frame; :93-116 per-pixel-column means of I and Q

@@ -45,12 +45,13 @@ def lib():
         _lib.jsdr_last_error.restype = C.c_char_p
         _lib.jsdr_bpsk_profile_name.restype = C.c_char_p
         _lib.jsdr_demod_profile_name.restype = C.c_char_p
-        for fn in ("jsdr_bpsk_front_kernel", "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel"):
+        for fn in ("jsdr_bpsk_front_kernel", "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel",
+                   "jsdr_fft_waterfall_kernel"):
             getattr(_lib, fn).restype = C.c_char_p
             getattr(_lib, fn).argtypes = [C.c_void_p]
         for name in EXPORTED_SYMBOLS:
             if name not in ("jsdr_last_error", "jsdr_bpsk_profile_name", "jsdr_demod_profile_name", "jsdr_bpsk_front_kernel",
-                            "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel"):
+                            "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel", "jsdr_fft_waterfall_kernel"):
                 getattr(_lib, name).restype = C.c_int
     return _lib
 
@@ -228,6 +229,23 @@ class Fft:
     def batch_f32(self, iq_dev, nframes, psd_dev, stream=None):
         _check(lib().jsdr_fft_batch_f32(self.h, _addr(iq_dev), C.c_int64(nframes), _addr(psd_dev),
                                         C.c_void_p(stream)), "jsdr_fft_batch_f32")
+
+    def waterfall_i16(self, raw_dev, nframes, width, pix_dev, ic=0, qc=0, peak_rgb=0x00FFFF, max_dev=None, peak_dev=None,
+                      stream=None):
+        """fft.receive + waterfall.paintLine of nframes int16 frames: pix_dev uint32 [nframes][width]; optionally max_dev float
+        [nframes][width] (the pooled maxima, unrotated) and peak_dev float [nframes][2] = (Hz, max dB).  No PSD array is written."""
+        _check(lib().jsdr_fft_waterfall_i16(self.h, _addr(raw_dev), C.c_int64(nframes), int(ic), int(qc), int(width),
+                                            C.c_uint32(peak_rgb), _addr(pix_dev), _addr(max_dev), _addr(peak_dev),
+                                            C.c_void_p(stream)), "jsdr_fft_waterfall_i16")
+
+    def waterfall_f32(self, iq_dev, nframes, width, pix_dev, peak_rgb=0x00FFFF, max_dev=None, peak_dev=None, stream=None):
+        _check(lib().jsdr_fft_waterfall_f32(self.h, _addr(iq_dev), C.c_int64(nframes), int(width), C.c_uint32(peak_rgb),
+                                            _addr(pix_dev), _addr(max_dev), _addr(peak_dev), C.c_void_p(stream)),
+               "jsdr_fft_waterfall_f32")
+
+    def waterfall_kernel(self):
+        """what the last waterfall_* call launched: "k_fft_pix", or "<batch kernel>+k_waterfall" """
+        return lib().jsdr_fft_waterfall_kernel(self.h).decode()
 
     def spectrum(self, bufs):
         """complex spectra of a [nframes, 2n] float32 array (for the 1e-5 parity tests)"""

@@ -127,7 +127,7 @@ constexpr int lds_frame_elems(int n) { return n + (n >> 4) + 1; }
 
 
 enum { IN_I16 = 0, IN_F32 = 1 };
-enum { OUT_PSD = 0, OUT_SPEC = 1 };
+enum { OUT_PSD = 0, OUT_SPEC = 1, OUT_PIX = 2 };  // OUT_PIX: waterfall pixel rows, the power-of-two kernel only (fft_psd.hip)
 
 struct FftArgs {
     const void *in;      // int16 pairs or float pairs, [nframes][n]

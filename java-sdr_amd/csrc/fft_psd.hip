@@ -11,7 +11,11 @@
 // PSD stores likewise.  HBM traffic = 4 B in + 4 B out per sample: the kernel is HBM bound.
 // Float arithmetic may contract to FMA here: parity for this path is the 1e-5 (peak-normalised)
 // tolerance of BASELINE.json, JTransforms' own rounding being unknowable (source absent).
+//
+// k_fft_pix (jsdr_fft_waterfall_*) is the same frame loop with waterfall.paintLine (waterfall.java:87-109) fused behind it: the
+// last pass leaves the frame's dB row in its LDS image, the frame's threads pool it into pixels, and no PSD row is stored.
 #include "fft_common.h"
+#include "waterfall_dev.h"
 #include <math.h>
 #include <stdlib.h>
 #include <vector>
@@ -113,6 +117,32 @@ __device__ __forceinline__ void fft_fetch(const FftArgs &a, long long frame, int
 // (tests/test_gpu_fft_i16_scaled.py).  SC_IN: this (first) pass produces scaled values; SC_OUT: this (second) pass removes
 // the scale.  A plan whose second pass is not "direct" keeps the two-instruction conversion.
 enum { SC_NONE = 0, SC_IN = 1, SC_OUT = 2 };
+
+// OUT_PIX (k_fft_pix): the frame's dB row never leaves the CU -- the last pass writes it over the frame's LDS image and the
+// epilogue of fft_frame pools it into waterfall pixels (waterfall_dev.h)
+struct FftPixArgs : FftArgs {
+    unsigned *pix;      // [nframes][width]
+    float *maxo;        // [nframes][width] pooled maxima, unrotated; may be null
+    float *peak;        // [nframes][2] = {Hz, max dB}; may be null
+    int width;
+    unsigned peak_rgb;
+};
+
+// fft.java:205-207: 10*log10((re^2+im^2) * (2/N)^2) = 10*log10(2) * (log2(re^2+im^2) + 2 - 2*log2(N)):
+// N is a power of two, so the scale is an exact integer offset of the base-2 logarithm.  Stated once: the PSD form stores
+// this value and the pixel form pools it, and the two must round (and contract) alike to the bit.
+template <int N>
+__device__ __forceinline__ float psd_db(float2 x)
+{
+    constexpr float L2 = 3.0102999566398120f;
+    constexpr float OFF = 3.0102999566398120f * (2.0f - 2.0f * (float)ilog2_c(N));
+    return L2 * __log2f(x.x * x.x + x.y * x.y) + OFF;
+}
+
+// the dB row of OUT_PIX in the frame's LDS image, as float[N]: one pad float per 32, so that the pooling reads of
+// neighbouring pixels -- a power-of-two stride of bins between lanes at the usual widths -- fall on 32 different banks
+// (ds_read_b32 is served in two groups of 32 lanes over 32 banks), and the writes, 32 consecutive bins a group, stay so
+__device__ __forceinline__ int row_pad(int idx) { return idx + (idx >> 5); }
 constexpr bool fft_i16_scaled(int R0, int R1) { return tw_direct(R0, R1); }
 
 template <int N, int T, int IN, int OUT, int R, int P, bool FIRST, bool LAST, class RAW = int, int SC = SC_NONE>
@@ -124,7 +154,10 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool
     constexpr int ITERS = NB / T;
     // the last pass writes to global memory, not to the LDS image: its butterflies need not all be in flight
     // before the first store, so they are processed one at a time (half the live registers at ITERS = 2)
-    constexpr int GROUP = LAST ? 1 : ITERS;
+    // (OUT_PIX: the last pass writes its dB values over the image it reads -- a float row, fft_frame -- so it is shaped like
+    //  the passes before it: everything loaded and transformed, a barrier, then the outputs)
+    constexpr bool TO_LDS = !LAST || OUT == OUT_PIX;
+    constexpr int GROUP = TO_LDS ? ITERS : 1;
 #pragma unroll
     for (int g0 = 0; g0 < ITERS; g0 += GROUP) {
         float2 v[GROUP][R];
@@ -164,7 +197,7 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool
             apply_twiddles<R, P>(v[gi], b & (P - 1), tab);
             dft_reg<R>(v[gi]);
         }
-        if constexpr (!FIRST && !LAST) __syncthreads();
+        if constexpr (!FIRST && TO_LDS) __syncthreads();
 #pragma unroll
         for (int gi = 0; gi < GROUP; gi++) {
             const int b = (g0 + gi) * T + tid;
@@ -178,20 +211,19 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool
 #pragma unroll
                     for (int r = 0; r < R; r++) dst[j0 + r * P] = v[gi][cx_bitrev(r, R)];
                 } else {
-                    // fft.java:205-207: 10*log10((re^2+im^2) * (2/N)^2) = 10*log10(2) * (log2(re^2+im^2) + 2 - 2*log2(N)):
-                    // N is a power of two, so the scale is an exact integer offset of the base-2 logarithm
-                    constexpr float L2 = 3.0102999566398120f;
-                    constexpr float OFF = 3.0102999566398120f * (2.0f - 2.0f * (float)ilog2_c(N));
                     float *dst = a.out + frame * (N + 2);
                     float db[R];
 #pragma unroll
                     for (int r = 0; r < R; r++) {
-                        float2 x = v[gi][cx_bitrev(r, R)];
-                        db[r] = L2 * __log2f(x.x * x.x + x.y * x.y) + OFF;
+                        db[r] = psd_db<N>(v[gi][cx_bitrev(r, R)]);
+                        if constexpr (OUT == OUT_PIX) {
+                            reinterpret_cast<float *>(buf)[row_pad(j0 + r * P)] = db[r];
+                        } else {
 #ifndef JSDR_X_FFT_NOSTORE  // timing experiment: no PSD stores (the argmax keeps the arithmetic alive)
-                        dst[j0 + r * P] = db[r];  // (nontemporal stores: 1.99 -> 2.39 ms, measured r02; 8-byte stores through a DPP
-                                                  //  exchange between neighbouring lanes: 15.5 -> 16.1 ms at 8192 streams, r03)
+                            dst[j0 + r * P] = db[r];  // (nontemporal stores: 1.99 -> 2.39 ms, measured r02; 8-byte stores through a DPP
+                                                      //  exchange between neighbouring lanes: 15.5 -> 16.1 ms at 8192 streams, r03)
 #endif
+                        }
                     }
                     // first strict maximum of this thread's bins (fft.java:208-211): the group's maximum
                     // (fmaxf ignores NaN, like the reference's '>'), then the lowest bin that holds it
@@ -214,8 +246,8 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool
 
 // One frame, executed by T threads (tid in [0,T)).  `raw` holds the frame's first-pass inputs (fft_fetch); before the
 // last pass the NEXT frame's inputs are fetched into it.
-template <int N, int T, int IN, int OUT, int R0, int R1, int R2, int R3>
-__device__ __forceinline__ void fft_frame(const FftArgs &a, long long frame, long long next, int tid, float2 *buf,
+template <int N, int T, int IN, int OUT, int R0, int R1, int R2, int R3, class ARGS>
+__device__ __forceinline__ void fft_frame(const ARGS &a, long long frame, long long next, int tid, float2 *buf,
                                           const float2 *tw_lds, float *red_val, int *red_idx, int frame_in_block,
                                           typename RawPoint<IN>::type (&raw)[R0])
 {
@@ -244,7 +276,12 @@ __device__ __forceinline__ void fft_frame(const FftArgs &a, long long frame, lon
         fft_pass<N, T, IN, OUT, R3, R0 * R1 * R2, false, NPASS == 4>(a, frame, active, tid, buf, tw_lds + O3, best);
     }
 
-    if constexpr (OUT == OUT_PSD) {
+    // OUT_PIX: the last pass left the frame's dB row over the image, float[N] behind row_pad.  (The next frame's fetch is in
+    // flight in `raw` and is not touched before the next first pass.)
+    [[maybe_unused]] const float *row = reinterpret_cast<const float *>(buf);
+    static_assert(N + (N >> 5) + 1 <= 2 * lds_frame_elems(N), "the padded row fits the image");
+
+    if constexpr (OUT == OUT_PSD || OUT == OUT_PIX) {
         // first strict maximum (fft.java:208-211): highest value, lowest bin on ties; none if all -inf
         float bestv = best.v;
         int bestk = best.k;
@@ -259,15 +296,23 @@ __device__ __forceinline__ void fft_frame(const FftArgs &a, long long frame, lon
         }
         if constexpr (T > 64) {
             constexpr int NW = T / 64;
+            int fb = frame_in_block, wv = tid >> 6;
+            if constexpr (OUT == OUT_PIX) {
+                // both are the same in every lane of a wave: as scalars the two LDS addresses below are made where they are used.
+                // As vector registers they are kept across the frame loop, the 2048-point kernel spills them at its 128 registers,
+                // and the reload -- a memory load -- waits for the next frame's fetch on its way.
+                fb = __builtin_amdgcn_readfirstlane(fb);
+                wv = __builtin_amdgcn_readfirstlane(wv);
+            }
             if ((tid & 63) == 0) {
-                red_val[frame_in_block * NW + (tid >> 6)] = bestv;
-                red_idx[frame_in_block * NW + (tid >> 6)] = bestk;
+                red_val[fb * NW + wv] = bestv;
+                red_idx[fb * NW + wv] = bestk;
             }
             __syncthreads();
             if (tid == 0) {
                 for (int w = 1; w < NW; w++) {
-                    float ov = red_val[frame_in_block * NW + w];
-                    int ok = red_idx[frame_in_block * NW + w];
+                    float ov = red_val[fb * NW + w];
+                    int ok = red_idx[fb * NW + w];
                     if (ov > bestv || (ov == bestv && ok < bestk)) {
                         bestv = ov;
                         bestk = ok;
@@ -282,9 +327,35 @@ __device__ __forceinline__ void fft_frame(const FftArgs &a, long long frame, lon
             const int datlen = 2 * N;
             if (p >= datlen / 2) p -= datlen;
             int hz = (int)((unsigned)p * (unsigned)a.rate) / datlen;
-            float *dst = a.out + frame * (N + 2);
-            dst[N] = (float)hz;
-            dst[N + 1] = m;
+            if constexpr (OUT == OUT_PIX) {
+                if (a.peak) {
+                    a.peak[frame * 2] = (float)hz;
+                    a.peak[frame * 2 + 1] = m;
+                }
+            } else {
+                float *dst = a.out + frame * (N + 2);
+                dst[N] = (float)hz;
+                dst[N + 1] = m;
+            }
+        }
+    }
+
+    if constexpr (OUT == OUT_PIX) {
+        // waterfall.paintLine over the row: the frame's T threads take pixels tid, tid + T, ... -- a wave writes a contiguous
+        // run of the rotated row (two where the rotation wraps inside it).  The row is complete behind the barrier of the
+        // reduction above where the frame spans waves, behind this one where it does not.
+        if constexpr (T <= 64) __syncthreads();
+        const int width = a.width, half = width / 2;
+        const float step = wf_step(N, width);
+        const int l = java_f2i(step);
+        const WfColour colour = wf_colour(a.peak_rgb);
+        unsigned *prow = a.pix + frame * width;
+        float *mrow = a.maxo ? a.maxo + frame * width : nullptr;
+        for (int p = tid; p < width; p += T) {
+            const float r = wf_getmax([&](int i) { return row[row_pad(i)]; }, java_f2i((float)p * step), l);
+            if (mrow) mrow[p] = r;
+            const int q = p + half;  // (p + width / 2) % width
+            prow[q >= width ? q - width : q] = wf_pixel(r, colour);
         }
     }
 }
@@ -300,54 +371,17 @@ __device__ unsigned long long g_fft_wgclk[WGCLK_SLOTS][WGCLK_WGS][3];
 template <int N, int T, int FPB, int IN, int OUT, int R0, int R1, int R2, int R3, bool TWG = false>
 __global__ __launch_bounds__(T *FPB, (N == 2048 ? 4 : 1)) void k_fft(FftArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int FE = lds_frame_elems(N);
-    constexpr int TWN = TWG ? 0 : tw_total(R0, R1, R2, R3);
-    float2 *tw_own = reinterpret_cast<float2 *>(smem);                    // [TWN]
-    float2 *bufs = tw_own + TWN;                                          // [FPB][FE]
-    float *red_val = reinterpret_cast<float *>(bufs + (size_t)FPB * FE);  // [FPB*NW]
-    int *red_idx = reinterpret_cast<int *>(red_val + FPB * ((T + 63) / 64));
-    const float2 *tw_lds = TWG ? a.tw : tw_own;
-#ifdef JSDR_X_WGCLK
-    const unsigned long long wgclk0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long wgclk_n = 0;
-#endif
+#include "fft_block_body.h"
+}
 
-    const int tid_b = threadIdx.x;
-    if constexpr (!TWG) {
-        for (int i = tid_b; i < TWN; i += T * FPB) tw_own[i] = a.tw[i];
-        __syncthreads();
-    }
-
-    const int fib = tid_b / T;
-    const int tid = tid_b - fib * T;
-    float2 *buf = bufs + (size_t)fib * FE;
-    const long long ngroups = (a.nframes + FPB - 1) / FPB;
-    // a surplus part-workgroup (frame count not a multiple of FPB) redoes the last frame: identical values to
-    // identical addresses, and no predicate on any load, store or barrier
-    auto frame_of = [&](long long g) {
-        long long f = g * FPB + fib;
-        return f < a.nframes ? f : a.nframes - 1;
-    };
-    typename RawPoint<IN>::type raw[R0];
-    if ((long long)blockIdx.x < ngroups) fft_fetch<N, T, IN, R0>(a, frame_of(blockIdx.x), tid, raw);
-    for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
-        const long long gn = g + gridDim.x;
-        fft_frame<N, T, IN, OUT, R0, R1, R2, R3>(a, frame_of(g), frame_of(gn < ngroups ? gn : g), tid, buf, tw_lds, red_val,
-                                                 red_idx, fib, raw);
-        __syncthreads();
-#ifdef JSDR_X_WGCLK
-        wgclk_n++;
-#endif
-    }
-#ifdef JSDR_X_WGCLK
-    if (tid_b == 0 && blockIdx.x < WGCLK_WGS) {
-        unsigned long long *c = g_fft_wgclk[a.wgclk_slot][blockIdx.x];
-        c[0] = wgclk0;
-        c[1] = __builtin_amdgcn_s_memrealtime();
-        c[2] = wgclk_n;
-    }
-#endif
+// the fused fft.receive + waterfall.paintLine form: k_fft's frame loop with OUT_PIX.  (8192: three waves a SIMD as k_fft has
+// them -- left alone the int16 form takes 170 registers, two more than that allows, and a CU holds one workgroup, not two)
+template <int N, int T, int FPB, int IN, int R0, int R1, int R2, int R3>
+__global__ __launch_bounds__(T *FPB, (N == 2048 ? 4 : N == 8192 ? 3 : 1)) void k_fft_pix(FftPixArgs a)
+{
+    constexpr int OUT = OUT_PIX;
+    constexpr bool TWG = false;
+#include "fft_block_body.h"
 }
 
 template <int N, int FPB, int T, int R0, int R1, int R2, int R3, bool TWG = false>
@@ -359,6 +393,7 @@ constexpr size_t fft_lds_bytes()
 
 struct Launcher {
     void (*launch)(const FftArgs &, int grid, hipStream_t) = nullptr;
+    void (*launch_pix)(const FftPixArgs &, int grid, hipStream_t) = nullptr;  // out == OUT_PIX
     int frames_per_block = 0;
     size_t lds_bytes = 0;
     int block = 0;
@@ -370,6 +405,13 @@ static void launch_impl(const FftArgs &a, int grid, hipStream_t s)
 {
     constexpr size_t lds = fft_lds_bytes<N, FPB, T, R0, R1, R2, R3, TWG>();
     hipLaunchKernelGGL((k_fft<N, T, FPB, IN, OUT, R0, R1, R2, R3, TWG>), dim3(grid), dim3(T * FPB), lds, s, a);
+}
+
+template <int N, int T, int FPB, int IN, int R0, int R1, int R2, int R3>
+static void launch_pix_impl(const FftPixArgs &a, int grid, hipStream_t s)
+{
+    constexpr size_t lds = fft_lds_bytes<N, FPB, T, R0, R1, R2, R3, false>();
+    hipLaunchKernelGGL((k_fft_pix<N, T, FPB, IN, R0, R1, R2, R3>), dim3(grid), dim3(T * FPB), lds, s, a);
 }
 
 template <int N, int T, int FPB, int R0, int R1, int R2, int R3, bool TWG = false>
@@ -386,6 +428,10 @@ static Launcher make_launcher(int in, int out)
     if (in == IN_I16 && out == OUT_PSD) l.launch = launch_impl<N, T, FPB, IN_I16, OUT_PSD, R0, R1, R2, R3, TWG>;
     if (in == IN_F32 && out == OUT_PSD) l.launch = launch_impl<N, T, FPB, IN_F32, OUT_PSD, R0, R1, R2, R3, TWG>;
     if (in == IN_F32 && out == OUT_SPEC) l.launch = launch_impl<N, T, FPB, IN_F32, OUT_SPEC, R0, R1, R2, R3, TWG>;
+    if constexpr (!TWG) {
+        if (in == IN_I16 && out == OUT_PIX) l.launch_pix = launch_pix_impl<N, T, FPB, IN_I16, R0, R1, R2, R3>;
+        if (in == IN_F32 && out == OUT_PIX) l.launch_pix = launch_pix_impl<N, T, FPB, IN_F32, R0, R1, R2, R3>;
+    }
     return l;
 }
 
@@ -404,6 +450,23 @@ static Launcher pick_launcher(int n, int in, int out)
         case 4096: return make_launcher<4096, 256, 1, 16, 16, 16, 1>(in, out);
         case 8192: return make_launcher<8192, 512, 1, 16, 16, 8, 4>(in, out);
         default: return Launcher();
+    }
+}
+
+// jsdr_fft_waterfall_* on a frame size the fused kernel does not serve: what k_waterfall does not write -- the pooled maxima,
+// unrotated (fft.paintComponent's getMax, fft.java:147), and the row's two trailing floats -- from the PSD rows of a chunk.
+// One workgroup a frame, grid-stride; the rows were written a kernel ago and are read from cache.
+__global__ __launch_bounds__(256) void k_waterfall_aux(const float *__restrict__ psd, long long nframes, int n, int width,
+                                                       float *__restrict__ maxo, float *__restrict__ peak)
+{
+    const float step = wf_step(n, width);
+    const int l = java_f2i(step);
+    for (long long frame = blockIdx.x; frame < nframes; frame += gridDim.x) {
+        const float *a = psd + frame * (n + 2);
+        if (maxo)
+            for (int p = threadIdx.x; p < width; p += 256)
+                maxo[frame * width + p] = wf_getmax([&](int i) { return a[i]; }, java_f2i((float)p * step), l);
+        if (peak && threadIdx.x < 2) peak[frame * 2 + threadIdx.x] = a[n + threadIdx.x];
     }
 }
 
@@ -427,7 +490,11 @@ struct jsdr_fft {
     bool direct = false;  // any other frame size: fft_any.hip
     long long last_items = 0, last_grid = 0;  // jsdr_fft_last_launch
     int share_wgs_per_cu = 0;  // jsdr_fft_set_cu_share: workgroups per CU the batch kernel is held to (0: all it can use)
+    // jsdr_fft_waterfall_*: frames the fused kernel does not serve go through PSD rows of the handle's own, WF_CHUNK at the most
+    DevBuf<float> wf_rows;
+    std::string wf_kernel;  // jsdr_fft_waterfall_kernel
 };
+constexpr long long WF_CHUNK = 1024;
 
 #ifdef JSDR_X_WGCLK
 static long long g_wgclk_log[WGCLK_SLOTS][3];  // per launch row: frame groups, grid, launch number
@@ -446,6 +513,9 @@ static void fft_wgclk_report()
     if (f) fclose(f);
 }
 #endif
+
+template <class ARGS>
+static int fft_launch_pow2(jsdr_fft *h, ARGS &a, int in_kind, int out_kind, hipStream_t s);
 
 static int fft_run(jsdr_fft *h, const void *in_dev, int in_kind, int out_kind, long long nframes, int ic, int qc,
                    float *out_dev, hipStream_t s)
@@ -489,8 +559,6 @@ static int fft_run(jsdr_fft *h, const void *in_dev, int in_kind, int out_kind, l
         long long cap = (long long)h->num_cu * mgrid;
         return mixed_launch(h->mplan, a, in_kind, out_kind, (int)(nframes < cap ? nframes : cap), s);
     }
-    Launcher l = pick_launcher(h->n, in_kind, out_kind);
-    JSDR_REQUIRE(l.launch, "fft: no kernel for n=%d in=%d out=%d", h->n, in_kind, out_kind);
     a.in = in_dev;
     a.out = out_dev;
     a.tw = in_kind == IN_I16 ? h->tw_i16.p : h->tw.p;
@@ -498,6 +566,17 @@ static int fft_run(jsdr_fft *h, const void *in_dev, int in_kind, int out_kind, l
     a.rate = h->rate;
     a.ic = ic;
     a.qc = qc;
+    return fft_launch_pow2(h, a, in_kind, out_kind, s);
+}
+
+// the power-of-two kernel, PSD / spectrum (FftArgs) or pixel form (FftPixArgs): one launch geometry for both
+template <class ARGS>
+static int fft_launch_pow2(jsdr_fft *h, ARGS &a, int in_kind, int out_kind, hipStream_t s)
+{
+    const long long nframes = a.nframes;
+    Launcher l = pick_launcher(h->n, in_kind, out_kind);
+    constexpr bool PIX = std::is_same<ARGS, FftPixArgs>::value;
+    JSDR_REQUIRE(PIX ? l.launch_pix != nullptr : l.launch != nullptr, "fft: no kernel for n=%d in=%d out=%d", h->n, in_kind, out_kind);
     long long groups = (nframes + l.frames_per_block - 1) / l.frames_per_block;
     // enough workgroups to fill every CU at the LDS-limited occupancy, grid-stride over the rest
     long long per_cu = (long long)(160 * 1024 / l.lds_bytes);
@@ -529,7 +608,8 @@ static int fft_run(jsdr_fft *h, const void *in_dev, int in_kind, int out_kind, l
         g_wgclk_log[a.wgclk_slot][2] = wgclk_seq++;
     }
 #endif
-    l.launch(a, grid, s);
+    if constexpr (PIX) l.launch_pix(a, grid, s);
+    else l.launch(a, grid, s);
     JSDR_LAUNCH_CHECK();
     return JSDR_OK;
 }
@@ -692,6 +772,59 @@ int jsdr_fft_spectrum_f32(jsdr_fft *h, const float *iq_dev, int64_t nframes, flo
     return fft_run(h, iq_dev, IN_F32, OUT_SPEC, nframes, 0, 0, spec_dev, as_stream(stream));
 }
 
+// fft.receive + waterfall.paintLine of a batch: the fused kernel where the frame is a power of two, otherwise the handle's
+// batch kernel into PSD rows of the handle's own (WF_CHUNK at a time), k_waterfall over them and k_waterfall_aux for the rest
+static const char *fft_waterfall_name(jsdr_fft *h)
+{
+    const bool pow2 = !h->rt && !h->direct && !h->mixed;
+    h->wf_kernel = pow2 ? std::string("k_fft_pix") : std::string(jsdr_fft_kernel(h)) + "+k_waterfall";
+    return h->wf_kernel.c_str();
+}
+
+static int fft_waterfall(const char *who, jsdr_fft *h, const void *in_dev, int in_kind, long long nframes, int ic, int qc,
+                         int width, uint32_t peak_rgb, uint32_t *pix_dev, float *max_dev, float *peak_dev, hipStream_t s)
+{
+    JSDR_REQUIRE(h, "%s: null handle", who);
+    JSDR_REQUIRE(in_dev, "%s: null %s", who, in_kind == IN_I16 ? "raw_dev" : "iq_dev");
+    JSDR_REQUIRE(pix_dev, "%s: null pix_dev", who);
+    JSDR_REQUIRE(width > 0, "%s: width=%d must be positive", who, width);
+    JSDR_REQUIRE(nframes >= 0, "%s: nframes=%lld is negative", who, nframes);
+    if (nframes == 0) return JSDR_OK;
+    if (!h->rt && !h->direct && !h->mixed) {
+        FftPixArgs a;
+        a.in = in_dev;
+        a.out = nullptr;
+        a.tw = in_kind == IN_I16 ? h->tw_i16.p : h->tw.p;
+        a.nframes = nframes;
+        a.rate = h->rate;
+        a.ic = ic;
+        a.qc = qc;
+        a.pix = reinterpret_cast<unsigned *>(pix_dev);
+        a.maxo = max_dev;
+        a.peak = peak_dev;
+        a.width = width;
+        a.peak_rgb = (unsigned)peak_rgb;
+        return fft_launch_pow2(h, a, in_kind, OUT_PIX, s);
+    }
+    const long long n = h->n, rows = nframes < WF_CHUNK ? nframes : WF_CHUNK;
+    // (a larger chunk than any before: the release inside alloc waits for the device, so no earlier call still uses the rows)
+    if (h->wf_rows.n < (size_t)(rows * (n + 2)) && h->wf_rows.alloc((size_t)(rows * (n + 2))) != JSDR_OK) return JSDR_ERR;
+    const size_t in_frame = (size_t)n * (in_kind == IN_I16 ? 2 * sizeof(int16_t) : 2 * sizeof(float));
+    for (long long f0 = 0; f0 < nframes; f0 += WF_CHUNK) {
+        const long long nf = nframes - f0 < WF_CHUNK ? nframes - f0 : WF_CHUNK;
+        if (fft_run(h, static_cast<const unsigned char *>(in_dev) + (size_t)f0 * in_frame, in_kind, OUT_PSD, nf, ic, qc,
+                    h->wf_rows.p, s) != JSDR_OK)
+            return JSDR_ERR;
+        if (jsdr_waterfall_lines(h->wf_rows.p, nf, (int)n, width, peak_rgb, pix_dev + f0 * width, s) != JSDR_OK) return JSDR_ERR;
+        if (max_dev || peak_dev) {
+            hipLaunchKernelGGL(k_waterfall_aux, dim3((unsigned)nf), dim3(256), 0, s, h->wf_rows.p, nf, (int)n, width,
+                               max_dev ? max_dev + f0 * width : nullptr, peak_dev ? peak_dev + f0 * 2 : nullptr);
+            JSDR_LAUNCH_CHECK();
+        }
+    }
+    return JSDR_OK;
+}
+
 // one frame from / to host buffers: through the handle's pinned stage when it has one (PinnedStage, common.h)
 static int fft_receive(jsdr_fft *h, const void *in_host, size_t in_bytes, int in_kind, int ic, int qc, float *psd_host)
 {
@@ -732,5 +865,21 @@ int jsdr_fft_receive_i16(jsdr_fft *h, const int16_t *raw_host, int ic, int qc, f
     }
     return fft_receive(h, raw_host, sizeof(int16_t) * 2 * (size_t)h->n, IN_I16, ic, qc, psd_host);
 }
+
+int jsdr_fft_waterfall_i16(jsdr_fft *h, const int16_t *raw_dev, int64_t nframes, int ic, int qc, int width, uint32_t peak_rgb,
+                           uint32_t *pix_dev, float *max_dev, float *peak_dev, void *stream)
+{
+    return fft_waterfall("jsdr_fft_waterfall_i16", h, raw_dev, IN_I16, nframes, ic, qc, width, peak_rgb, pix_dev, max_dev,
+                         peak_dev, as_stream(stream));
+}
+
+int jsdr_fft_waterfall_f32(jsdr_fft *h, const float *iq_dev, int64_t nframes, int width, uint32_t peak_rgb, uint32_t *pix_dev,
+                           float *max_dev, float *peak_dev, void *stream)
+{
+    return fft_waterfall("jsdr_fft_waterfall_f32", h, iq_dev, IN_F32, nframes, 0, 0, width, peak_rgb, pix_dev, max_dev, peak_dev,
+                         as_stream(stream));
+}
+
+const char *jsdr_fft_waterfall_kernel(jsdr_fft *h) { return h ? fft_waterfall_name(h) : ""; }
 
 }  // extern "C"

@@ -5,6 +5,7 @@
 //        batch kernels take;
 //   out: the waterfall pixel row of every PSD frame (waterfall.paintLine/getMax, waterfall.java:87-109).
 #include "common.h"
+#include "waterfall_dev.h"
 #include <errno.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -14,15 +15,6 @@
 
 namespace jsdr {
 
-// Java (int) of a float: truncate toward zero, saturate, NaN -> 0
-__device__ __forceinline__ int java_f2i(float v)
-{
-    if (v != v) return 0;
-    if (v >= 2147483648.0f) return 2147483647;
-    if (v <= -2147483648.0f) return (-2147483647 - 1);
-    return (int)v;
-}
-
 // One 256-thread workgroup per PSD frame (grid-stride over the frames): the frame is read once with 16-byte loads
 // into LDS, every thread then takes the maximum of its pixels' bins from LDS and writes its pixels, a contiguous
 // run of the row (rotated by width/2) per wave.  HBM bound: 4 B read per bin + 4 B written per pixel.
@@ -31,10 +23,9 @@ __global__ __launch_bounds__(256) void k_waterfall(const float *__restrict__ psd
 {
     extern __shared__ __align__(16) float fr[];  // [n]
     const int tid = threadIdx.x;
-    const float step = (float)n / (float)width;
-    const float h = -2.55f;
+    const float step = wf_step(n, width);
     const int l = java_f2i(step);
-    const int pr = (int)((peak_rgb >> 16) & 0xff), pg = (int)((peak_rgb >> 8) & 0xff), pb = (int)(peak_rgb & 0xff);
+    const WfColour colour = wf_colour(peak_rgb);
     for (long long frame = blockIdx.x; frame < nframes; frame += gridDim.x) {
         const float *a = psd + frame * (n + 2);  // rows are n+2 floats: 8-byte aligned only
         const float2 *a2 = reinterpret_cast<const float2 *>(a);
@@ -43,18 +34,8 @@ __global__ __launch_bounds__(256) void k_waterfall(const float *__restrict__ psd
         __syncthreads();
         unsigned *row = pix + frame * width;
         for (int p = tid; p < width; p += 256) {
-            const int o = java_f2i((float)p * step);
-            // waterfall.java:102-109 getMax: '>' never replaces with or by a NaN
-            float r = fr[o];
-            for (int i = o + 1; i < o + l; i++) {
-                const float v = fr[i];
-                if (v > r) r = v;
-            }
-            int f = 255 - java_f2i(r * h);
-            f = f < 0 ? 0 : f;
-            f = f > 255 ? 255 : f;
-            const unsigned cr = (unsigned)(pr * f / 256), cg = (unsigned)(pg * f / 256), cb = (unsigned)(pb * f / 256);
-            row[(p + width / 2) % width] = 0xff000000u | (cr << 16) | (cg << 8) | cb;
+            const float r = wf_getmax([&](int i) { return fr[i]; }, java_f2i((float)p * step), l);
+            row[(p + width / 2) % width] = wf_pixel(r, colour);
         }
         __syncthreads();
     }
