@@ -6,6 +6,7 @@ import pytest
 
 import java_sdr_amd as J
 import oracle_lib as O
+import peak_ties as PT
 
 pytestmark = pytest.mark.gpu
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "oracle_vectors.npz"))
@@ -20,9 +21,12 @@ def lin(db):
     return 10.0 ** (np.asarray(db, np.float64) / 20.0)
 
 
-def check_psd(got, ref, n):
+def check_psd(got, ref, n, rate=None):
     """psd[n+2] vs oracle: amplitudes within FFT_RTOL of the frame peak; dB within 1e-3 where the bin is
-    within 60 dB of the peak; argmax bin identical or an exact-tie mirror (hard part 6)."""
+    within 60 dB of the peak; argmax bin identical or an exact-tie mirror (hard part 6).  Given the rate, also the
+    exact pair: psd[n], psd[n+1] are, bit for bit, what the reference's loop gives for the row's OWN bins (tests/peak_ties.py)."""
+    if rate is not None:
+        PT.assert_row_peak(got, n, rate, ("check_psd", n, rate))
     a, b = lin(got[:n]), lin(ref[:n])
     assert np.abs(a - b).max() <= FFT_RTOL * b.max()
     strong = ref[:n] > ref[:n].max() - 60.0
@@ -76,7 +80,7 @@ def test_fft_sine4410_fixture(golden_dir):
     for k in range(2):
         fr = raw[k * 4096:(k + 1) * 4096]
         psd = f.receive_raw(fr)
-        check_psd(psd, G["sine_psd96k"][k], 2048)
+        check_psd(psd, G["sine_psd96k"][k], 2048, 96000)
         assert int(np.argmax(psd[:2048])) in (205, 1843)
         assert abs(psd[2048]) == 9609.0
         assert abs(f44.receive_raw(fr)[2048]) == 4414.0
@@ -146,14 +150,14 @@ def test_fft_batch_matches_oracle_ragged_counts(n, nframes):
     psd = f.batch_host_i16(raw)
     buf = O.convert_i16(raw)
     for k in range(nframes):
-        check_psd(psd[k], O.fft_receive(buf[k * 2 * n:(k + 1) * 2 * n], 96000), n)
+        check_psd(psd[k], O.fft_receive(buf[k * 2 * n:(k + 1) * 2 * n], 96000), n, 96000)
 
 
 def test_fft_golden_tones():
     f = J.Fft(2048, 96000)
     psd = f.batch_host_i16(G["tones_iq"])
     for k in range(4):
-        check_psd(psd[k], G["tones_psd"][k], 2048)
+        check_psd(psd[k], G["tones_psd"][k], 2048, 96000)
 
 
 @pytest.mark.parametrize("n,rate", [(9600, 96000), (4800, 48000), (19200, 192000)])
@@ -177,12 +181,12 @@ def test_fft_default_non_power_of_two_frames(n, rate):
         got = spec[k, 0::2] + 1j * spec[k, 1::2]
         assert np.abs(got - want).max() <= FFT_RTOL * np.abs(want).max()
     for k in range(nchk):
-        check_psd(f.receive(bufs[k]), O.fft_receive(bufs[k], rate), n)
+        check_psd(f.receive(bufs[k]), O.fft_receive(bufs[k], rate), n, rate)
     # raw (IRawHandler) form with DC correction, batched, ragged count
     raw = rng.integers(-20000, 20000, (5, 2 * n)).astype(np.int16)
     psd = f.batch_host_i16(raw, ic=11, qc=-7)
     for k in range(5 if n < 19200 else 1):
-        check_psd(psd[k], O.fft_receive(O.convert_i16(raw[k], ic=11, qc=-7), rate), n)
+        check_psd(psd[k], O.fft_receive(O.convert_i16(raw[k], ic=11, qc=-7), rate), n, rate)
     # every frame of the batch against numpy's FFT of the converted samples (independent of the oracle)
     for k in range(5):
         x = O.convert_i16(raw[k], ic=11, qc=-7).astype(np.float64)
@@ -228,10 +232,10 @@ def test_fft_any_frame_size(n, rate):
         assert np.abs(got - want).max() <= FFT_RTOL * np.abs(want).max()
     nchk = 3 if n <= 4410 else 1  # (the oracle's exact DFT is O(n^2) in long double)
     for k in range(nchk):
-        check_psd(f.receive(bufs[k]), O.fft_receive(bufs[k], rate), n)
+        check_psd(f.receive(bufs[k]), O.fft_receive(bufs[k], rate), n, rate)
     raw = rng.integers(-20000, 20000, (5, 2 * n)).astype(np.int16)
     psd = f.batch_host_i16(raw, ic=11, qc=-7)
-    check_psd(psd[4], O.fft_receive(O.convert_i16(raw[4], ic=11, qc=-7), rate), n)
+    check_psd(psd[4], O.fft_receive(O.convert_i16(raw[4], ic=11, qc=-7), rate), n, rate)
     for k in range(5):
         xx = O.convert_i16(raw[k], ic=11, qc=-7).astype(np.float64)
         pw = np.abs(np.fft.fft(xx[0::2] + 1j * xx[1::2])) ** 2 * (2.0 / n) ** 2
@@ -251,7 +255,7 @@ def test_fft_sine4410_wav_at_its_own_rate(golden_dir):
     f = J.Fft(n, 44100)
     for k in range(2):
         psd = f.receive_raw(raw[2 * n * k:2 * n * (k + 1)])
-        check_psd(psd, O.fft_receive(O.convert_i16(raw[2 * n * k:2 * n * (k + 1)]), 44100), n)
+        check_psd(psd, O.fft_receive(O.convert_i16(raw[2 * n * k:2 * n * (k + 1)]), 44100), n, 44100)
         assert abs(abs(psd[n]) - 4410.0) <= 44100 / n + 1  # the tone the file is named after
 
 
@@ -270,7 +274,7 @@ def test_fft_frame_independence_in_a_4096_frame_batch():
     raw = d_raw.to_host(np.int16).reshape(nframes, 2 * n)
     for k in (0, 1, 777, 4095):
         assert np.array_equal(f.receive_raw(raw[k]), psd[k])
-        check_psd(psd[k], O.fft_receive(O.convert_i16(raw[k]), 96000), n)
+        check_psd(psd[k], O.fft_receive(O.convert_i16(raw[k]), 96000), n, 96000)
 
 
 def test_fft_run_time_plan_at_random_smooth_sizes():
@@ -317,5 +321,5 @@ def test_fft_run_time_plan_at_random_sizes_with_large_prime_factors():
             want = np.fft.fft(bufs[k, 0::2].astype(np.float64) + 1j * bufs[k, 1::2].astype(np.float64))
             got = spec[k, 0::2] + 1j * spec[k, 1::2]
             assert np.abs(got - want).max() <= FFT_RTOL * np.abs(want).max(), (n, prime_factors(n))
-            check_psd(psd[k], O.fft_receive(bufs[k], 10 * n), n)
+            check_psd(psd[k], O.fft_receive(bufs[k], 10 * n), n, 10 * n)
     assert seen == {"k_fft_rt", "k_dft_any"}

@@ -111,7 +111,7 @@ def test_fft_psd_config2_past_2_to_33_bytes_and_its_waterfall():
         got = B.read_rows(d_psd, rows, 4 * (n + 2), dtype=np.float32)
         refs = {c: O.fft_receive(O.convert_i16(src[c]), 96000) for c in {B.twin(r) for r in rows}}
         for r in rows:
-            check_psd(got[r], refs[B.twin(r)], n)
+            check_psd(got[r], refs[B.twin(r)], n, 96000)
         B.check_twins(d_psd, nfr, 4 * (n + 2), what="psd row")
         # the waterfall of that PSD
         free(d_in)
@@ -167,7 +167,7 @@ def test_float_input_path_past_2_to_33_bytes():
             want = np.fft.fft(x[0::2] + 1j * x[1::2])
             got = spec[r][0::2].astype(np.float64) + 1j * spec[r][1::2].astype(np.float64)
             assert np.abs(got - want).max() <= FFT_RTOL * np.abs(want).max(), f"spectrum row {r}"
-            check_psd(psd[r], O.fft_receive(bufs[c], 96000), n)
+            check_psd(psd[r], O.fft_receive(bufs[c], 96000), n, 96000)
         B.check_twins(d_f, nfr, 8 * n, what="converted row")
         B.check_twins(d_spec, nfr, 8 * n, what="spectrum row")
         B.check_twins(d_psd, nfr, 4 * (n + 2), what="psd row")
@@ -209,7 +209,7 @@ def test_fft_other_frame_sizes_past_32_bit_offsets(n, rate, nfr, kernel, cross):
             pw = np.sqrt(np.abs(np.fft.fft(x[0::2] + 1j * x[1::2])) ** 2 * (2.0 / n) ** 2)
             assert np.abs(10.0 ** (psd[r][:n].astype(np.float64) / 20) - pw).max() <= FFT_RTOL * pw.max(), f"psd row {r}"
             if c not in oracle_done and len(oracle_done) < (2 if n > 4410 else 6):
-                check_psd(psd[r], O.fft_receive(O.convert_i16(src[c], ic=11, qc=-7), rate), n)
+                check_psd(psd[r], O.fft_receive(O.convert_i16(src[c], ic=11, qc=-7), rate), n, rate)
                 oracle_done.add(c)
         B.check_twins(d_psd, nfr, 4 * (n + 2), what="psd row")
     finally:

@@ -179,7 +179,7 @@ def test_fft_batch_poisoned_around_the_frames_and_guarded_psd(n, rate, nf, kerne
     for k in range(nf):
         frame = raw[2 * n * k:2 * n * (k + 1)]
         assert psds[0][k].tobytes() == f.receive_raw(frame).tobytes(), (n, nf, k)
-        check_psd(psds[0][k], O.fft_receive(flt[2 * n * k:2 * n * (k + 1)], rate), n)
+        check_psd(psds[0][k], O.fft_receive(flt[2 * n * k:2 * n * (k + 1)], rate), n, rate)
     # the complex spectrum: equal to the contiguous call, and within FFT_RTOL of a float64 FFT
     buf, _ = LY.build_input([flt], lead=2, tail=2 * 33, unit=2, seed=100 + nf)
     d_in = upload(buf)
@@ -441,7 +441,7 @@ def test_group_strided_psd_and_slots_of_two_members_on_one_device():
             for k in (0, nf - 1):
                 frame = rows[s][2 * n * k:2 * n * (k + 1)]
                 assert got[m][sl, k].tobytes() == f.receive_raw(frame).tobytes(), (call, s, k)
-                check_psd(got[m][sl, k], O.fft_receive(O.convert_i16(frame), 96000), n)
+                check_psd(got[m][sl, k], O.fft_receive(O.convert_i16(frame), 96000), n, 96000)
         one = upload(LY.build_input(rows, stride, lead=2, tail=2 * 33, unit=2, seed=7)[0])
         ref.batch_i16(one.ptr + 4, stride, L)
         _, want = pack_slots_guarded(ref, S, "reference slots")
