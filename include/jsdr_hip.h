@@ -121,6 +121,38 @@ int jsdr_fft_waterfall_i16(jsdr_fft *h, const int16_t *raw_dev, int64_t nframes,
 int jsdr_fft_waterfall_f32(jsdr_fft *h, const float *iq_dev, int64_t nframes, int width, uint32_t peak_rgb,
                            uint32_t *pix_dev, float *max_dev, float *peak_dev, void *stream);
 const char *jsdr_fft_waterfall_kernel(jsdr_fft *h);   /* what the last waterfall call launched */
+/* The batch and the waterfall calls over raw[stream][stride], as every other batch entry point takes its IQ: one launch
+ * where rows longer than a call (a ring per stream, the chunked calls of a longer capture, a 2 * max_batch stride) took one
+ * launch a stream.
+ *   frame j of stream s   starts at element s * stream_stride + j * 2n of the input (int16 / float values);
+ *   its PSD row           is at psd_dev + s * psd_stream_stride_f32 + j * (n + 2); psd_stream_stride_f32 == 0 means packed,
+ *                         frames_per_stream * (n + 2);
+ *   the waterfall outputs are packed: row s * frames_per_stream + j of pix_dev, max_dev and peak_dev, each
+ *                         [nstreams * frames_per_stream][...] as in jsdr_fft_waterfall_*.
+ * Defined by composition, bit for bit: what stream s receives equals what jsdr_fft_batch_i16(h, raw_dev + s * stream_stride,
+ * frames_per_stream, ic, qc, psd_dev + s * psd_stride, stream) writes, likewise _f32 and jsdr_fft_waterfall_* with that
+ * stream's block of rows.  Input outside the frames is not read into any result; output between a stream's last row and the
+ * next stream's first is not written.  Every frame size jsdr_fft_create accepts is served by a strided instantiation of the
+ * handle's own kernel (jsdr_fft_kernel / jsdr_fft_waterfall_kernel name it as before; the fallback's chunks of 1024 rows run
+ * across stream boundaries); a frame's (stream, frame) pair is found once per frame -- one division when a workgroup starts,
+ * additions from there on.  jsdr_fft_set_cu_share and jsdr_fft_last_launch apply as to the batch kernel.  A call whose rows
+ * are in fact packed -- stream_stride == frames_per_stream * 2n and a packed PSD stride, or nstreams == 1 -- IS the contiguous
+ * call of nstreams * frames_per_stream frames: the same launch of the same kernel.  Asynchronous on `stream`.
+ * JSDR_ERR before any device work, the message naming the argument: a null handle, input or required output (psd_dev,
+ * pix_dev); nstreams <= 0; frames_per_stream < 0; with nstreams > 1 an input stride that is odd or below
+ * frames_per_stream * 2n; a non-zero PSD stride below frames_per_stream * (n + 2); width <= 0.  frames_per_stream == 0 is
+ * JSDR_OK and launches nothing.  (Not covered: the JNI shim and the Java classes, jsdr_fft_spectrum_f32, jsdr_harness.) */
+int jsdr_fft_batch_streams_i16(jsdr_fft *h, const int16_t *raw_dev, int nstreams, int64_t stream_stride_i16,
+                               int64_t frames_per_stream, int ic, int qc,
+                               float *psd_dev, int64_t psd_stream_stride_f32, void *stream);
+int jsdr_fft_batch_streams_f32(jsdr_fft *h, const float *iq_dev, int nstreams, int64_t stream_stride_f32,
+                               int64_t frames_per_stream, float *psd_dev, int64_t psd_stream_stride_f32, void *stream);
+int jsdr_fft_waterfall_streams_i16(jsdr_fft *h, const int16_t *raw_dev, int nstreams, int64_t stream_stride_i16,
+                                   int64_t frames_per_stream, int ic, int qc, int width, uint32_t peak_rgb,
+                                   uint32_t *pix_dev, float *max_dev, float *peak_dev, void *stream);
+int jsdr_fft_waterfall_streams_f32(jsdr_fft *h, const float *iq_dev, int nstreams, int64_t stream_stride_f32,
+                                   int64_t frames_per_stream, int width, uint32_t peak_rgb,
+                                   uint32_t *pix_dev, float *max_dev, float *peak_dev, void *stream);
 
 /* ------------------------------------------------------------------ phase.java
  * phase.java:75-80 max|x| over the 2n floats of a frame; :93-116 per-pixel-column means of I and Q

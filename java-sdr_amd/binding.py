@@ -243,6 +243,34 @@ class Fft:
                                             _addr(pix_dev), _addr(max_dev), _addr(peak_dev), C.c_void_p(stream)),
                "jsdr_fft_waterfall_f32")
 
+    def batch_streams_i16(self, raw_dev, nstreams, stream_stride_i16, frames_per_stream, psd_dev, psd_stream_stride_f32=0, ic=0,
+                          qc=0, stream=None):
+        """batch_i16 over raw[stream][stride]: frame j of stream s at int16 s * stream_stride_i16 + j * 2n, its PSD row at float
+        s * psd_stream_stride_f32 + j * (n + 2) (0: packed).  One launch; each stream's rows are batch_i16's, bit for bit."""
+        _check(lib().jsdr_fft_batch_streams_i16(self.h, _addr(raw_dev), int(nstreams), C.c_int64(stream_stride_i16),
+                                                C.c_int64(frames_per_stream), int(ic), int(qc), _addr(psd_dev),
+                                                C.c_int64(psd_stream_stride_f32), C.c_void_p(stream)), "jsdr_fft_batch_streams_i16")
+
+    def batch_streams_f32(self, iq_dev, nstreams, stream_stride_f32, frames_per_stream, psd_dev, psd_stream_stride_f32=0, stream=None):
+        _check(lib().jsdr_fft_batch_streams_f32(self.h, _addr(iq_dev), int(nstreams), C.c_int64(stream_stride_f32),
+                                                C.c_int64(frames_per_stream), _addr(psd_dev), C.c_int64(psd_stream_stride_f32),
+                                                C.c_void_p(stream)), "jsdr_fft_batch_streams_f32")
+
+    def waterfall_streams_i16(self, raw_dev, nstreams, stream_stride_i16, frames_per_stream, width, pix_dev, ic=0, qc=0,
+                              peak_rgb=0x00FFFF, max_dev=None, peak_dev=None, stream=None):
+        """waterfall_i16 over raw[stream][stride]; the outputs are packed, row s * frames_per_stream + j."""
+        _check(lib().jsdr_fft_waterfall_streams_i16(self.h, _addr(raw_dev), int(nstreams), C.c_int64(stream_stride_i16),
+                                                    C.c_int64(frames_per_stream), int(ic), int(qc), int(width), C.c_uint32(peak_rgb),
+                                                    _addr(pix_dev), _addr(max_dev), _addr(peak_dev), C.c_void_p(stream)),
+               "jsdr_fft_waterfall_streams_i16")
+
+    def waterfall_streams_f32(self, iq_dev, nstreams, stream_stride_f32, frames_per_stream, width, pix_dev, peak_rgb=0x00FFFF,
+                              max_dev=None, peak_dev=None, stream=None):
+        _check(lib().jsdr_fft_waterfall_streams_f32(self.h, _addr(iq_dev), int(nstreams), C.c_int64(stream_stride_f32),
+                                                    C.c_int64(frames_per_stream), int(width), C.c_uint32(peak_rgb), _addr(pix_dev),
+                                                    _addr(max_dev), _addr(peak_dev), C.c_void_p(stream)),
+               "jsdr_fft_waterfall_streams_f32")
+
     def waterfall_kernel(self):
         """what the last waterfall_* call launched: "k_fft_pix", or "<batch kernel>+k_waterfall" """
         return lib().jsdr_fft_waterfall_kernel(self.h).decode()

@@ -18,15 +18,16 @@ namespace jsdr {
 
 enum { DFT_T = 256 };
 
-template <int IN, int OUT>
-__global__ __launch_bounds__(DFT_T) void k_dft_any(FftArgs a, int n, int bins_per_group)
+// ARGS = Strided<FftArgs>: the strided instantiation (jsdr_fft_*_streams_*) -- a workgroup's frame is a FramePos (fft_common.h)
+template <int IN, int OUT, class ARGS = FftArgs>
+__global__ __launch_bounds__(DFT_T) void k_dft_any(ARGS a, int n, int bins_per_group)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     float2 *xs = reinterpret_cast<float2 *>(smem);
-    const long long f = blockIdx.x;
+    const auto f = frame_first(a, blockIdx.x);
     const int tid = threadIdx.x;
     if constexpr (IN == IN_I16) {
-        const int *raw = reinterpret_cast<const int *>(a.in) + f * n;
+        const int *raw = reinterpret_cast<const int *>(a.in) + frame_in(f, n);
         for (int t = tid; t < n; t += DFT_T) {
             const int w = raw[t];
             const int si = java_short_add((int)(short)(w & 0xffff), a.ic);  // JavaAudio.java:281-288
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(DFT_T) void k_dft_any(FftArgs a, int n, int bins_pe
             xs[t] = make_float2(i16_to_float_java(si), i16_to_float_java(sq));
         }
     } else {
-        const float2 *in = reinterpret_cast<const float2 *>(a.in) + f * n;
+        const float2 *in = reinterpret_cast<const float2 *>(a.in) + frame_in(f, n);
         for (int t = tid; t < n; t += DFT_T) xs[t] = in[t];
     }
     __syncthreads();
@@ -62,22 +63,21 @@ __global__ __launch_bounds__(DFT_T) void k_dft_any(FftArgs a, int n, int bins_pe
         }
         const float fr = (float)re, fi = (float)im;
         if constexpr (OUT == OUT_SPEC) {
-            reinterpret_cast<float2 *>(a.out)[f * n + k] = make_float2(fr, fi);
+            reinterpret_cast<float2 *>(a.out)[frame_out(f, n) + k] = make_float2(fr, fi);
         } else {
             float cf = 2.0f / (float)n;  // fft.java:196-197
             cf = __fmul_rn(cf, cf);
             const float pw = __fmul_rn(__fadd_rn(__fmul_rn(fr, fr), __fmul_rn(fi, fi)), cf);  // :207, float products
-            a.out[f * (n + 2) + k] = 10.0f * (float)log10((double)pw);
+            a.out[frame_out(f, n + 2) + k] = 10.0f * (float)log10((double)pw);
         }
     }
 }
 
-// first strictly greater maximum (fft.java:208-211), bin -> Hz in Java int arithmetic (:214-221)
-__global__ __launch_bounds__(DFT_T) void k_psd_fin(float *psd, int n, int rate)
+// first strictly greater maximum (fft.java:208-211), bin -> Hz in Java int arithmetic (:214-221), of the row at p
+__device__ __forceinline__ void psd_fin_row(float *p, int n, int rate)
 {
     __shared__ float bv[DFT_T];
     __shared__ int bk[DFT_T];
-    float *p = psd + (long long)blockIdx.x * (n + 2);
     float best = -3.402823466e+38f;  // -Float.MAX_VALUE (:199)
     int kb = -1;
     for (int k = threadIdx.x; k < n; k += DFT_T) {  // ascending k per thread: a later equal value does not replace
@@ -119,6 +119,15 @@ __global__ __launch_bounds__(DFT_T) void k_psd_fin(float *psd, int n, int rate)
     }
 }
 
+__global__ __launch_bounds__(DFT_T) void k_psd_fin(float *psd, int n, int rate)
+{
+    psd_fin_row(psd + (long long)blockIdx.x * (n + 2), n, rate);
+}
+__global__ __launch_bounds__(DFT_T) void k_psd_fin_streams(float *psd, int n, int rate, StreamGeom g)
+{
+    psd_fin_row(psd + stream_pos(g, blockIdx.x).out, n, rate);
+}
+
 bool dft_any_supported(int n) { return n >= 2 && n <= 20000; }  // (the frame as float pairs fits a workgroup's LDS)
 
 int dft_any_launch(const FftArgs &a, int n, int in_kind, int out_kind, int num_cu, hipStream_t st)
@@ -149,6 +158,31 @@ int dft_any_launch(const FftArgs &a, int n, int in_kind, int out_kind, int num_c
         hipLaunchKernelGGL(k_psd_fin, dim3((unsigned)a.nframes), dim3(DFT_T), 0, st, a.out, n, a.rate);
         JSDR_LAUNCH_CHECK();
     }
+    return JSDR_OK;
+}
+
+int dft_any_launch_streams(const Strided<FftArgs> &a, int n, int in_kind, int num_cu, hipStream_t st)
+{
+    long long groups = 1;  // (as dft_any_launch)
+    if (a.nframes < 2LL * num_cu) {
+        groups = (2LL * num_cu + a.nframes - 1) / a.nframes;
+        const long long maxg = (n + DFT_T - 1) / DFT_T;
+        if (groups > maxg) groups = maxg;
+    }
+    const int bins = (int)((n + groups - 1) / groups);
+    const size_t lds = sizeof(float2) * (size_t)n;
+    const dim3 grid((unsigned)a.nframes, (unsigned)((n + bins - 1) / bins)), block(DFT_T);
+    JSDR_REQUIRE(a.nframes <= 0x7fffffffLL, "fft: too many frames for one launch");
+    if (in_kind == IN_I16) {
+        JSDR_LDS_ATTR((k_dft_any<IN_I16, OUT_PSD, Strided<FftArgs>>), lds);
+        hipLaunchKernelGGL((k_dft_any<IN_I16, OUT_PSD, Strided<FftArgs>>), grid, block, lds, st, a, n, bins);
+    } else {
+        JSDR_LDS_ATTR((k_dft_any<IN_F32, OUT_PSD, Strided<FftArgs>>), lds);
+        hipLaunchKernelGGL((k_dft_any<IN_F32, OUT_PSD, Strided<FftArgs>>), grid, block, lds, st, a, n, bins);
+    }
+    JSDR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_psd_fin_streams, dim3((unsigned)a.nframes), dim3(DFT_T), 0, st, a.out, n, a.rate, a.g);
+    JSDR_LAUNCH_CHECK();
     return JSDR_OK;
 }
 

@@ -2,6 +2,7 @@
 // spectrum kernels: compile-time twiddles, in-register radix-2^k DFT, LDS padding.
 #pragma once
 #include "common.h"
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -142,6 +143,102 @@ struct FftArgs {
 #endif
 };
 
+// ------------------------------------------------------------------ strided batches (jsdr_fft_batch_streams_* / jsdr_fft_waterfall_streams_*)
+// The launch's frame k is frame j of stream s with (s, j) = ((f0 + k) / fps, (f0 + k) % fps); it is read at point
+// s * in_stride + j * n of the input and its PSD row is written at float out_base + s * out_stride + j * (n + 2).  A workgroup
+// divides ONCE, for the first frame it takes; from there it walks: a persistent workgroup's next frame is `step` frames on
+// (the grid is known to the host, which states the step as offsets), and a walk that leaves its stream adds the gap.  What a
+// frame costs is four 64-bit additions and a compare -- scalar ones where the frame is the same in every lane of a wave.
+struct StreamGeom {
+    long long fps;                 // frames per stream
+    long long f0;                  // the launch's frame 0 in the call's numbering (the waterfall fallback goes in chunks)
+    long long in_stride;           // points between the first frames of two streams
+    long long out_stride;          // floats between the first PSD rows of two streams
+    long long out_base;            // of the launch's output pointer (a chunk's rows are packed from its own frame 0: -f0 * (n + 2))
+    long long step_j;              // the step as (streams, frames): its frames ...
+    long long step_in, step_out;   // ... and what it adds to the two offsets while the walk stays inside fps
+    long long wrap_in, wrap_out;   // added as well when j passes fps: stride - fps * row
+    long long last_in, last_out;   // the launch's last frame (k_fft's surplus part-workgroup redoes it)
+    int n;                         // points a frame (k_fft_mixed_dual's template N is half of it)
+};
+template <class BASE>
+struct Strided : BASE {
+    StreamGeom g;
+};
+template <class ARGS>
+struct is_strided : std::false_type {};
+template <class B>
+struct is_strided<Strided<B>> : std::true_type {};
+// host: the geometry of frames [f0, f0 + nf) of a call; strides in points / floats.  The step waits for the grid.
+inline StreamGeom stream_geom(int n, long long fps, long long in_stride, long long out_stride, long long f0, long long nf, long long out_base)
+{
+    StreamGeom g = {};
+    g.fps = fps;
+    g.f0 = f0;
+    g.in_stride = in_stride;
+    g.out_stride = out_stride;
+    g.out_base = out_base;
+    g.wrap_in = in_stride - fps * n;
+    g.wrap_out = out_stride - fps * (n + 2);
+    const long long s = (f0 + nf - 1) / fps, j = (f0 + nf - 1) % fps;
+    g.last_in = s * in_stride + j * n;
+    g.last_out = out_base + s * out_stride + j * (n + 2);
+    g.n = n;
+    return g;
+}
+inline void stream_geom_step(StreamGeom &g, long long step)
+{
+    const long long ss = step / g.fps;
+    g.step_j = step % g.fps;
+    g.step_in = ss * g.in_stride + g.step_j * g.n;
+    g.step_out = ss * g.out_stride + g.step_j * (g.n + 2);
+}
+struct FramePos {
+    long long f;        // the launch's frame number: the loop bound, and the row of the packed waterfall outputs
+    long long j;        // frame within its stream
+    long long in, out;  // offsets, as above
+};
+__device__ __forceinline__ FramePos stream_pos(const StreamGeom &g, long long f)
+{
+    FramePos p;
+    const unsigned long long G = (unsigned long long)(g.f0 + f), s = G / (unsigned long long)g.fps;
+    p.f = f;
+    p.j = (long long)(G - s * (unsigned long long)g.fps);
+    p.in = (long long)s * g.in_stride + p.j * g.n;
+    p.out = g.out_base + (long long)s * g.out_stride + p.j * (g.n + 2);
+    return p;
+}
+__device__ __forceinline__ void stream_step(const StreamGeom &g, FramePos &p, long long step)
+{
+    p.f += step;
+    p.j += g.step_j;
+    p.in += g.step_in;
+    p.out += g.step_out;
+    if (p.j >= g.fps) {
+        p.j -= g.fps;
+        p.in += g.wrap_in;
+        p.out += g.wrap_out;
+    }
+}
+
+// A kernel's frame is a number (contiguous batches: frame f lies at f * row) or a FramePos (strided ones); the kernels state
+// their frame loop and their addresses through these, and each instantiation gets its own form at compile time.
+__device__ __forceinline__ long long frame_first(const FftArgs &, long long f) { return f; }
+__device__ __forceinline__ bool frame_more(const FftArgs &a, long long f) { return f < a.nframes; }
+__device__ __forceinline__ void frame_next(const FftArgs &, long long &f, long long step) { f += step; }
+template <class B>
+__device__ __forceinline__ FramePos frame_first(const Strided<B> &a, long long f) { return stream_pos(a.g, f); }
+template <class B>
+__device__ __forceinline__ bool frame_more(const Strided<B> &a, const FramePos &p) { return p.f < a.nframes; }
+template <class B>
+__device__ __forceinline__ void frame_next(const Strided<B> &a, FramePos &p, long long step) { stream_step(a.g, p, step); }
+__device__ __forceinline__ long long frame_in(long long f, int n) { return f * n; }               // points
+__device__ __forceinline__ long long frame_in(const FramePos &p, int) { return p.in; }
+__device__ __forceinline__ long long frame_out(long long f, int row) { return f * row; }          // floats (float2 of a spectrum)
+__device__ __forceinline__ long long frame_out(const FramePos &p, int) { return p.out; }
+__device__ __forceinline__ long long frame_row(long long f) { return f; }                         // row of a packed output
+__device__ __forceinline__ long long frame_row(const FramePos &p) { return p.f; }
+
 struct Best {
     float v;
     int k;
@@ -172,5 +269,11 @@ int rt_launch(const FftArgs &a, int n, int in_kind, int out_kind, int num_cu, hi
 // what is left -- prime frame sizes, frames above 9800 samples (fft_any.hip): the DFT itself, double accumulation
 bool dft_any_supported(int n);
 int dft_any_launch(const FftArgs &a, int n, int in_kind, int out_kind, int num_cu, hipStream_t st);
+
+// the strided forms of the four (PSD rows only): the same kernels' strided instantiations on the same grids
+int mixed_launch_streams(const MixedPlan &p, const Strided<FftArgs> &a, int in_kind, int grid, hipStream_t st);
+int mixed_launch_split2_streams(const MixedPlan &p, const Strided<FftArgs> &a, int in_kind, int num_cu, hipStream_t st);
+int rt_launch_streams(const Strided<FftArgs> &a, int n, int in_kind, int num_cu, hipStream_t st);
+int dft_any_launch_streams(const Strided<FftArgs> &a, int n, int in_kind, int num_cu, hipStream_t st);
 
 }  // namespace jsdr

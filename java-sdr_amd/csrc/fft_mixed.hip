@@ -101,8 +101,23 @@ __device__ __forceinline__ void mixed_twiddles_apply(float2 *v, int k, const flo
     }
 }
 
-template <int N, int T, int IN, int OUT, int R, int P, bool FIRST, bool LAST>
-__device__ __forceinline__ void mixed_pass(const FftArgs &a, long long frame, int tid, float2 *buf, const float2 *tab,
+// where a frame's (or, split, a half frame's) first point lies; a strided frame carries its offset (the dual kernel adds the half)
+template <int N>
+__device__ __forceinline__ long long mixed_in(const FftArgs &a, long long frame)
+{
+    return a.split ? (frame >> 1) * (2LL * N) + (frame & 1) : frame * (long long)N;
+}
+template <int N>
+__device__ __forceinline__ long long mixed_in(const FftArgs &, const FramePos &p) { return p.in; }
+__device__ __forceinline__ long long mixed_half(long long frame, int h) { return 2 * frame + h; }
+__device__ __forceinline__ FramePos mixed_half(FramePos p, int h)
+{
+    p.in += h;
+    return p;
+}
+
+template <int N, int T, int IN, int OUT, int R, int P, bool FIRST, bool LAST, class FR>
+__device__ __forceinline__ void mixed_pass(const FftArgs &a, FR frame, int tid, float2 *buf, const float2 *tab,
                                            Best &best)
 {
     constexpr int NB = N / R;
@@ -112,7 +127,7 @@ __device__ __forceinline__ void mixed_pass(const FftArgs &a, long long frame, in
         // all of a thread's samples are requested before the first one is converted: loads under a per-butterfly
         // guard were issued one at a time, each waiting for the one before (R * ITERS memory latencies per frame)
         // split: this transform is the even / odd half of input frame (frame >> 1), 2N samples long
-        const long long fbase = a.split ? (frame >> 1) * (2LL * N) + (frame & 1) : frame * (long long)N;
+        const long long fbase = mixed_in<N>(a, frame);
         const int st = a.split ? 2 : 1;
         if constexpr (IN == IN_I16) {
             const int *src = reinterpret_cast<const int *>(a.in) + fbase;
@@ -164,12 +179,12 @@ __device__ __forceinline__ void mixed_pass(const FftArgs &a, long long frame, in
 #pragma unroll
                 for (int r = 0; r < R; r++) buf[mpad<N>(j0 + r * P)] = v[it][out_slot<R>(r)];
             } else if constexpr (OUT == OUT_SPEC) {
-                float2 *dst = reinterpret_cast<float2 *>(a.out) + frame * N;
+                float2 *dst = reinterpret_cast<float2 *>(a.out) + frame_out(frame, N);
 #pragma unroll
                 for (int r = 0; r < R; r++) dst[j0 + r * P] = v[it][out_slot<R>(r)];
             } else {
                 const float cf = (2.0f / (float)N) * (2.0f / (float)N);
-                float *dst = a.out + frame * (N + 2);
+                float *dst = a.out + frame_out(frame, N + 2);
 #pragma unroll
                 for (int r = 0; r < R; r++) {
                     const float2 x = v[it][out_slot<R>(r)];
@@ -188,8 +203,10 @@ __device__ __forceinline__ void mixed_pass(const FftArgs &a, long long frame, in
     if constexpr (!LAST) __syncthreads();
 }
 
-template <int N, int T, int IN, int OUT, int R0, int R1, int R2, int R3, int R4>
-__global__ __launch_bounds__(T, (N == 9600 ? 2 : 4)) void k_fft_mixed(FftArgs a)
+// ARGS = Strided<FftArgs>: the strided instantiation (jsdr_fft_*_streams_*) -- the frame is a FramePos, walked by the frame loop
+// (fft_common.h).  The default is the contiguous kernel, whose frame is its number.
+template <int N, int T, int IN, int OUT, int R0, int R1, int R2, int R3, int R4, class ARGS = FftArgs>
+__global__ __launch_bounds__(T, (N == 9600 ? 2 : 4)) void k_fft_mixed(ARGS a)
 {
     static_assert(R0 * R1 * R2 * R3 * R4 == N, "radix plan must multiply to N");
     extern __shared__ __align__(16) unsigned char smem[];
@@ -207,7 +224,7 @@ __global__ __launch_bounds__(T, (N == 9600 ? 2 : 4)) void k_fft_mixed(FftArgs a)
     const float2 *tw4 = (TWL == TWN) ? tw + O4 : a.tw + O4;
     const float2 *tw5 = (TWL == TWN) ? tw + O5 : a.tw + O5;
     __syncthreads();
-    for (long long frame = blockIdx.x; frame < a.nframes; frame += gridDim.x) {
+    for (auto frame = frame_first(a, blockIdx.x); frame_more(a, frame); frame_next(a, frame, gridDim.x)) {
         Best best;
         best.v = -3.402823466e+38f;
         best.k = 0x7fffffff;
@@ -255,7 +272,7 @@ __global__ __launch_bounds__(T, (N == 9600 ? 2 : 4)) void k_fft_mixed(FftArgs a)
                 const int datlen = 2 * N;
                 if (p >= datlen / 2) p -= datlen;
                 int hz = (int)((unsigned)p * (unsigned)a.rate) / datlen;
-                float *dst = a.out + frame * (N + 2);
+                float *dst = a.out + frame_out(frame, N + 2);
                 dst[N] = (float)hz;
                 dst[N + 1] = m;
             }
@@ -269,8 +286,8 @@ __global__ __launch_bounds__(T, (N == 9600 ? 2 : 4)) void k_fft_mixed(FftArgs a)
 // One workgroup runs both half transforms back to back, each into its own LDS image (2 x 79 KB), and combines them
 // from LDS with the PSD epilogue: 4 B in, 4 B out per sample, where the former two-kernel form moved the half
 // spectra through HBM (three times the traffic).
-template <int T, int IN, int OUT>
-__global__ __launch_bounds__(T) void k_fft_mixed_dual(FftArgs a, const float2 *__restrict__ wcomb)
+template <int T, int IN, int OUT, class ARGS = FftArgs>
+__global__ __launch_bounds__(T) void k_fft_mixed_dual(ARGS a, const float2 *__restrict__ wcomb)
 {
     constexpr int N = 9600, R0 = 16, R1 = 8, R2 = 5, R3 = 5, R4 = 3, N2 = 2 * N;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -287,7 +304,7 @@ __global__ __launch_bounds__(T) void k_fft_mixed_dual(FftArgs a, const float2 *_
     for (int i = tid; i < TWL; i += T) tw[i] = a.tw[i];
     const float2 *tw4 = a.tw + O4, *tw5 = a.tw + O5;
     __syncthreads();
-    for (long long frame = blockIdx.x; frame < a.nframes; frame += gridDim.x) {
+    for (auto frame = frame_first(a, blockIdx.x); frame_more(a, frame); frame_next(a, frame, gridDim.x)) {
         Best best;
         best.v = -3.402823466e+38f;
         best.k = 0x7fffffff;
@@ -296,7 +313,7 @@ __global__ __launch_bounds__(T) void k_fft_mixed_dual(FftArgs a, const float2 *_
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             float2 *buf = h ? bufO : bufE;
-            const long long hf = 2 * frame + h;  // a.split addressing: even / odd samples of frame `frame`
+            const auto hf = mixed_half(frame, h);  // a.split addressing: even / odd samples of frame `frame`
             int th = tf;
             asm volatile("" : "+v"(th));  // (and per half: shared between the halves, the addresses live through ten passes)
             mixed_pass<N, T, IN, OUT_SPEC, R0, 1, true, false>(a, hf, th, buf, tw, best);
@@ -320,12 +337,12 @@ __global__ __launch_bounds__(T) void k_fft_mixed_dual(FftArgs a, const float2 *_
                 const float2 t = cmul(bufO[mpad<N>(k)], wk[it]);
                 const float2 x0 = cadd(e, t), x1 = csub(e, t);
                 if constexpr (OUT == OUT_SPEC) {
-                    float2 *dst = reinterpret_cast<float2 *>(a.out) + frame * N2;
+                    float2 *dst = reinterpret_cast<float2 *>(a.out) + frame_out(frame, N2);
                     dst[k] = x0;
                     dst[k + N] = x1;
                 } else {
                     const float cf = (2.0f / (float)N2) * (2.0f / (float)N2);
-                    float *dst = a.out + frame * (N2 + 2);
+                    float *dst = a.out + frame_out(frame, N2 + 2);
                     const float d0 = 3.0102999566398120f * __log2f((x0.x * x0.x + x0.y * x0.y) * cf);  // fft.java:207
                     const float d1 = 3.0102999566398120f * __log2f((x1.x * x1.x + x1.y * x1.y) * cf);
                     dst[k] = d0;
@@ -373,7 +390,7 @@ __global__ __launch_bounds__(T) void k_fft_mixed_dual(FftArgs a, const float2 *_
                 const int datlen = 2 * N2;
                 if (p >= datlen / 2) p -= datlen;
                 const int hz = (int)((unsigned)p * (unsigned)a.rate) / datlen;
-                float *dst = a.out + frame * (N2 + 2);
+                float *dst = a.out + frame_out(frame, N2 + 2);
                 dst[N2] = (float)hz;
                 dst[N2 + 1] = m;
             }
@@ -500,6 +517,52 @@ int mixed_launch_split2(const MixedPlan &p, const FftArgs &a, int in_kind, int o
     if (in_kind == IN_F32 && out_kind == OUT_SPEC) return go(k_fft_mixed_dual<T, IN_F32, OUT_SPEC>);
     if (in_kind == IN_I16 && out_kind == OUT_SPEC) return go(k_fft_mixed_dual<T, IN_I16, OUT_SPEC>);
     JSDR_REQUIRE(false, "fft: no kernel for in=%d out=%d", in_kind, out_kind);
+}
+
+template <int N, int T, int R0, int R1, int R2, int R3, int R4>
+static int mixed_launch_streams_t(const MixedPlan &p, const Strided<FftArgs> &a, int in_kind, int grid, hipStream_t st)
+{
+    Strided<FftArgs> b = a;
+    stream_geom_step(b.g, grid);
+    auto go = [&](auto kern) -> int {
+        JSDR_LDS_ATTR(kern, p.lds_bytes);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(T), p.lds_bytes, st, b);
+        JSDR_LAUNCH_CHECK();
+        return JSDR_OK;
+    };
+    if (in_kind == IN_I16) return go(k_fft_mixed<N, T, IN_I16, OUT_PSD, R0, R1, R2, R3, R4, Strided<FftArgs>>);
+    return go(k_fft_mixed<N, T, IN_F32, OUT_PSD, R0, R1, R2, R3, R4, Strided<FftArgs>>);
+}
+
+int mixed_launch_streams(const MixedPlan &p, const Strided<FftArgs> &a, int in_kind, int grid, hipStream_t st)
+{
+    if (p.n == 9600) return mixed_launch_streams_t<9600, 512, 16, 8, 5, 5, 3>(p, a, in_kind, grid, st);
+    if (p.n == 4800) return mixed_launch_streams_t<4800, 512, 16, 4, 5, 5, 3>(p, a, in_kind, grid, st);
+    set_error("fft: no mixed-radix plan for n=%d", p.n);
+    return JSDR_ERR;
+}
+
+int mixed_launch_split2_streams(const MixedPlan &p, const Strided<FftArgs> &a, int in_kind, int num_cu, hipStream_t st)
+{
+    JSDR_REQUIRE(p.n == 19200, "fft: no two-half plan for n=%d", p.n);
+    constexpr int T = 512, N = 9600;
+    constexpr int O4 = mtw_size(16, 8) + mtw_size(16 * 8, 5);
+    const size_t lds = sizeof(float2) * ((size_t)O4 + 2 * (size_t)mixed_frame_elems(N)) + (sizeof(float) + sizeof(int)) * ((T + 63) / 64) + 16;
+    static const int mgrid = [] { const char *e = knob("JSDR_MIXED_GRID"); return e ? atoi(e) : 16; }();
+    const long long cap = (long long)num_cu * mgrid;
+    const unsigned grid = (unsigned)(a.nframes < cap ? a.nframes : cap);
+    Strided<FftArgs> h = a;
+    h.split = 1;  // (the passes read every second point; the half's first point is in its FramePos)
+    stream_geom_step(h.g, grid);
+    const float2 *wcomb = a.tw + p.half_tw_count;
+    auto go = [&](auto kern) -> int {
+        JSDR_LDS_ATTR(kern, lds);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(T), lds, st, h, wcomb);
+        JSDR_LAUNCH_CHECK();
+        return JSDR_OK;
+    };
+    if (in_kind == IN_I16) return go(k_fft_mixed_dual<T, IN_I16, OUT_PSD, Strided<FftArgs>>);
+    return go(k_fft_mixed_dual<T, IN_F32, OUT_PSD, Strided<FftArgs>>);
 }
 
 int mixed_launch(const MixedPlan &p, const FftArgs &a, int in_kind, int out_kind, int grid, hipStream_t st)

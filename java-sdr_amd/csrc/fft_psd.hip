@@ -82,16 +82,16 @@ template <>
 struct RawPoint<IN_F32> {
     using type = float2;
 };
-template <int N, int T, int IN, int R>
-__device__ __forceinline__ void fft_fetch(const FftArgs &a, long long frame, int tid, typename RawPoint<IN>::type (&w)[R])
+template <int N, int T, int IN, int R, class FR>
+__device__ __forceinline__ void fft_fetch(const FftArgs &a, FR frame, int tid, typename RawPoint<IN>::type (&w)[R])
 {
     constexpr int NB = N / R;
     static_assert(NB == T, "one first-pass butterfly per thread");
     const typename RawPoint<IN>::type *src = reinterpret_cast<const typename RawPoint<IN>::type *>(a.in) +
 #ifdef JSDR_X_FFT_SMALLSET  // timing probe (round 5): every frame reads one of 8192 frames -- 64 MB, served by the memory-side cache
-        (frame & 8191) * N;
+        (frame_row(frame) & 8191) * N;
 #else
-        frame * N;
+        frame_in(frame, N);
 #endif
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -145,8 +145,8 @@ __device__ __forceinline__ float psd_db(float2 x)
 __device__ __forceinline__ int row_pad(int idx) { return idx + (idx >> 5); }
 constexpr bool fft_i16_scaled(int R0, int R1) { return tw_direct(R0, R1); }
 
-template <int N, int T, int IN, int OUT, int R, int P, bool FIRST, bool LAST, class RAW = int, int SC = SC_NONE>
-__device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool active, int tid, float2 *buf,
+template <int N, int T, int IN, int OUT, int R, int P, bool FIRST, bool LAST, class RAW = int, int SC = SC_NONE, class FR>
+__device__ __forceinline__ void fft_pass(const FftArgs &a, FR frame, bool active, int tid, float2 *buf,
                                          const float2 *tab, Best &best, const RAW *raw = nullptr)
 {
     constexpr int NB = N / R;
@@ -207,11 +207,11 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool
                 store_lds<R>(buf, v[gi], j0, P, std::make_integer_sequence<int, R>{});
             } else if (active) {
                 if constexpr (OUT == OUT_SPEC) {
-                    float2 *dst = reinterpret_cast<float2 *>(a.out) + frame * N;
+                    float2 *dst = reinterpret_cast<float2 *>(a.out) + frame_out(frame, N);
 #pragma unroll
                     for (int r = 0; r < R; r++) dst[j0 + r * P] = v[gi][cx_bitrev(r, R)];
                 } else {
-                    float *dst = a.out + frame * (N + 2);
+                    float *dst = a.out + frame_out(frame, N + 2);
                     float db[R];
 #pragma unroll
                     for (int r = 0; r < R; r++) {
@@ -246,8 +246,8 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, long long frame, bool
 
 // One frame, executed by T threads (tid in [0,T)).  `raw` holds the frame's first-pass inputs (fft_fetch); before the
 // last pass the NEXT frame's inputs are fetched into it.
-template <int N, int T, int IN, int OUT, int R0, int R1, int R2, int R3, class ARGS>
-__device__ __forceinline__ void fft_frame(const ARGS &a, long long frame, long long next, int tid, float2 *buf,
+template <int N, int T, int IN, int OUT, int R0, int R1, int R2, int R3, class ARGS, class FR, class FN>
+__device__ __forceinline__ void fft_frame(const ARGS &a, FR frame, FN next, int tid, float2 *buf,
                                           const float2 *tw_lds, float *red_val, int *red_idx, int frame_in_block,
                                           typename RawPoint<IN>::type (&raw)[R0])
 {
@@ -329,11 +329,11 @@ __device__ __forceinline__ void fft_frame(const ARGS &a, long long frame, long l
             int hz = (int)((unsigned)p * (unsigned)a.rate) / datlen;
             if constexpr (OUT == OUT_PIX) {
                 if (a.peak) {
-                    a.peak[frame * 2] = (float)hz;
-                    a.peak[frame * 2 + 1] = m;
+                    a.peak[frame_row(frame) * 2] = (float)hz;
+                    a.peak[frame_row(frame) * 2 + 1] = m;
                 }
             } else {
-                float *dst = a.out + frame * (N + 2);
+                float *dst = a.out + frame_out(frame, N + 2);
                 dst[N] = (float)hz;
                 dst[N + 1] = m;
             }
@@ -349,8 +349,8 @@ __device__ __forceinline__ void fft_frame(const ARGS &a, long long frame, long l
         const float step = wf_step(N, width);
         const int l = java_f2i(step);
         const WfColour colour = wf_colour(a.peak_rgb);
-        unsigned *prow = a.pix + frame * width;
-        float *mrow = a.maxo ? a.maxo + frame * width : nullptr;
+        unsigned *prow = a.pix + frame_row(frame) * width;
+        float *mrow = a.maxo ? a.maxo + frame_row(frame) * width : nullptr;
         for (int p = tid; p < width; p += T) {
             const float r = wf_getmax([&](int i) { return row[row_pad(i)]; }, java_f2i((float)p * step), l);
             if (mrow) mrow[p] = r;
@@ -384,6 +384,114 @@ __global__ __launch_bounds__(T *FPB, (N == 2048 ? 4 : N == 8192 ? 3 : 1)) void k
 #include "fft_block_body.h"
 }
 
+// The strided form of both (jsdr_fft_batch_streams_* / jsdr_fft_waterfall_streams_*; ARGS = Strided<FftArgs> / Strided<FftPixArgs>):
+// the same frame loop with a position where k_fft has a frame number.  Each of a workgroup's FPB frames maps on its own -- a
+// group of frames straddles two streams -- by one division when the workgroup starts; the persistent loop walks from there
+// (StreamGeom, fft_common.h).  What a surplus part-workgroup redoes is the launch's last frame, as in k_fft.
+//   T >= 64, a wave holds one frame: the frame's slot in the workgroup is made a scalar, and with it the whole position -- the
+//            walk is scalar arithmetic and takes no vector register from the frame loop.
+//   T <  64, a wave holds 64 / T frames with a position each: the positions live in LDS, a slot a frame, and are read where
+//            they are used -- the offset of the next frame's input at its fetch (which is also where the walk steps: before
+//            the last pass, registers to spare), the row's offset at the stores.  As vector registers they were live through
+//            every pass and cost the 64- to 256-point kernels a wave a SIMD.  A frame's threads are lanes of one wave: they
+//            read and write their slot in step, all the same values.
+struct LdsFrame {
+    const long long *slot;  // {j, in, out: of the frame being fetched or fetched last; out of the frame in flight}
+    long long f;            // the frame in flight (clamped): the row of the packed outputs
+};
+struct LdsNext {
+    long long *slot;
+    const StreamGeom *g;
+    long long step;
+    bool more, past;  // the workgroup has a further group of frames; that one lies past the launch's last frame
+};
+__device__ __forceinline__ long long frame_out(const LdsFrame &p, int) { return p.slot[3]; }
+__device__ __forceinline__ long long frame_row(const LdsFrame &p) { return p.f; }
+__device__ __forceinline__ long long frame_in(const LdsNext &q, int)
+{
+    if (!q.more) return q.slot[1];  // the last group fetches itself again
+    FramePos p;
+    p.f = 0;
+    p.j = q.slot[0];
+    p.in = q.slot[1];
+    p.out = q.slot[2];
+    stream_step(*q.g, p, q.step);
+    if (q.past) {
+        p.in = q.g->last_in;
+        p.out = q.g->last_out;
+    }
+    q.slot[0] = p.j;
+    q.slot[1] = p.in;
+    q.slot[2] = p.out;
+    return p.in;
+}
+
+template <int N, int T, int FPB, int IN, int OUT, int R0, int R1, int R2, int R3, class ARGS>
+__global__ __launch_bounds__(T *FPB, (N == 2048 ? 4 : (N == 8192 && OUT == OUT_PIX) ? 3 : N == 64 ? 8 : (N == 4096 && OUT == OUT_PSD) ? 4 : (N == 128 && OUT == OUT_PIX && IN == IN_F32) ? 6 : 1)) void k_fft_streams(ARGS a)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int FE = lds_frame_elems(N);
+    constexpr int TWN = tw_total(R0, R1, R2, R3);
+    float2 *tw_own = reinterpret_cast<float2 *>(smem);                    // [TWN]
+    float2 *bufs = tw_own + TWN;                                          // [FPB][FE]
+    float *red_val = reinterpret_cast<float *>(bufs + (size_t)FPB * FE);  // [FPB*NW]
+    int *red_idx = reinterpret_cast<int *>(red_val + FPB * ((T + 63) / 64));
+    [[maybe_unused]] long long *slots = reinterpret_cast<long long *>(red_idx + FPB * ((T + 63) / 64));  // [FPB][4], T < 64
+
+    const int tid_b = threadIdx.x;
+    for (int i = tid_b; i < TWN; i += T * FPB) tw_own[i] = a.tw[i];
+    __syncthreads();
+
+    int fib = FPB == 1 ? 0 : tid_b / T;  // (said outright where the workgroup is one frame: the 4096-point kernel fits its 128 registers with it)
+    const int tid = tid_b - fib * T;
+    if constexpr (T >= 64 && FPB > 1) fib = __builtin_amdgcn_readfirstlane(fib);
+    float2 *buf = bufs + (size_t)fib * FE;
+    const long long ngroups = (a.nframes + FPB - 1) / FPB;
+    const long long step = (long long)gridDim.x * FPB;
+    if ((long long)blockIdx.x >= ngroups) return;
+    auto clamped = [&](FramePos p) {
+        if (p.f >= a.nframes) {
+            p.f = a.nframes - 1;
+            p.in = a.g.last_in;
+            p.out = a.g.last_out;
+        }
+        return p;
+    };
+    typename RawPoint<IN>::type raw[R0];
+    if constexpr (T >= 64) {
+        FramePos walk = stream_pos(a.g, (long long)blockIdx.x * FPB + fib);  // (unclamped: the walk goes on from where it is)
+        FramePos cur = clamped(walk);
+        fft_fetch<N, T, IN, R0>(a, cur, tid, raw);
+        for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
+            FramePos next = cur;
+            if (g + gridDim.x < ngroups) {
+                stream_step(a.g, walk, step);
+                next = clamped(walk);
+            }
+            fft_frame<N, T, IN, OUT, R0, R1, R2, R3>(a, cur, next, tid, buf, tw_own, red_val, red_idx, fib, raw);
+            __syncthreads();
+            cur = next;
+        }
+    } else {
+        long long *slot = slots + 4 * fib;
+        {
+            const FramePos first = clamped(stream_pos(a.g, (long long)blockIdx.x * FPB + fib));
+            slot[0] = first.j;
+            slot[1] = first.in;
+            slot[2] = first.out;
+            fft_fetch<N, T, IN, R0>(a, first, tid, raw);
+        }
+        for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
+            slot[3] = slot[2];
+            const long long f = g * FPB + fib, fn = f + step;
+            const LdsFrame cur = {slot, f < a.nframes ? f : a.nframes - 1};
+            const LdsNext next = {slot, &a.g, step, g + gridDim.x < ngroups, fn >= a.nframes};
+            fft_frame<N, T, IN, OUT, R0, R1, R2, R3>(a, cur, next, tid, buf, tw_own, red_val, red_idx, fib, raw);
+            __syncthreads();
+        }
+    }
+}
+
 template <int N, int FPB, int T, int R0, int R1, int R2, int R3, bool TWG = false>
 constexpr size_t fft_lds_bytes()
 {
@@ -394,6 +502,8 @@ constexpr size_t fft_lds_bytes()
 struct Launcher {
     void (*launch)(const FftArgs &, int grid, hipStream_t) = nullptr;
     void (*launch_pix)(const FftPixArgs &, int grid, hipStream_t) = nullptr;  // out == OUT_PIX
+    void (*launch_s)(const Strided<FftArgs> &, int grid, hipStream_t) = nullptr;         // k_fft_streams, out == OUT_PSD
+    void (*launch_pix_s)(const Strided<FftPixArgs> &, int grid, hipStream_t) = nullptr;  // k_fft_streams, out == OUT_PIX
     int frames_per_block = 0;
     size_t lds_bytes = 0;
     int block = 0;
@@ -414,6 +524,13 @@ static void launch_pix_impl(const FftPixArgs &a, int grid, hipStream_t s)
     hipLaunchKernelGGL((k_fft_pix<N, T, FPB, IN, R0, R1, R2, R3>), dim3(grid), dim3(T * FPB), lds, s, a);
 }
 
+template <int N, int T, int FPB, int IN, int OUT, int R0, int R1, int R2, int R3, class ARGS>
+static void launch_streams_impl(const ARGS &a, int grid, hipStream_t s)
+{
+    constexpr size_t lds = fft_lds_bytes<N, FPB, T, R0, R1, R2, R3, false>() + (T < 64 ? sizeof(long long) * 4 * FPB : 0);
+    hipLaunchKernelGGL((k_fft_streams<N, T, FPB, IN, OUT, R0, R1, R2, R3, ARGS>), dim3(grid), dim3(T * FPB), lds, s, a);
+}
+
 template <int N, int T, int FPB, int R0, int R1, int R2, int R3, bool TWG = false>
 static Launcher make_launcher(int in, int out)
 {
@@ -431,6 +548,10 @@ static Launcher make_launcher(int in, int out)
     if constexpr (!TWG) {
         if (in == IN_I16 && out == OUT_PIX) l.launch_pix = launch_pix_impl<N, T, FPB, IN_I16, R0, R1, R2, R3>;
         if (in == IN_F32 && out == OUT_PIX) l.launch_pix = launch_pix_impl<N, T, FPB, IN_F32, R0, R1, R2, R3>;
+        if (in == IN_I16 && out == OUT_PSD) l.launch_s = launch_streams_impl<N, T, FPB, IN_I16, OUT_PSD, R0, R1, R2, R3, Strided<FftArgs>>;
+        if (in == IN_F32 && out == OUT_PSD) l.launch_s = launch_streams_impl<N, T, FPB, IN_F32, OUT_PSD, R0, R1, R2, R3, Strided<FftArgs>>;
+        if (in == IN_I16 && out == OUT_PIX) l.launch_pix_s = launch_streams_impl<N, T, FPB, IN_I16, OUT_PIX, R0, R1, R2, R3, Strided<FftPixArgs>>;
+        if (in == IN_F32 && out == OUT_PIX) l.launch_pix_s = launch_streams_impl<N, T, FPB, IN_F32, OUT_PIX, R0, R1, R2, R3, Strided<FftPixArgs>>;
     }
     return l;
 }
@@ -569,14 +690,49 @@ static int fft_run(jsdr_fft *h, const void *in_dev, int in_kind, int out_kind, l
     return fft_launch_pow2(h, a, in_kind, out_kind, s);
 }
 
-// the power-of-two kernel, PSD / spectrum (FftArgs) or pixel form (FftPixArgs): one launch geometry for both
+// frames [f0, f0 + nframes) of a strided call (StreamRows) into PSD rows: the strided instantiation of the handle's kernel
+struct StreamRows {
+    long long fps;         // frames per stream
+    long long in_stride;   // points between two streams' first frames
+    long long out_stride;  // floats between two streams' first PSD rows
+};
+static int fft_run_streams(jsdr_fft *h, const void *in_dev, int in_kind, const StreamRows &r, long long f0, long long nframes,
+                           long long out_base, int ic, int qc, float *out_dev, hipStream_t s)
+{
+    Strided<FftArgs> a;
+    a.in = in_dev;
+    a.out = out_dev;
+    a.tw = h->direct ? nullptr : (!h->rt && !h->mixed && in_kind == IN_I16) ? h->tw_i16.p : h->tw.p;
+    a.nframes = nframes;
+    a.rate = h->rate;
+    a.ic = ic;
+    a.qc = qc;
+    a.g = stream_geom(h->n, r.fps, r.in_stride, r.out_stride, f0, nframes, out_base);
+    if (h->rt) return rt_launch_streams(a, h->n, in_kind, h->num_cu, s);
+    if (h->direct) return dft_any_launch_streams(a, h->n, in_kind, h->num_cu, s);
+    if (h->mixed) {
+        if (h->mplan.split2) return mixed_launch_split2_streams(h->mplan, a, in_kind, h->num_cu, s);
+        static const int mgrid = [] { const char *e = knob("JSDR_MIXED_GRID"); return e ? atoi(e) : 16; }();  // (as fft_run)
+        const long long cap = (long long)h->num_cu * mgrid;
+        return mixed_launch_streams(h->mplan, a, in_kind, (int)(nframes < cap ? nframes : cap), s);
+    }
+    return fft_launch_pow2(h, a, in_kind, OUT_PSD, s);
+}
+
+// the power-of-two kernel, PSD / spectrum (FftArgs) or pixel form (FftPixArgs), contiguous or Strided<>: one launch geometry for all
 template <class ARGS>
 static int fft_launch_pow2(jsdr_fft *h, ARGS &a, int in_kind, int out_kind, hipStream_t s)
 {
     const long long nframes = a.nframes;
     Launcher l = pick_launcher(h->n, in_kind, out_kind);
-    constexpr bool PIX = std::is_same<ARGS, FftPixArgs>::value;
-    JSDR_REQUIRE(PIX ? l.launch_pix != nullptr : l.launch != nullptr, "fft: no kernel for n=%d in=%d out=%d", h->n, in_kind, out_kind);
+    constexpr bool PIX = std::is_base_of<FftPixArgs, ARGS>::value, STR = is_strided<ARGS>::value;
+    const auto launch = [&] {
+        if constexpr (PIX && STR) return l.launch_pix_s;
+        else if constexpr (STR) return l.launch_s;
+        else if constexpr (PIX) return l.launch_pix;
+        else return l.launch;
+    }();
+    JSDR_REQUIRE(launch != nullptr, "fft: no kernel for n=%d in=%d out=%d", h->n, in_kind, out_kind);
     long long groups = (nframes + l.frames_per_block - 1) / l.frames_per_block;
     // enough workgroups to fill every CU at the LDS-limited occupancy, grid-stride over the rest
     long long per_cu = (long long)(160 * 1024 / l.lds_bytes);
@@ -608,8 +764,8 @@ static int fft_launch_pow2(jsdr_fft *h, ARGS &a, int in_kind, int out_kind, hipS
         g_wgclk_log[a.wgclk_slot][2] = wgclk_seq++;
     }
 #endif
-    if constexpr (PIX) l.launch_pix(a, grid, s);
-    else l.launch(a, grid, s);
+    if constexpr (STR) stream_geom_step(a.g, (long long)grid * l.frames_per_block);
+    launch(a, grid, s);
     JSDR_LAUNCH_CHECK();
     return JSDR_OK;
 }
@@ -781,8 +937,10 @@ static const char *fft_waterfall_name(jsdr_fft *h)
     return h->wf_kernel.c_str();
 }
 
+// (sr: the frames are those of a strided call, nframes of them in all, and the rows of every output are packed in that order)
 static int fft_waterfall(const char *who, jsdr_fft *h, const void *in_dev, int in_kind, long long nframes, int ic, int qc,
-                         int width, uint32_t peak_rgb, uint32_t *pix_dev, float *max_dev, float *peak_dev, hipStream_t s)
+                         int width, uint32_t peak_rgb, uint32_t *pix_dev, float *max_dev, float *peak_dev, hipStream_t s,
+                         const StreamRows *sr = nullptr)
 {
     JSDR_REQUIRE(h, "%s: null handle", who);
     JSDR_REQUIRE(in_dev, "%s: null %s", who, in_kind == IN_I16 ? "raw_dev" : "iq_dev");
@@ -804,6 +962,12 @@ static int fft_waterfall(const char *who, jsdr_fft *h, const void *in_dev, int i
         a.peak = peak_dev;
         a.width = width;
         a.peak_rgb = (unsigned)peak_rgb;
+        if (sr) {
+            Strided<FftPixArgs> b;
+            static_cast<FftPixArgs &>(b) = a;
+            b.g = stream_geom(h->n, sr->fps, sr->in_stride, sr->out_stride, 0, nframes, 0);
+            return fft_launch_pow2(h, b, in_kind, OUT_PIX, s);
+        }
         return fft_launch_pow2(h, a, in_kind, OUT_PIX, s);
     }
     const long long n = h->n, rows = nframes < WF_CHUNK ? nframes : WF_CHUNK;
@@ -812,8 +976,10 @@ static int fft_waterfall(const char *who, jsdr_fft *h, const void *in_dev, int i
     const size_t in_frame = (size_t)n * (in_kind == IN_I16 ? 2 * sizeof(int16_t) : 2 * sizeof(float));
     for (long long f0 = 0; f0 < nframes; f0 += WF_CHUNK) {
         const long long nf = nframes - f0 < WF_CHUNK ? nframes - f0 : WF_CHUNK;
-        if (fft_run(h, static_cast<const unsigned char *>(in_dev) + (size_t)f0 * in_frame, in_kind, OUT_PSD, nf, ic, qc,
-                    h->wf_rows.p, s) != JSDR_OK)
+        // (a strided call's chunk holds the end of one stream and the start of the next wherever fps does not divide WF_CHUNK)
+        if ((sr ? fft_run_streams(h, in_dev, in_kind, *sr, f0, nf, -f0 * (n + 2), ic, qc, h->wf_rows.p, s)
+                : fft_run(h, static_cast<const unsigned char *>(in_dev) + (size_t)f0 * in_frame, in_kind, OUT_PSD, nf, ic, qc,
+                          h->wf_rows.p, s)) != JSDR_OK)
             return JSDR_ERR;
         if (jsdr_waterfall_lines(h->wf_rows.p, nf, (int)n, width, peak_rgb, pix_dev + f0 * width, s) != JSDR_OK) return JSDR_ERR;
         if (max_dev || peak_dev) {
@@ -881,5 +1047,95 @@ int jsdr_fft_waterfall_f32(jsdr_fft *h, const float *iq_dev, int64_t nframes, in
 }
 
 const char *jsdr_fft_waterfall_kernel(jsdr_fft *h) { return h ? fft_waterfall_name(h) : ""; }
+
+// ------------------------------------------------------------------ raw[stream][stride]: the strided forms of the four batch calls
+// JSDR_FFT_STREAMS_FORCE=1 (A/B knob, tools/ab_fft_streams.py): packed rows take the strided instantiation as well.  Read at
+// every call: the tool alternates the two forms within one process.
+static bool fft_streams_forced()
+{
+    const char *e = knob("JSDR_FFT_STREAMS_FORCE");
+    return e && atoi(e) != 0;
+}
+
+// the arguments the four share; on JSDR_OK `r` is the geometry and *packed says that the rows are one contiguous run
+static int fft_streams_args(const char *who, jsdr_fft *h, const void *in_dev, int in_kind, int nstreams, int64_t in_stride,
+                            int64_t fps, bool want_psd, const float *psd_dev, int64_t psd_stride, StreamRows &r, bool *packed)
+{
+    const char *in_name = in_kind == IN_I16 ? "raw_dev" : "iq_dev", *stride_name = in_kind == IN_I16 ? "stream_stride_i16" : "stream_stride_f32";
+    JSDR_REQUIRE(h, "%s: null handle", who);
+    JSDR_REQUIRE(in_dev, "%s: null %s", who, in_name);
+    JSDR_REQUIRE(!want_psd || psd_dev, "%s: null psd_dev", who);
+    JSDR_REQUIRE(nstreams > 0, "%s: nstreams=%d must be positive", who, nstreams);
+    JSDR_REQUIRE(fps >= 0, "%s: frames_per_stream=%lld is negative", who, (long long)fps);
+    const long long n = h->n;
+    if (nstreams > 1) {
+        JSDR_REQUIRE((in_stride & 1) == 0, "%s: %s=%lld is odd (I and Q alternate)", who, stride_name, (long long)in_stride);
+        JSDR_REQUIRE(in_stride >= fps * 2 * n, "%s: %s=%lld is below a stream's %lld frames of %lld values", who, stride_name,
+                     (long long)in_stride, (long long)fps, 2 * n);
+    }
+    JSDR_REQUIRE(!want_psd || psd_stride == 0 || psd_stride >= fps * (n + 2), "%s: psd_stream_stride_f32=%lld is below a stream's %lld rows of %lld floats",
+                 who, (long long)psd_stride, (long long)fps, n + 2);
+    r.fps = fps;
+    r.in_stride = nstreams > 1 ? in_stride / 2 : fps * n;
+    r.out_stride = want_psd && psd_stride != 0 ? psd_stride : fps * (n + 2);
+    *packed = nstreams == 1 || (r.in_stride == fps * n && r.out_stride == fps * (n + 2));
+    return JSDR_OK;
+}
+
+static int fft_batch_streams(const char *who, jsdr_fft *h, const void *in_dev, int in_kind, int nstreams, int64_t in_stride,
+                             int64_t fps, int ic, int qc, float *psd_dev, int64_t psd_stride, hipStream_t s)
+{
+    StreamRows r;
+    bool packed = false;
+    if (fft_streams_args(who, h, in_dev, in_kind, nstreams, in_stride, fps, true, psd_dev, psd_stride, r, &packed) != JSDR_OK) return JSDR_ERR;
+    if (fps == 0) return JSDR_OK;
+    // rows that are in fact packed are the contiguous call's: the same launch, the same kernel
+    if (packed && !fft_streams_forced()) return fft_run(h, in_dev, in_kind, OUT_PSD, nstreams * fps, ic, qc, psd_dev, s);
+    return fft_run_streams(h, in_dev, in_kind, r, 0, nstreams * fps, 0, ic, qc, psd_dev, s);
+}
+
+static int fft_waterfall_streams(const char *who, jsdr_fft *h, const void *in_dev, int in_kind, int nstreams, int64_t in_stride,
+                                 int64_t fps, int ic, int qc, int width, uint32_t peak_rgb, uint32_t *pix_dev, float *max_dev,
+                                 float *peak_dev, hipStream_t s)
+{
+    StreamRows r;
+    bool packed = false;
+    if (fft_streams_args(who, h, in_dev, in_kind, nstreams, in_stride, fps, false, nullptr, 0, r, &packed) != JSDR_OK) return JSDR_ERR;
+    JSDR_REQUIRE(pix_dev, "%s: null pix_dev", who);
+    JSDR_REQUIRE(width > 0, "%s: width=%d must be positive", who, width);
+    if (fps == 0) return JSDR_OK;
+    return fft_waterfall(who, h, in_dev, in_kind, nstreams * fps, ic, qc, width, peak_rgb, pix_dev, max_dev, peak_dev, s,
+                         packed && !fft_streams_forced() ? nullptr : &r);
+}
+
+int jsdr_fft_batch_streams_i16(jsdr_fft *h, const int16_t *raw_dev, int nstreams, int64_t stream_stride_i16, int64_t frames_per_stream,
+                               int ic, int qc, float *psd_dev, int64_t psd_stream_stride_f32, void *stream)
+{
+    return fft_batch_streams("jsdr_fft_batch_streams_i16", h, raw_dev, IN_I16, nstreams, stream_stride_i16, frames_per_stream, ic, qc,
+                             psd_dev, psd_stream_stride_f32, as_stream(stream));
+}
+
+int jsdr_fft_batch_streams_f32(jsdr_fft *h, const float *iq_dev, int nstreams, int64_t stream_stride_f32, int64_t frames_per_stream,
+                               float *psd_dev, int64_t psd_stream_stride_f32, void *stream)
+{
+    return fft_batch_streams("jsdr_fft_batch_streams_f32", h, iq_dev, IN_F32, nstreams, stream_stride_f32, frames_per_stream, 0, 0,
+                             psd_dev, psd_stream_stride_f32, as_stream(stream));
+}
+
+int jsdr_fft_waterfall_streams_i16(jsdr_fft *h, const int16_t *raw_dev, int nstreams, int64_t stream_stride_i16,
+                                   int64_t frames_per_stream, int ic, int qc, int width, uint32_t peak_rgb, uint32_t *pix_dev,
+                                   float *max_dev, float *peak_dev, void *stream)
+{
+    return fft_waterfall_streams("jsdr_fft_waterfall_streams_i16", h, raw_dev, IN_I16, nstreams, stream_stride_i16, frames_per_stream,
+                                 ic, qc, width, peak_rgb, pix_dev, max_dev, peak_dev, as_stream(stream));
+}
+
+int jsdr_fft_waterfall_streams_f32(jsdr_fft *h, const float *iq_dev, int nstreams, int64_t stream_stride_f32,
+                                   int64_t frames_per_stream, int width, uint32_t peak_rgb, uint32_t *pix_dev, float *max_dev,
+                                   float *peak_dev, void *stream)
+{
+    return fft_waterfall_streams("jsdr_fft_waterfall_streams_f32", h, iq_dev, IN_F32, nstreams, stream_stride_f32, frames_per_stream,
+                                 0, 0, width, peak_rgb, pix_dev, max_dev, peak_dev, as_stream(stream));
+}
 
 }  // extern "C"

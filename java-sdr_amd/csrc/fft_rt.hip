@@ -165,8 +165,8 @@ constexpr int rt_slot(int q)
 // One Stockham pass of radix R: butterfly b (k = b mod P) takes in[b + j nb], j < R, multiplies input j >= 1 by T[k j], and
 // stores output q at (b - k) R + k + q P.  FIRST: inputs from the frame in global memory (converted); LAST: outputs to the
 // PSD (or the spectrum) in global memory.
-template <int R, int IN, int OUT, bool FIRST, bool LAST>
-__device__ __forceinline__ void rt_pass(const FftArgs &a, long long frame, int n, int P, const float2 *__restrict__ tw, const float2 *src,
+template <int R, int IN, int OUT, bool FIRST, bool LAST, class FR>
+__device__ __forceinline__ void rt_pass(const FftArgs &a, FR frame, int n, int P, const float2 *__restrict__ tw, const float2 *src,
                                         float2 *dst, int tid, Best &best)
 {
     const int nb = n / R;
@@ -174,7 +174,7 @@ __device__ __forceinline__ void rt_pass(const FftArgs &a, long long frame, int n
         float2 v[R];
         if constexpr (FIRST) {
             if constexpr (IN == IN_I16) {
-                const int *raw = reinterpret_cast<const int *>(a.in) + frame * n;
+                const int *raw = reinterpret_cast<const int *>(a.in) + frame_in(frame, n);
                 int w[R];
 #pragma unroll
                 for (int j = 0; j < R; j++) w[j] = raw[b + j * nb];
@@ -185,7 +185,7 @@ __device__ __forceinline__ void rt_pass(const FftArgs &a, long long frame, int n
                     v[j] = make_float2(i16_to_float_java(si), i16_to_float_java(sq));
                 }
             } else {
-                const float2 *in = reinterpret_cast<const float2 *>(a.in) + frame * n;
+                const float2 *in = reinterpret_cast<const float2 *>(a.in) + frame_in(frame, n);
 #pragma unroll
                 for (int j = 0; j < R; j++) v[j] = in[b + j * nb];
             }
@@ -204,12 +204,12 @@ __device__ __forceinline__ void rt_pass(const FftArgs &a, long long frame, int n
 #pragma unroll
             for (int q = 0; q < R; q++) dst[j0 + q * P] = v[rt_slot<R>(q)];
         } else if constexpr (OUT == OUT_SPEC) {
-            float2 *o = reinterpret_cast<float2 *>(a.out) + frame * n;
+            float2 *o = reinterpret_cast<float2 *>(a.out) + frame_out(frame, n);
 #pragma unroll
             for (int q = 0; q < R; q++) o[j0 + q * P] = v[rt_slot<R>(q)];
         } else {
             const float cf = (2.0f / (float)n) * (2.0f / (float)n);  // fft.java:203: cf = 2f / N, squared
-            float *o = a.out + frame * (n + 2);
+            float *o = a.out + frame_out(frame, n + 2);
 #pragma unroll
             for (int q = 0; q < R; q++) {
                 const float2 x = v[rt_slot<R>(q)];
@@ -254,33 +254,33 @@ __device__ __forceinline__ void rt_pass_generic(int n, int P, int r, const float
 }
 
 // the frame into an LDS image, converted (a plan whose FIRST radix has no butterfly of its own: 143 = 11 . 13)
-template <int IN>
-__device__ __forceinline__ void rt_load(const FftArgs &a, long long frame, int n, float2 *dst, int tid)
+template <int IN, class FR>
+__device__ __forceinline__ void rt_load(const FftArgs &a, FR frame, int n, float2 *dst, int tid)
 {
     for (int t = tid; t < n; t += RT_T) {
         if constexpr (IN == IN_I16) {
-            const int w = (reinterpret_cast<const int *>(a.in) + frame * n)[t];
+            const int w = (reinterpret_cast<const int *>(a.in) + frame_in(frame, n))[t];
             const int si = java_short_add((int)(short)(w & 0xffff), a.ic);
             const int sq = java_short_add(w >> 16, a.qc);
             dst[t] = make_float2(i16_to_float_java(si), i16_to_float_java(sq));
         } else {
-            dst[t] = (reinterpret_cast<const float2 *>(a.in) + frame * n)[t];
+            dst[t] = (reinterpret_cast<const float2 *>(a.in) + frame_in(frame, n))[t];
         }
     }
 }
 
 // PSD / first maximum (or the spectrum) from an LDS image (a plan whose LAST radix has no butterfly of its own)
-template <int OUT>
-__device__ __forceinline__ void rt_epilogue(const FftArgs &a, long long frame, int n, const float2 *src, int tid, Best &best)
+template <int OUT, class FR>
+__device__ __forceinline__ void rt_epilogue(const FftArgs &a, FR frame, int n, const float2 *src, int tid, Best &best)
 {
     const float cf = (2.0f / (float)n) * (2.0f / (float)n);
     for (int bin = tid; bin < n; bin += RT_T) {
         const float2 x = src[bin];
         if constexpr (OUT == OUT_SPEC) {
-            (reinterpret_cast<float2 *>(a.out) + frame * n)[bin] = x;
+            (reinterpret_cast<float2 *>(a.out) + frame_out(frame, n))[bin] = x;
         } else {
             const float db = 3.0102999566398120f * __log2f((x.x * x.x + x.y * x.y) * cf);  // fft.java:207
-            (a.out + frame * (n + 2))[bin] = db;
+            (a.out + frame_out(frame, n + 2))[bin] = db;
             if (db > best.v || (db == best.v && bin < best.k)) {
                 best.v = db;
                 best.k = bin;
@@ -291,8 +291,8 @@ __device__ __forceinline__ void rt_epilogue(const FftArgs &a, long long frame, i
 
 // FULL: the composite radices as well.  They are a kernel of their own: a switch that holds a 25-point butterfly gives EVERY
 // plan that kernel's register count (3200 = 16.8.5.5: 5.3 ms per 2^30 samples in the small kernel, 6.8 in the full one).
-template <int IN, int OUT, bool FIRST, bool LAST, bool FULL>
-__device__ __forceinline__ void rt_pass_any(int r, const FftArgs &a, long long frame, int n, int P, const float2 *tw, const float2 *src,
+template <int IN, int OUT, bool FIRST, bool LAST, bool FULL, class FR>
+__device__ __forceinline__ void rt_pass_any(int r, const FftArgs &a, FR frame, int n, int P, const float2 *tw, const float2 *src,
                                             float2 *dst, int tid, Best &best)
 {
     switch (r) {
@@ -319,8 +319,10 @@ __device__ __forceinline__ void rt_pass_any(int r, const FftArgs &a, long long f
     }
 }
 
-template <int IN, int OUT, bool FULL>
-__global__ __launch_bounds__(RT_T) void k_fft_rt(FftArgs a, RtPlan p)
+// ARGS = Strided<FftArgs>: the strided instantiation (jsdr_fft_*_streams_*) -- the frame is a FramePos, walked by the frame loop
+// (fft_common.h).  The default is the contiguous kernel, whose frame is its number.
+template <int IN, int OUT, bool FULL, class ARGS = FftArgs>
+__global__ __launch_bounds__(RT_T) void k_fft_rt(ARGS a, RtPlan p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int n = p.n;
@@ -329,7 +331,7 @@ __global__ __launch_bounds__(RT_T) void k_fft_rt(FftArgs a, RtPlan p)
     float *red_val = reinterpret_cast<float *>(img1 + n);
     int *red_idx = reinterpret_cast<int *>(red_val + RT_T / 64);
     const int tid = threadIdx.x;
-    for (long long frame = blockIdx.x; frame < a.nframes; frame += gridDim.x) {
+    for (auto frame = frame_first(a, blockIdx.x); frame_more(a, frame); frame_next(a, frame, gridDim.x)) {
         Best best;
         best.v = -3.402823466e+38f;
         best.k = 0x7fffffff;
@@ -394,7 +396,7 @@ __global__ __launch_bounds__(RT_T) void k_fft_rt(FftArgs a, RtPlan p)
                 const int datlen = 2 * n;
                 if (pp >= datlen / 2) pp -= datlen;
                 const int hz = (int)((unsigned)pp * (unsigned)a.rate) / datlen;
-                float *o = a.out + frame * (n + 2);
+                float *o = a.out + frame_out(frame, n + 2);
                 o[n] = (float)hz;
                 o[n + 1] = m;
             }
@@ -500,9 +502,16 @@ void rt_twiddles(int n, std::vector<float2> &w)
     }
 }
 
-int rt_launch(const FftArgs &a, int n, int in_kind, int out_kind, int num_cu, hipStream_t st)
-{
+// what a launch of nframes frames takes, the contiguous and the strided kernel alike
+struct RtLaunch {
     RtPlan p;
+    size_t lds = 0;
+    unsigned grid = 0;
+    bool full = false;  // the plan holds a composite radix: the kernel with those butterflies
+};
+static int rt_launch_plan(long long nframes, int n, int num_cu, RtLaunch &l)
+{
+    RtPlan &p = l.p;
     size_t cnt = 0;
     p.n = n;
     if (!rt_plan(n, &p.np, p.rad, p.tw_off, &cnt, p.wr_off)) {
@@ -510,18 +519,29 @@ int rt_launch(const FftArgs &a, int n, int in_kind, int out_kind, int num_cu, hi
         return JSDR_ERR;
     }
     for (int i = p.np; i < RT_MAXPASS; i++) p.rad[i] = 1, p.tw_off[i] = 0, p.wr_off[i] = 0;
-    const size_t lds = sizeof(float2) * 2 * (size_t)n + (sizeof(float) + sizeof(int)) * (RT_T / 64) + 16;
-    const long long per_cu = (long long)(160 * 1024 / lds) < 8 ? (long long)(160 * 1024 / lds) : 8;
+    l.lds = sizeof(float2) * 2 * (size_t)n + (sizeof(float) + sizeof(int)) * (RT_T / 64) + 16;
+    const long long per_cu = (long long)(160 * 1024 / l.lds) < 8 ? (long long)(160 * 1024 / l.lds) : 8;
     const long long cap = (long long)num_cu * (per_cu < 1 ? 1 : per_cu) * 4;
-    const unsigned grid = (unsigned)(a.nframes < cap ? a.nframes : cap);
+    l.grid = (unsigned)(nframes < cap ? nframes : cap);
+    l.full = false;
+    for (int i = 0; i < p.np; i++) l.full |= rt_special(p.rad[i]) && (p.rad[i] == 6 || p.rad[i] > 8) && p.rad[i] != 16;
+    return JSDR_OK;
+}
+
+int rt_launch(const FftArgs &a, int n, int in_kind, int out_kind, int num_cu, hipStream_t st)
+{
+    RtLaunch l;
+    if (rt_launch_plan(a.nframes, n, num_cu, l) != JSDR_OK) return JSDR_ERR;
+    const RtPlan &p = l.p;
+    const size_t lds = l.lds;
+    const unsigned grid = l.grid;
+    const bool full = l.full;
     auto go = [&](auto kern) -> int {
         JSDR_LDS_ATTR(kern, lds);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(RT_T), lds, st, a, p);
         JSDR_LAUNCH_CHECK();
         return JSDR_OK;
     };
-    bool full = false;
-    for (int i = 0; i < p.np; i++) full |= rt_special(p.rad[i]) && (p.rad[i] == 6 || p.rad[i] > 8) && p.rad[i] != 16;
     if (full) {
         if (in_kind == IN_I16 && out_kind == OUT_PSD) return go(k_fft_rt<IN_I16, OUT_PSD, true>);
         if (in_kind == IN_F32 && out_kind == OUT_PSD) return go(k_fft_rt<IN_F32, OUT_PSD, true>);
@@ -535,6 +555,23 @@ int rt_launch(const FftArgs &a, int n, int in_kind, int out_kind, int num_cu, hi
     }
     set_error("fft: no run-time-plan kernel for in=%d out=%d", in_kind, out_kind);
     return JSDR_ERR;
+}
+
+int rt_launch_streams(const Strided<FftArgs> &a, int n, int in_kind, int num_cu, hipStream_t st)
+{
+    RtLaunch l;
+    if (rt_launch_plan(a.nframes, n, num_cu, l) != JSDR_OK) return JSDR_ERR;
+    Strided<FftArgs> b = a;
+    stream_geom_step(b.g, l.grid);
+    auto go = [&](auto kern) -> int {
+        JSDR_LDS_ATTR(kern, l.lds);
+        hipLaunchKernelGGL(kern, dim3(l.grid), dim3(RT_T), l.lds, st, b, l.p);
+        JSDR_LAUNCH_CHECK();
+        return JSDR_OK;
+    };
+    using S = Strided<FftArgs>;
+    if (l.full) return in_kind == IN_I16 ? go(k_fft_rt<IN_I16, OUT_PSD, true, S>) : go(k_fft_rt<IN_F32, OUT_PSD, true, S>);
+    return in_kind == IN_I16 ? go(k_fft_rt<IN_I16, OUT_PSD, false, S>) : go(k_fft_rt<IN_F32, OUT_PSD, false, S>);
 }
 
 bool rt_supported(int n)

@@ -152,18 +152,11 @@ static void run_batch(Rank *r, const Job &j)
         return;
     }
     if (g->with_psd && j.psd) {
-        // raw is [S][stride]: only when the streams lie back to back (stride == 2 nsamples int16) are their frames ONE run;
-        // otherwise (the chunked calls of a longer buffer, the JNI's 2 max_batch stride) the transform goes stream by stream
+        // raw is [S][stride]: one launch whatever the stride (the chunked calls of a longer buffer, the JNI's 2 max_batch stride);
+        // streams that lie back to back (stride == 2 nsamples int16) are the contiguous call's one run of frames
         const int64_t nf = j.nsamples / g->frame;
-        if (j.stride == 2 * j.nsamples) {
-            if (jsdr_fft_batch_i16(r->fft, j.raw, (int64_t)S * nf, j.ic, j.qc, j.psd, r->psd) != JSDR_OK) failed = true;
-        } else {
-            for (int s = 0; s < S && !failed; s++)
-                if (jsdr_fft_batch_i16(r->fft, j.raw + (int64_t)s * j.stride, nf, j.ic, j.qc,
-                                       j.psd + (int64_t)s * nf * (g->frame + 2), r->psd) != JSDR_OK)
-                    failed = true;
-        }
-        if (failed) rank_fail(r, "jsdr_fft_batch_i16");
+        if (jsdr_fft_batch_streams_i16(r->fft, j.raw, S, j.stride, nf, j.ic, j.qc, j.psd, 0, r->psd) != JSDR_OK) failed = true;
+        if (failed) rank_fail(r, "jsdr_fft_batch_streams_i16");
     }
     if (!failed && jsdr_bpsk_batch_i16(r->dem, j.raw, j.stride, j.nsamples, j.ic, j.qc, r->main) != JSDR_OK) {
         rank_fail(r, "jsdr_bpsk_batch_i16");
