@@ -169,6 +169,47 @@ int jsdr_phase_receive_f32(jsdr_phase *h, const float *iq_host);   /* 2n floats 
 int jsdr_phase_get_max(jsdr_phase *h, float *max_out);
 int jsdr_phase_get_columns(jsdr_phase *h, int bx, int32_t *pix_host, float *avgi_host, float *avgq_host, int cap,
                            int *ncol);
+/* The phase scope over batches: everything phase.paintComponent computes from a frame (phase.java:75-116), for every frame of
+ * raw[stream][stride], in one launch that reads each frame once.  For a frame dpy[2n] and a strip bx pixels wide:
+ *   max_dev[r]          = max|x| as :75-80 takes it: from -1, `max < a` never admits a NaN (an all-NaN frame gives -1);
+ *   the column schedule = step = (float)(bx*2)/(float)(2n); `pos += step` in float; a column closes at the sample where
+ *                         (int)pos > lpix (:81, 84, 93-99, 110-114).  It depends on (n, bx) alone -- jsdr_phase_layout states it
+ *                         on the host: pix (the closing (int)pos), first sample and sample count of every closed column.  It is the
+ *                         float recurrence, not floor((s+1)*bx/n): (600, 1) closes no column.  Samples behind the last closed
+ *                         column belong to none;
+ *   avg_dev[r][c]       = {avgi, avgq}: float sums in sample order divided by (float)count -- jsdr_phase_columns' values;
+ *   pts_dev[r][c]       = {(int)(avgi*hiq), (int)(avgq*hiq), (int)(dpy[2e]*hph), (int)(dpy[2e+1]*hph)}, e the column's closing
+ *                         sample, hiq = (float)quarter_height/max, hph = (float)half_size/max (:85-86, 102, 107, 109) with
+ *                         quarter_height = getHeight()/4 and half_size = size/2; (int) is Java's cast (truncates, saturates,
+ *                         NaN -> 0).  The pixel offsets around these values stay with the caller; a column's lsti / lstq is the
+ *                         entry before it, 0 in front of the first.
+ * int16 samples are taken as jsdr_convert_i16 takes them (wrapping s += (short)ic, then (float)s/32767f).  Bit-exact throughout.
+ * Geometry: n is the handle's; rows = nstreams * frames_per_stream; frame j of stream s starts at element s * stream_stride +
+ * j * 2n of the input; the outputs are packed, row s * frames_per_stream + j, ncol entries a row (ncol from jsdr_phase_layout).
+ * bx == 0, or any (n, bx) that closes no column: only max_dev is written (the batched int16 maxabs).  avg_dev and pts_dev may each
+ * be NULL.  The input starts on an IQ pair (4 / 8 bytes); max_dev, avg_dev and pts_dev on a row entry (4 / 8 / 16 bytes).
+ * Frames up to 8192 samples run "k_phase_scope" (the converted frame in LDS), larger ones "k_phase_scope_g" (the columns read the
+ * samples again, from cache); jsdr_phase_scope_kernel names what the last call launched.
+ * Asynchronous on `stream`.  The first scope call on a handle allocates the schedule table (n columns, counted by
+ * jsdr_live_resources, gone with jsdr_phase_destroy; jsdr_phase_create allocates nothing for it); no later call allocates or
+ * waits for the device, a change of bx included: the table is rebuilt by a one-thread kernel on `stream`, behind the previous
+ * call's readers.  Scope calls on one handle share that table, so they belong on one stream at a time.
+ * JSDR_ERR before any device work, the message naming the argument: a null handle, input or max_dev; nstreams <= 0;
+ * frames_per_stream < 0; rows >= 2^31; bx < 0; with nstreams > 1 a stride that is odd or below frames_per_stream * 2n; a
+ * misaligned pointer.  frames_per_stream == 0 is JSDR_OK and launches nothing.
+ * (Not covered: the JNI shim and the Java classes, jsdr_harness, jsdr_group_*, strided outputs.) */
+/* host only, no device: the schedule of (n, bx).  pix / first / count may each be NULL; *ncol is always set */
+int jsdr_phase_layout(int n, int bx, int32_t *pix_host, int32_t *first_host, int32_t *count_host, int cap, int *ncol);
+int jsdr_phase_scope_i16(jsdr_phase *h, const int16_t *raw_dev, int nstreams, int64_t stream_stride_i16,
+                         int64_t frames_per_stream, int ic, int qc, int bx, int half_size, int quarter_height,
+                         float   *max_dev   /* [rows], required                                              */,
+                         float   *avg_dev   /* [rows][ncol][2] = {avgi, avgq}, may be NULL                   */,
+                         int32_t *pts_dev   /* [rows][ncol][4] = {line_i, line_q, dot_i, dot_q}, may be NULL */,
+                         void *stream);
+int jsdr_phase_scope_f32(jsdr_phase *h, const float *iq_dev, int nstreams, int64_t stream_stride_f32,
+                         int64_t frames_per_stream, int bx, int half_size, int quarter_height,
+                         float *max_dev, float *avg_dev, int32_t *pts_dev, void *stream);
+const char *jsdr_phase_scope_kernel(jsdr_phase *h);   /* what the last scope call launched */
 
 /* ------------------------------------------------------------------ fir.java
  * weights (fir.java:169-195) is setup arithmetic (host); filter (:198-211) runs on the GPU over a

@@ -46,12 +46,13 @@ def lib():
         _lib.jsdr_bpsk_profile_name.restype = C.c_char_p
         _lib.jsdr_demod_profile_name.restype = C.c_char_p
         for fn in ("jsdr_bpsk_front_kernel", "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel",
-                   "jsdr_fft_waterfall_kernel"):
+                   "jsdr_fft_waterfall_kernel", "jsdr_phase_scope_kernel"):
             getattr(_lib, fn).restype = C.c_char_p
             getattr(_lib, fn).argtypes = [C.c_void_p]
         for name in EXPORTED_SYMBOLS:
             if name not in ("jsdr_last_error", "jsdr_bpsk_profile_name", "jsdr_demod_profile_name", "jsdr_bpsk_front_kernel",
-                            "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel", "jsdr_fft_waterfall_kernel"):
+                            "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel", "jsdr_fft_waterfall_kernel",
+                            "jsdr_phase_scope_kernel"):
                 getattr(_lib, name).restype = C.c_int
     return _lib
 
@@ -322,6 +323,17 @@ def phase_columns(buf, bx):
     return pix[:k].copy(), ai[:k].copy(), aq[:k].copy()
 
 
+def phase_layout(n, bx):
+    """the painter's column schedule of (n, bx), host only: (pix, first sample, sample count) of every closed column"""
+    ncol = C.c_int()
+    _check(lib().jsdr_phase_layout(int(n), int(bx), None, None, None, 0, C.byref(ncol)), "jsdr_phase_layout")
+    k = ncol.value
+    pix, first, count = (np.empty(k, np.int32) for _ in range(3))
+    if k:
+        _check(lib().jsdr_phase_layout(int(n), int(bx), _addr(pix), _addr(first), _addr(count), k, C.byref(ncol)), "jsdr_phase_layout")
+    return pix, first, count
+
+
 class Phase:
     """phase.java as a handle (the IAudioHandler drop-in): receive() keeps the frame on the device and takes max|x|
     (phase.java:75-80,123-128); columns(bx) are the painter's per-pixel-column means (:93-116)"""
@@ -351,6 +363,25 @@ class Phase:
                "jsdr_phase_get_columns")
         k = ncol.value
         return pix[:k].copy(), ai[:k].copy(), aq[:k].copy()
+
+    def scope_i16(self, raw_dev, nstreams, stream_stride_i16, frames_per_stream, ic, qc, bx, half_size, quarter_height, max_dev,
+                  avg_dev=None, pts_dev=None, stream=None):
+        """phase.paintComponent's arithmetic for every frame of raw[stream][stride] in one launch: max_dev float [rows], avg_dev
+        float [rows][ncol][2] = (avgi, avgq), pts_dev int32 [rows][ncol][4] = (line_i, line_q, dot_i, dot_q), rows = nstreams *
+        frames_per_stream packed, ncol = len(phase_layout(n, bx)[0]).  bx == 0 writes max_dev alone."""
+        _check(lib().jsdr_phase_scope_i16(self.h, _addr(raw_dev), int(nstreams), C.c_int64(stream_stride_i16),
+                                          C.c_int64(frames_per_stream), int(ic), int(qc), int(bx), int(half_size), int(quarter_height),
+                                          _addr(max_dev), _addr(avg_dev), _addr(pts_dev), C.c_void_p(stream)), "jsdr_phase_scope_i16")
+
+    def scope_f32(self, iq_dev, nstreams, stream_stride_f32, frames_per_stream, bx, half_size, quarter_height, max_dev, avg_dev=None,
+                  pts_dev=None, stream=None):
+        _check(lib().jsdr_phase_scope_f32(self.h, _addr(iq_dev), int(nstreams), C.c_int64(stream_stride_f32),
+                                          C.c_int64(frames_per_stream), int(bx), int(half_size), int(quarter_height), _addr(max_dev),
+                                          _addr(avg_dev), _addr(pts_dev), C.c_void_p(stream)), "jsdr_phase_scope_f32")
+
+    def scope_kernel(self):
+        """what the last scope_* call launched: "k_phase_scope" (the frame's image in LDS) or "k_phase_scope_g" """
+        return lib().jsdr_phase_scope_kernel(self.h).decode()
 
     def __del__(self):
         try:

@@ -34,6 +34,8 @@ SOURCES = {
     "fft_any.hip": ["-ffp-contract=off"],
     "fft_rt.hip": [],
     "fir_phase.hip": ["-ffp-contract=off"],
+    # (the batched phase scope: the schedule's float recurrence, the column sums, quotients and products round one by one)
+    "phase_scope.hip": ["-ffp-contract=off"],
     "fir_batch.hip": ["-ffp-contract=off"],
     "fec.hip": [],
     "synth.hip": [],

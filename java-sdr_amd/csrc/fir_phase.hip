@@ -2,6 +2,7 @@
 // Compiled with -ffp-contract=off: fir.filter's double accumulation must round like Java
 // (separate multiply and add, fir.java:205).
 #include "common.h"
+#include "phase_handle.h"
 #include <math.h>
 #include <vector>
 
@@ -336,13 +337,7 @@ int jsdr_phase_columns(const float *iq_dev, int n, int bx, int32_t *pix_host, fl
 // ---- phase.java as a handle (the IAudioHandler drop-in: one frame in per receive(), the two reductions of
 // paintComponent out): phase.java:123-128 copies the frame -- here to the device, where max|x| (:75-80) is taken at
 // once; the column means (:93-116) depend on the panel width and are computed when the painter asks.
-struct jsdr_phase {
-    int n = 0;
-    DevBuf<float> dpy;   // [2n] the frame
-    DevBuf<float> dmax;  // [1]
-    float max = -1.0f;   // phase.java:75: `float max = -1` before the first frame
-    bool have = false;
-};
+// (struct jsdr_phase: phase_handle.h -- the batched scope of phase_scope.hip keeps its schedule table in the same handle)
 
 int jsdr_phase_create(jsdr_phase **out, int n)
 {
