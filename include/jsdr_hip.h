@@ -782,6 +782,58 @@ int jsdr_demod_profile_enable(jsdr_demod *h, int on);
 int jsdr_demod_profile_count(void);
 const char *jsdr_demod_profile_name(int kernel);
 int jsdr_demod_profile_read(jsdr_demod *h, double *ms_total, int *launches);
+/* The demod scope over batches: what demod.paintComponent (demod.java:509-558) draws from a frame, for every frame of a batch
+ * call.  A scope call IS the batch call plus the painter: it runs jsdr_demod_batch_i16 / _f32 with the same arguments -- the
+ * same launches, the same audio, frame_stats, jsdr_demod_state and carried state, bit for bit -- and then, on the same stream,
+ * the scope passes over the frames of the call.  After receive() of a frame of n samples (:398-483) the painter sees
+ *   sam[2k]     the final float of sample k, (AM ? d - avg : d) * (doagc ? 1.0f / max : 1) (:472), before the cast to short;
+ *   sam[2k + 1] the mixed Q of sample k, behind filter() and the NCO (0 in MODE_OFF, :443);
+ *   dbg[]       the frame's mixed (I, Q) pairs in order (:436-437), in every mode, MODE_OFF included.
+ * For a panel W = width pixels wide and H = height pixels high:
+ *   trace_dev[row][W]  the magenta polyline (:519-531): entry 0 is H/4 (the start, `ly`); entry x + 1 is y of column x < W - 1,
+ *                      y = H/4 - (int)(getAbsMax(sam, 2i, (int)scale, 2) * (float)(H/4)), scale = (float)(n / W) (an int
+ *                      division), i = (int)((float)x * scale).  getAbsMax as written (:569-578, `c = |r|` outside the if, the
+ *                      walk from o + 1 in steps of 2): r = sam[2i], then the Qs of samples i, i + 1, .. while 2k + 1 <
+ *                      (int)scale, each taken when |Q| > |r| (strict; a NaN never wins, and nothing beats a NaN r);
+ *   spec_dev[row][W]   the green polyline (:534-555) before the caller's column arithmetic (m - 1 + W/2) % W: entry 0 is
+ *                      H/2 + (int)(psd[0] * h), entry m is H/2 + (int)(getMax(psd, i, (int)pi) * h) with pi = n / (float)W,
+ *                      i = (int)(pi * (float)m), h = (H/2) / -100.0f, getMax (:560-567) from psd[i] with strict >;
+ *                      psd is fft.java's formula over dbg, 10f * (float)log10((re^2 + im^2) * (2f/n)^2) -- defined by
+ *                      composition, bit for bit: the row jsdr_fft_batch_f32 of a jsdr_fft of n samples writes for the dbg row;
+ *   dbg_dev[row][2n]   the dbg row itself.
+ * (int) is Java's cast (truncates, saturates, NaN -> 0); the subtraction and the additions wrap as Java's ints do.  row =
+ * s * frames + f for frame f of stream s, rows packed; each of the three may be NULL, and with all three NULL the call is the
+ * batch call and launches nothing more.  dbg_dev starts on 16 bytes, trace_dev and spec_dev on 4.
+ * jsdr_demod_scope_layout (host only, no device) states the two column schedules of (n, width) in the reference's float
+ * arithmetic, `width` entries each: trace_first[x] = i and trace_count[x] = (int)scale for x < W - 1 (the last entry is (0, 0));
+ * spec_first[m] = i and spec_count[m] = (int)pi for m >= 1 (entry 0 is (0, 0)).  Any of the four may be NULL; cap is the room
+ * of each.  JSDR_ERR for n < 1, width outside 1 .. 32768, cap < width, and for a pair at which the reference would index
+ * outside sam[] or psd[] (none is known for n up to 20000 and width up to 2n); the scope calls refuse what it refuses.
+ * Passes, a chunk of frames at a time: "k_demod_scope_front" (one workgroup a tile: the mixed IQ and the final floats
+ * again, from the caller's input, the filter history and FM state of before the call, the call's carrier table and its
+ * (max, avg) rows), "k_demod_trace", and for the spectrum the handle's own jsdr_fft (its kernel as jsdr_fft_kernel names it)
+ * and "k_demod_spec"; jsdr_demod_scope_kernel joins what the last scope call launched with '+' ("" before the first and after
+ * a call with no output).  The rows between the passes belong to the handle: allocated at the first scope call or when a call
+ * needs more, counted by jsdr_live_resources, gone with jsdr_demod_destroy, and bounded: a pass takes at most
+ * 64 MiB / (16 n + 8) frames (one frame at least), which jsdr_demod_scope_chunk lowers (0: the default).  The schedule table
+ * lives on the device and is rebuilt by a kernel on `stream` when width changes; no call after the first with its outputs
+ * and size waits for the device.  A handle that makes no scope call allocates and launches what it did before.  Scope
+ * calls share those rows, so they belong on one stream at a time, the stream of the handle's batch calls.
+ * JSDR_ERR before any device work, handle and state untouched, the message naming the argument: a null handle, input or
+ * audio_dev; nsamples not whole frames or above max_batch_samples; a stride that is odd or below 2 * nsamples; width outside
+ * 1 .. 32768; height < 0; spec_dev with a frame size jsdr_fft_create refuses (outside 2 .. 20000); a misaligned output; a
+ * channel handle (jsdr_demod_create_channels): its channels have no scope yet.
+ * (Not covered: channel handles, the host receive_f32 form, the JNI shim and the Java classes.) */
+int jsdr_demod_scope_layout(int n, int width, int32_t *trace_first, int32_t *trace_count,
+                            int32_t *spec_first, int32_t *spec_count, int cap);
+int jsdr_demod_scope_i16(jsdr_demod *h, const int16_t *raw_dev, int64_t stream_stride_i16, int64_t nsamples, int ic, int qc,
+                         int16_t *audio_dev, int64_t audio_stride_i16, int width, int height,
+                         int32_t *trace_dev, int32_t *spec_dev, float *dbg_dev, void *stream);
+int jsdr_demod_scope_f32(jsdr_demod *h, const float *iq_dev, int64_t stream_stride_f32, int64_t nsamples,
+                         int16_t *audio_dev, int64_t audio_stride_i16, int width, int height,
+                         int32_t *trace_dev, int32_t *spec_dev, float *dbg_dev, void *stream);
+int jsdr_demod_scope_chunk(jsdr_demod *h, int frames_per_pass);   /* 0: the default */
+const char *jsdr_demod_scope_kernel(jsdr_demod *h);               /* what the last scope call launched */
 
 /* ------------------------------------------------------------------ formats either side of the path
  * waterfall.paintLine / getMax (waterfall.java:87-109): one pixel row per PSD frame as fft.receive publishes it

@@ -46,13 +46,13 @@ def lib():
         _lib.jsdr_bpsk_profile_name.restype = C.c_char_p
         _lib.jsdr_demod_profile_name.restype = C.c_char_p
         for fn in ("jsdr_bpsk_front_kernel", "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel",
-                   "jsdr_fft_waterfall_kernel", "jsdr_phase_scope_kernel"):
+                   "jsdr_fft_waterfall_kernel", "jsdr_phase_scope_kernel", "jsdr_demod_scope_kernel"):
             getattr(_lib, fn).restype = C.c_char_p
             getattr(_lib, fn).argtypes = [C.c_void_p]
         for name in EXPORTED_SYMBOLS:
             if name not in ("jsdr_last_error", "jsdr_bpsk_profile_name", "jsdr_demod_profile_name", "jsdr_bpsk_front_kernel",
                             "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel", "jsdr_fft_waterfall_kernel",
-                            "jsdr_phase_scope_kernel"):
+                            "jsdr_phase_scope_kernel", "jsdr_demod_scope_kernel"):
                 getattr(_lib, name).restype = C.c_int
     return _lib
 
@@ -1052,6 +1052,15 @@ def unpack_slot(slot, info):
 
 
 # ------------------------------------------------------------------ demod.java
+def demod_scope_layout(n, width):
+    """demod.paintComponent's two column schedules of (n, width), host only: (trace_first, trace_count, spec_first, spec_count),
+    `width` entries each (jsdr_demod_scope_layout)"""
+    out = [np.zeros(max(int(width), 0), np.int32) for _ in range(4)]
+    _check(lib().jsdr_demod_scope_layout(int(n), int(width), *[_addr(a) if a.size else None for a in out], int(width)),
+           "jsdr_demod_scope_layout")
+    return tuple(out)
+
+
 class Demod:
     """demod.receive batched over streams: mode 0 OFF, 1 RAW, 2 AM, 3 NFM, 4 WFM (demod.java:39-43)"""
 
@@ -1105,6 +1114,28 @@ class Demod:
         car, phi = C.c_float(), C.c_float()
         _check(lib().jsdr_demod_state(self.h, C.byref(car), C.byref(phi)), "jsdr_demod_state")
         return np.float32(car.value), np.float32(phi.value)
+
+    def scope_i16(self, raw_dev, stride_i16, nsamples, audio_dev, audio_stride_i16, width, height, trace_dev=None, spec_dev=None,
+                  dbg_dev=None, ic=0, qc=0, stream=None):
+        """batch_i16 plus demod.paintComponent for every frame of the call (jsdr_demod_scope_i16): trace_dev / spec_dev int32
+        [S * frames][width], dbg_dev float32 [S * frames][2n], each optional, rows packed, row = stream * frames + frame"""
+        _check(lib().jsdr_demod_scope_i16(self.h, _addr(raw_dev), C.c_int64(stride_i16), C.c_int64(nsamples), int(ic), int(qc),
+                                          _addr(audio_dev), C.c_int64(audio_stride_i16), int(width), int(height), _addr(trace_dev),
+                                          _addr(spec_dev), _addr(dbg_dev), C.c_void_p(stream)), "jsdr_demod_scope_i16")
+
+    def scope_f32(self, iq_dev, stride_f32, nsamples, audio_dev, audio_stride_i16, width, height, trace_dev=None, spec_dev=None,
+                  dbg_dev=None, stream=None):
+        _check(lib().jsdr_demod_scope_f32(self.h, _addr(iq_dev), C.c_int64(stride_f32), C.c_int64(nsamples), _addr(audio_dev),
+                                          C.c_int64(audio_stride_i16), int(width), int(height), _addr(trace_dev), _addr(spec_dev),
+                                          _addr(dbg_dev), C.c_void_p(stream)), "jsdr_demod_scope_f32")
+
+    def scope_chunk(self, frames):
+        """frames of one scope pass (0: the default, what 64 MiB of rows hold)"""
+        _check(lib().jsdr_demod_scope_chunk(self.h, int(frames)), "jsdr_demod_scope_chunk")
+
+    def scope_kernel(self):
+        """what the last scope_* call launched, joined with '+': "k_demod_scope_front+k_demod_trace+k_fft+k_demod_spec" """
+        return lib().jsdr_demod_scope_kernel(self.h).decode()
 
     def profile_enable(self, on):
         _check(lib().jsdr_demod_profile_enable(self.h, int(on)), "jsdr_demod_profile_enable")

@@ -42,6 +42,8 @@ SOURCES = {
     "formats.hip": [],
     "demod.hip": ["-ffp-contract=off"],
     "demod_chan.hip": ["-ffp-contract=off"],
+    # (the demod scope: demod.hip's tile again, the column schedules' float products and the painters' casts)
+    "demod_scope.hip": ["-ffp-contract=off"],
     # (the handle: host code only, but tuPhaseInc and its sin / cos tables are doubles that must round as Java's do)
     "bpsk_handle.hip": ["-ffp-contract=off"],
     # (the host scheduler: host code only, it steps the reference's phase recurrences in doubles that must round as Java's do)

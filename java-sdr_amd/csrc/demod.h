@@ -66,4 +66,30 @@ int launch_demod_chan_state(const DemodChanArgs &a, bool f32in, float2 *hist_new
 // the AM mean subtraction / AGC / int16 output of the d rows (favg: k_demod_mean's result for the AM rows)
 int launch_demod_chan_out(const DemodChanArgs &a, int drows, const float *favg, hipStream_t st);
 
+// ---- the demod scope (jsdr_demod_scope_*, demod_scope.hip): demod.paintComponent's trace and spectrum (:509-558) per frame
+struct DemodArgs;  // demod_dev.h
+constexpr int DSCOPE_WIDTH_MAX = 32768;
+constexpr size_t DSCOPE_SCRATCH_BYTES = (size_t)64 << 20;  // the handle's rows of one pass: dbg, final floats and PSD together
+
+// the two column schedules in the reference's float arithmetic, one statement each: host (jsdr_demod_scope_layout) and device
+// (k_demod_scope_layout) round the one product alike
+__host__ __device__ inline int dscope_trace_first(int x, float scale) { return (int)((float)x * scale); }  // :527
+__host__ __device__ inline int dscope_spec_first(int m, float pi) { return (int)(pi * (float)m); }         // :550
+inline float dscope_scale(int n, int width) { return (float)(n / width); }                                  // :519
+inline float dscope_pi(int n, int width) { return (float)n / (float)width; }                                // :544
+
+// tab = int[4][width]: trace_first, trace_count, spec_first, spec_count (jsdr_demod_scope_layout's four arrays), filled on `st`
+int launch_demod_scope_layout(int n, int width, int *tab, hipStream_t st);
+// rows [row0, row0 + nrows) of the call `a` describes (row = stream * a.nfr + frame; a.hist / a.lilq / a.nco as they were
+// BEFORE the call, stats = its (max, avg) rows): the mixed IQ to dbg_rows[nrows][n], the final floats to fin_rows[nrows][n]
+// (may be null)
+int launch_demod_scope_front(const DemodArgs &a, bool f32in, const float *stats, long long row0, int nrows, float2 *dbg_rows,
+                             float *fin_rows, hipStream_t st);
+// trace_rows[nrows][width] from the final floats and the Qs (mode_off: every Q is 0); quarter = H/4
+int launch_demod_trace(const float *fin_rows, const float2 *dbg_rows, int n, bool mode_off, int nrows, int width, int quarter,
+                       const int *tab, int32_t *trace_rows, hipStream_t st);
+// spec_rows[nrows][width] from PSD rows of n + 2 floats; half = H/2
+int launch_demod_spec(const float *psd_rows, int n, int nrows, int width, int half, const int *tab, int32_t *spec_rows,
+                      hipStream_t st);
+
 }  // namespace jsdr

@@ -15,8 +15,11 @@
 //   * max / AGC need the whole frame: the output is a second pass over the demodulated floats.
 // Kernels: k_demod_front (raw -> demodulated float per sample + per-frame max), k_demod_mean (AM only),
 // k_demod_out (-> int16 L,R), k_demod_state (history for the next call), k_demod_nco.
+// The demod scope (jsdr_demod_scope_*: the batch call, then demod.paintComponent's trace and spectrum per frame) has its host
+// side here, behind demod_run, and its kernels in demod_scope.hip.
 #include "common.h"
 #include "demod.h"
+#include "demod_dev.h"
 #include <math.h>
 #include <stdlib.h>
 #include <thread>
@@ -25,224 +28,7 @@
 namespace jsdr {
 
 
-struct DemodConst {
-    float w[21];
-    float fmgain;
-    int mode, dofir, dodwn, doagc;
-};
-
-struct DemodArgs {
-    const int *raw;        // int16 pairs [S][stride]
-    const float2 *rawf;    // or float pairs
-    long long stride_pairs;
-    long long L;           // samples per stream in this call
-    int n;                 // samples per frame
-    int nfr;               // frames per stream in this call
-    int ic, qc;
-    const float2 *hist;    // [S][21] filter input before the call
-    const float2 *lilq;    // [S] FM detector state before the call
-    const float2 *nco;     // [L] (cos, sin) of the carrier phase per sample (dodwn)
-    float *d;              // [S][L] demodulated value per sample (sam[s] after :441-462)
-    unsigned *fmax_bits;   // [S][nfr] bit pattern of max |d| (zeroed before launch)
-    DemodConst c;
-};
-
-template <bool F32IN>
-__device__ __forceinline__ float2 demod_in(const DemodArgs &a, const int *raw, const float2 *rawf, const float2 *hist,
-                                           long long g)
-{
-    if (g < 0) return hist[DHALO + g];
-    if (F32IN) return rawf[g];
-    const int w = raw[g];
-    return make_float2(i16_to_float_java(java_short_add((int)(short)(w & 0xffff), a.ic)),
-                       i16_to_float_java(java_short_add(w >> 16, a.qc)));
-}
-
-// filter() (:378-396) + mixer (:423-434) at ONE sample whose window sits in xs[first .. first+20] (newest last);
-// used for the sample just before a tile and for the state kernel
-template <class IDX>
-__device__ __forceinline__ float2 demod_mixed_at(const DemodConst &c, const float2 *xs, IDX idx, int newest, const float2 *nco,
-                                                 long long g)
-{
-    float2 v = xs[idx(newest)];
-    if (c.dofir) {
-        float oi = 0.0f, oq = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 21; k++) {  // ring order: the newest sample meets w[0]
-            const float2 x = xs[idx(newest - k)];
-            oi = oi + x.x * c.w[k];
-            oq = oq + x.y * c.w[k];
-        }
-        v = make_float2(oi, oq);
-    }
-    if (c.dodwn) {
-        const float2 cs = nco[g];
-        v = make_float2(v.x * cs.x - v.y * cs.y, v.x * cs.y + v.y * cs.x);
-    }
-    return v;
-}
-
-// the sample just before the tile: xs[xpad8(20)] is x(g0 - 1)
-__device__ __forceinline__ float2 demod_mixed(const DemodConst &c, const float2 *xs, const float2 *nco, long long g)
-{
-    return demod_mixed_at(c, xs, [](int i) { return xpad8(i); }, DHALO - 1, nco, g);
-}
-
-// One tile = 2048 samples of one frame of one stream; every thread owns 8 CONSECUTIVE samples: their 21-tap
-// windows overlap, so 28 LDS reads feed 8 outputs (3.5 per sample instead of 21), and I/Q ride in one packed
-// register pair: acc = acc + x*w is v_pk_mul_f32 + v_pk_add_f32, each half rounded separately exactly like the
-// reference's two scalar statements (:388-389).
-constexpr int DXS = DTILE + DHALO + (DTILE + DHALO) / 8 + 1;
-
-// tile j of frame f of stream s -> this thread's 8 detected samples dv[] (sam[s] after :441-462) and the running
-// maximum of their magnitudes; xs / last are the workgroup's LDS (two barriers inside, none after)
-template <bool F32IN, bool CHAINED>
-__device__ __forceinline__ void demod_tile(const DemodArgs &a, const int s, const int f, const int j, float2 *xs, float2 *last,
-                                           float (&dv)[DPER], unsigned &mbits)
-{
-    constexpr int PER = DPER;
-    const int tid = threadIdx.x;
-    const long long g0 = (long long)f * a.n + (long long)j * DTILE;
-    const int len = (a.n - j * DTILE) < DTILE ? (a.n - j * DTILE) : DTILE;
-    const int *raw = a.raw + (long long)s * a.stride_pairs;
-    const float2 *rawf = a.rawf + (long long)s * a.stride_pairs;
-    const float2 *hist = a.hist + (long long)s * DHALO;
-    // FM detector across tiles of one workgroup: the previous tile's last sample, read before the staging barrier
-    // below lets anyone overwrite it
-    float2 carried = make_float2(0.0f, 0.0f);
-    if (CHAINED && tid == 0) carried = last[255];
-    // xs[xpad8(i)] = x(g0 - 21 + i); beyond the tile's end: zeros (their outputs are never stored)
-    if (g0 >= DHALO) {
-        // every tile but the call's first: all nine loads of a thread are in flight before the first conversion /
-        // LDS store (as a plain loop the compiler waits for each load in turn: nine memory latencies per tile)
-        // addressing: one uniform base per tile and a 32-bit offset per load, clamped inside the call (values
-        // beyond the tile's end are dropped below)
-        constexpr int NLD = (DTILE + DHALO + 255) / 256;
-        const long long room = a.L - 1 - (g0 - DHALO);
-        const unsigned relmax = (unsigned)(room < (long long)(DTILE + DHALO - 1) ? room : (long long)(DTILE + DHALO - 1));
-        const int *rb = raw + (g0 - DHALO);
-        const float2 *rbf = rawf + (g0 - DHALO);
-        int w[NLD];
-        float2 wf[NLD];
-#pragma unroll
-        for (int q = 0; q < NLD; q++) {
-            unsigned rel = (unsigned)(tid + 256 * q);
-            rel = rel < relmax ? rel : relmax;
-            if (F32IN)
-                wf[q] = rbf[rel];
-            else
-                w[q] = rb[rel];
-        }
-        const bool full = len == DTILE;  // every tile of a frame but a ragged last one
-#pragma unroll
-        for (int q = 0; q < NLD; q++) {
-            const int i = tid + 256 * q;
-            float2 v;
-            if (F32IN)
-                v = wf[q];
-            else
-                v = make_float2(i16_to_float_java(java_short_add((int)(short)(w[q] & 0xffff), a.ic)),
-                                i16_to_float_java(java_short_add(w[q] >> 16, a.qc)));
-            // xpad8(tid + 256 q) = xpad8(tid) + 288 q: one address register, constant offsets
-            float2 *slot = xs + (tid + (tid >> 3)) + 288 * q;
-            if (full) {
-                if (q < NLD - 1 || i < DTILE + DHALO) *slot = v;
-            } else if (i < DTILE + DHALO) {
-                *slot = (i < len + DHALO) ? v : make_float2(0.0f, 0.0f);
-            }
-        }
-    } else {
-        for (int i = tid; i < DTILE + DHALO; i += 256)
-            xs[xpad8(i)] = (i < len + DHALO) ? demod_in<F32IN>(a, raw, rawf, hist, g0 - DHALO + i) : make_float2(0.0f, 0.0f);
-    }
-    __syncthreads();
-    const int t0 = tid * PER;  // first sample of this thread within the tile
-    v2f m[PER];                // filtered + mixed samples
-    if (a.c.dofir) {
-        v2f x[PER + 20];  // x[q] = input sample t0 - 20 + q
-#pragma unroll
-        for (int q = 0; q < PER + 20; q++) {
-            // xpad8(8 tid + c) = 9 tid + c + (c >> 3)
-            const float2 v = xs[9 * tid + (1 + q) + ((1 + q) >> 3)];
-            x[q] = (v2f){v.x, v.y};
-        }
-#pragma unroll
-        for (int u = 0; u < PER; u++) {
-            v2f acc = (v2f){0.0f, 0.0f};
-#pragma unroll
-            for (int k = 0; k < 21; k++) acc = acc + x[u + 20 - k] * a.c.w[k];  // ring order: newest sample meets w[0]
-            m[u] = acc;
-        }
-    } else {
-#pragma unroll
-        for (int u = 0; u < PER; u++) {
-            const float2 v = xs[9 * tid + (DHALO + u) + ((DHALO + u) >> 3)];
-            m[u] = (v2f){v.x, v.y};
-        }
-    }
-    if (a.c.dodwn) {  // :423-434
-        const float2 *nc = a.nco + g0 + t0;
-        float2 cs[PER];
-        if (((g0 + t0) & 1) == 0) {  // 16-byte aligned pairs (always, unless the frame length is odd)
-#pragma unroll
-            for (int u = 0; u < PER; u += 2) {
-                // (an odd tile end reads one entry past its last sample: inside the table, which has spare slots)
-                const float4 c2 = (t0 + u < len) ? reinterpret_cast<const float4 *>(nc)[u / 2] : make_float4(1.0f, 0.0f, 1.0f, 0.0f);
-                cs[u] = make_float2(c2.x, c2.y);
-                cs[u + 1] = make_float2(c2.z, c2.w);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < PER; u++) cs[u] = (t0 + u < len) ? nc[u] : make_float2(1.0f, 0.0f);
-        }
-#pragma unroll
-        for (int u = 0; u < PER; u++) {
-            // (x*c - y*s, x*s + y*c) as x*(c, s) + (-y, y)*(s, c): two packed products and one packed sum (x - y == x + (-y) exactly)
-            const v2f v = m[u];
-            const v2f c = (v2f){cs[u].x, cs[u].y};
-            const v2f ny = (v2f){-v.y, v.y};
-            m[u] = __builtin_shufflevector(v, v, 0, 0) * c + ny * __builtin_shufflevector(c, c, 1, 0);
-        }
-    }
-    // the FM detector's previous sample: the neighbour thread's last one; thread 0 recomputes it from the halo,
-    // or takes the carried state at the first sample of the call
-    float2 prev = make_float2(0.0f, 0.0f);
-    if (a.c.mode == MODE_NFM || a.c.mode == MODE_WFM) {
-        last[tid] = make_float2(m[PER - 1].x, m[PER - 1].y);
-        __syncthreads();
-        if (tid > 0)
-            prev = last[tid - 1];
-        else if (CHAINED)
-            prev = carried;
-        else if (g0 > 0)
-            prev = demod_mixed(a.c, xs, a.nco, g0 - 1);
-        else
-            prev = a.lilq[s];
-    }
-    // max |d| travels as a bit pattern: non-negative floats order like unsigned ints, and any NaN beats every
-    // number -- Math.max's NaN propagation (:463) for free
-#pragma unroll
-    for (int u = 0; u < PER; u++) {
-        const v2f mm = m[u];
-        if (a.c.mode == MODE_OFF) {
-            dv[u] = 0.0f;
-        } else if (a.c.mode == MODE_RAW) {
-            dv[u] = mm.x;
-        } else if (a.c.mode == MODE_AM) {
-            // :449 (float)Math.sqrt((double)..): the correctly rounded double root of a float, rounded to float, IS the
-            // correctly rounded float root (53 >= 2*24 + 2 bits), which is what sqrtf compiles to here (v_sqrt_f32
-            // plus a one-ulp fix-up; __fsqrt_rn is NOT correctly rounded) -- all FP32, no v_rsq_f64 chain
-            dv[u] = __builtin_sqrtf(mm.x * mm.x + mm.y * mm.y);
-        } else {
-            dv[u] = ((prev.x * mm.y) - (prev.y * mm.x)) * a.c.fmgain;
-            prev = make_float2(mm.x, mm.y);
-        }
-        if (t0 + u < len) {
-            const unsigned bb = __float_as_uint(dv[u]) & 0x7fffffffu;
-            mbits = bb > mbits ? bb : mbits;
-        }
-    }
-}
+// (DemodArgs, demod_in, demod_mixed_at, demod_mixed and demod_tile: demod_dev.h, shared with demod_scope.hip)
 
 __device__ __forceinline__ unsigned demod_block_max(unsigned mbits, unsigned *red)
 {
@@ -497,6 +283,14 @@ __global__ __launch_bounds__(256) void k_demod_out(const float *__restrict__ d, 
 
 using namespace jsdr;
 
+// the scope's jsdr_fft, owned like a stream or an event (counted by jsdr_live_resources among them)
+static hipError_t demod_scope_fft_release(jsdr_fft *f)
+{
+    (void)jsdr_fft_destroy(f);
+    return hipSuccess;
+}
+using DemodScopeFft = Owned<jsdr_fft *, demod_scope_fft_release>;
+
 struct jsdr_demod {
     int rate = 0, n = 0, nstreams = 0;
     long long max_batch = 0;
@@ -545,6 +339,17 @@ struct jsdr_demod {
     DevBuf<float> dch;         // [dslots * nin][L] float rows (AM channels; every channel of a frame above 5 tiles)
     Event ev_done, ev_clear;   // end of the last call; a channel ring cleared after it
     bool done_any = false, clear_pending = false;
+    // the demod scope (jsdr_demod_scope_*): all of it empty until the first scope call
+    struct Scope {
+        DevBuf<float2> dbg;    // [frames of a pass][n] mixed IQ, when the caller takes no dbg rows
+        DevBuf<float> fin;     // [frames of a pass][n] final floats (trace)
+        DevBuf<float> psd;     // [frames of a pass][n + 2] (spectrum)
+        DevBuf<int> tab;       // int[4][width]: the column schedules of tab_width
+        int tab_width = 0;
+        DemodScopeFft fft;     // jsdr_fft of n samples (spectrum)
+        int chunk = 0;         // jsdr_demod_scope_chunk; 0: the default
+        std::string kernel;
+    } scope;
 };
 
 enum { DK_NCO = 0, DK_FRONT, DK_STATE, DK_MEAN, DK_OUT, DK_CHAN, DK_COUNT };
@@ -924,7 +729,178 @@ static int demod_chan_receive(jsdr_demod *h, const float *buf_host, int16_t *aud
     return JSDR_OK;
 }
 
+// ---- the demod scope: demod.paintComponent's trace and spectrum (:509-558) for every frame of a batch call
+// the column schedules of (n, width) in the reference's float arithmetic; any of the four arrays may be null.  Refuses a pair
+// at which the reference would index outside sam[] (getAbsMax, :569-578) or psd[] (getMax, :560-567).
+static int demod_scope_layout(const char *who, int n, int width, int32_t *tf, int32_t *tc, int32_t *sf, int32_t *sc)
+{
+    const float scale = dscope_scale(n, width), pi = dscope_pi(n, width);
+    const int tcnt = (int)scale, scnt = (int)pi;
+    for (int x = 0; x < width; x++) {
+        const bool col = x < width - 1;
+        const int i = col ? dscope_trace_first(x, scale) : 0;
+        // sam[2i] always; then sam[2i + 1], sam[2i + 3], .. below 2i + (int)scale: the Qs of samples i .. i + tcnt/2 - 1
+        JSDR_REQUIRE(!col || (i >= 0 && i < n && i + tcnt / 2 <= n),
+                     "%s: n=%d, width=%d: trace column %d would read sam[] from sample %d on, %d values", who, n, width, x, i, tcnt);
+        if (tf) tf[x] = i;
+        if (tc) tc[x] = col ? tcnt : 0;
+        const int k = x ? dscope_spec_first(x, pi) : 0;
+        JSDR_REQUIRE(k >= 0 && k < n && (!x || k + scnt <= n),
+                     "%s: n=%d, width=%d: spectrum column %d would read psd[] from bin %d on, %d values", who, n, width, x, k, scnt);
+        if (sf) sf[x] = k;
+        if (sc) sc[x] = x ? scnt : 0;
+    }
+    return JSDR_OK;
+}
+
+template <bool F32IN>
+static int demod_scope_run(const char *who, jsdr_demod *h, const int16_t *raw_dev, const float *rawf_dev, int64_t stride_i16,
+                           int64_t L, int ic, int qc, int16_t *audio_dev, int64_t audio_stride_i16, int width, int height,
+                           int32_t *trace_dev, int32_t *spec_dev, float *dbg_dev, hipStream_t st)
+{
+    const char *in_name = F32IN ? "iq_dev" : "raw_dev", *stride_name = F32IN ? "stream_stride_f32" : "stream_stride_i16";
+    // every refusal before any device work, the handle and its state untouched
+    JSDR_REQUIRE(h, "%s: null handle", who);
+    JSDR_REQUIRE(raw_dev || rawf_dev, "%s: null %s", who, in_name);
+    JSDR_REQUIRE(audio_dev, "%s: null audio_dev", who);
+    JSDR_REQUIRE(width >= 1 && width <= DSCOPE_WIDTH_MAX, "%s: width=%d outside 1..%d", who, width, (int)DSCOPE_WIDTH_MAX);
+    JSDR_REQUIRE(height >= 0, "%s: height=%d is negative", who, height);
+    JSDR_REQUIRE(!h->chan, "%s: a channel handle (jsdr_demod_create_channels) has no scope", who);
+    JSDR_REQUIRE(!spec_dev || (h->n >= 2 && h->n <= 20000),
+                 "%s: spec_dev with a frame of %d samples: jsdr_fft_create takes 2 .. 20000", who, h->n);
+    JSDR_REQUIRE((stride_i16 & 1) == 0 && (h->nstreams == 1 || (stride_i16 >= 0 && stride_i16 / 2 >= L)),
+                 "%s: %s=%lld is odd or below a stream's nsamples=%lld", who, stride_name, (long long)stride_i16, (long long)L);
+    JSDR_REQUIRE((audio_stride_i16 & 1) == 0 && (h->nstreams == 1 || (audio_stride_i16 >= 0 && audio_stride_i16 / 2 >= L)),
+                 "%s: audio_stride_i16=%lld is odd or below a stream's nsamples=%lld", who, (long long)audio_stride_i16, (long long)L);
+    JSDR_REQUIRE(h->n > 0 && L > 0 && L <= h->max_batch && L % h->n == 0,
+                 "%s: nsamples=%lld must be a positive multiple of the frame (%d) and at most max_batch_samples=%lld", who,
+                 (long long)L, h->n, h->max_batch);
+    if (trace_dev || spec_dev)
+        if (demod_scope_layout(who, h->n, width, nullptr, nullptr, nullptr, nullptr) != JSDR_OK) return JSDR_ERR;
+    JSDR_REQUIRE((reinterpret_cast<uintptr_t>(dbg_dev) & 15) == 0, "%s: dbg_dev is not aligned to 16 bytes", who);
+    JSDR_REQUIRE((reinterpret_cast<uintptr_t>(trace_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(spec_dev) & 3) == 0,
+                 "%s: trace_dev or spec_dev is not aligned to 4 bytes", who);
+    if (!trace_dev && !spec_dev && !dbg_dev) {  // the batch call itself
+        h->scope.kernel.clear();
+        return demod_run<F32IN>(h, raw_dev, rawf_dev, stride_i16, L, ic, qc, audio_dev, audio_stride_i16, st);
+    }
+    jsdr_demod::Scope &sc = h->scope;
+    const int n = h->n, nfr = (int)(L / n);
+    const long long rows = (long long)h->nstreams * nfr;
+    // frames of a pass: what DSCOPE_SCRATCH_BYTES holds of dbg (8n), final floats (4n) and PSD (4n + 8) rows -- one frame at least
+    long long fpp = (long long)(DSCOPE_SCRATCH_BYTES / (16 * (size_t)n + 8));
+    if (fpp < 1) fpp = 1;
+    if (sc.chunk > 0 && sc.chunk < fpp) fpp = sc.chunk;
+    if (fpp > rows) fpp = rows;
+    // scratch, the schedule table and the FFT handle: before the call's own work, so that a failure leaves the state as it was
+    const size_t want_dbg = dbg_dev ? 0 : (size_t)fpp * n, want_fin = trace_dev ? (size_t)fpp * n : 0,
+                 want_psd = spec_dev ? (size_t)fpp * ((size_t)n + 2) : 0;
+    if (want_dbg > sc.dbg.n || want_fin > sc.fin.n || want_psd > sc.psd.n || !sc.tab.p) {
+        JSDR_HIP_TRY(hipDeviceSynchronize());  // earlier calls may still use the smaller rows
+        if (want_dbg > sc.dbg.n && sc.dbg.alloc(want_dbg) != JSDR_OK) return JSDR_ERR;
+        if (want_fin > sc.fin.n && sc.fin.alloc(want_fin) != JSDR_OK) return JSDR_ERR;
+        if (want_psd > sc.psd.n && sc.psd.alloc(want_psd) != JSDR_OK) return JSDR_ERR;
+        if (!sc.tab.p) {
+            if (sc.tab.alloc(4 * (size_t)DSCOPE_WIDTH_MAX) != JSDR_OK) return JSDR_ERR;
+            sc.tab_width = 0;
+        }
+    }
+    if (spec_dev && !sc.fft.h) {
+        jsdr_fft *f = nullptr;
+        if (jsdr_fft_create(&f, n, h->rate) != JSDR_OK) return JSDR_ERR;
+        sc.fft.adopt(f);
+    }
+    // what the passes read, as it is BEFORE the call: demod_run leaves the other halves of hist / lilq and this call's
+    // carrier table alone until the next call (the call after next, for the table)
+    DemodArgs a;
+    a.raw = reinterpret_cast<const int *>(raw_dev);
+    a.rawf = reinterpret_cast<const float2 *>(rawf_dev);
+    a.stride_pairs = stride_i16 / 2;
+    a.L = L;
+    a.n = n;
+    a.nfr = nfr;
+    a.ic = ic;
+    a.qc = qc;
+    a.hist = h->hist[h->cur].p;
+    a.lilq = h->lilq[h->cur].p;
+    const int set = (int)(h->calls & 1);
+    a.nco = h->nco[set].p;
+    a.d = nullptr;
+    a.fmax_bits = nullptr;
+    memcpy(a.c.w, h->wfir, sizeof(a.c.w));
+    a.c.fmgain = (float)h->rate / (MODE_NFM == h->mode ? 5000.0f : 75000.0f);  // :410
+    a.c.mode = h->mode;
+    a.c.dofir = h->dofir;
+    a.c.dodwn = h->dodwn;
+    a.c.doagc = h->doagc;
+    if (demod_run<F32IN>(h, raw_dev, rawf_dev, stride_i16, L, ic, qc, audio_dev, audio_stride_i16, st) != JSDR_OK) return JSDR_ERR;
+    if ((trace_dev || spec_dev) && sc.tab_width != width) {  // on the caller's stream, behind the previous call's readers
+        sc.tab_width = 0;
+        if (launch_demod_scope_layout(n, width, sc.tab.p, st) != JSDR_OK) return JSDR_ERR;
+        sc.tab_width = width;
+    }
+    for (long long r0 = 0; r0 < rows; r0 += fpp) {
+        const int nr = (int)(rows - r0 < fpp ? rows - r0 : fpp);
+        float2 *dbg_rows = dbg_dev ? reinterpret_cast<float2 *>(dbg_dev) + (size_t)r0 * n : sc.dbg.p;
+        if (launch_demod_scope_front(a, F32IN, h->stats.p, r0, nr, dbg_rows, trace_dev ? sc.fin.p : nullptr, st) != JSDR_OK)
+            return JSDR_ERR;
+        if (trace_dev &&
+            launch_demod_trace(sc.fin.p, dbg_rows, n, h->mode == MODE_OFF, nr, width, height / 4, sc.tab.p,
+                               trace_dev + (size_t)r0 * width, st) != JSDR_OK)
+            return JSDR_ERR;
+        if (spec_dev) {
+            if (jsdr_fft_batch_f32(sc.fft.h, reinterpret_cast<const float *>(dbg_rows), nr, sc.psd.p, st) != JSDR_OK) return JSDR_ERR;
+            if (launch_demod_spec(sc.psd.p, n, nr, width, height / 2, sc.tab.p, spec_dev + (size_t)r0 * width, st) != JSDR_OK)
+                return JSDR_ERR;
+        }
+    }
+    if (h->dodwn) JSDR_HIP_TRY(hipEventRecord(h->ev_used[set], st));  // the passes read the carrier table too
+    sc.kernel = "k_demod_scope_front";
+    if (trace_dev) sc.kernel += "+k_demod_trace";
+    if (spec_dev) sc.kernel += std::string("+") + jsdr_fft_kernel(sc.fft.h) + "+k_demod_spec";
+    return JSDR_OK;
+}
+
 extern "C" {
+
+int jsdr_demod_scope_layout(int n, int width, int32_t *trace_first, int32_t *trace_count, int32_t *spec_first, int32_t *spec_count,
+                            int cap)
+{
+    JSDR_REQUIRE(n >= 1, "jsdr_demod_scope_layout: n=%d must be positive", n);
+    JSDR_REQUIRE(width >= 1 && width <= DSCOPE_WIDTH_MAX, "jsdr_demod_scope_layout: width=%d outside 1..%d", width,
+                 (int)DSCOPE_WIDTH_MAX);
+    JSDR_REQUIRE(cap >= width || !(trace_first || trace_count || spec_first || spec_count),
+                 "jsdr_demod_scope_layout: cap=%d is below width=%d", cap, width);
+    // (checked first, so that a refused pair writes nothing)
+    if (demod_scope_layout("jsdr_demod_scope_layout", n, width, nullptr, nullptr, nullptr, nullptr) != JSDR_OK) return JSDR_ERR;
+    return demod_scope_layout("jsdr_demod_scope_layout", n, width, trace_first, trace_count, spec_first, spec_count);
+}
+
+int jsdr_demod_scope_i16(jsdr_demod *h, const int16_t *raw_dev, int64_t stream_stride_i16, int64_t nsamples, int ic, int qc,
+                         int16_t *audio_dev, int64_t audio_stride_i16, int width, int height, int32_t *trace_dev,
+                         int32_t *spec_dev, float *dbg_dev, void *stream)
+{
+    return demod_scope_run<false>("jsdr_demod_scope_i16", h, raw_dev, nullptr, stream_stride_i16, nsamples, ic, qc, audio_dev,
+                                  audio_stride_i16, width, height, trace_dev, spec_dev, dbg_dev, as_stream(stream));
+}
+
+int jsdr_demod_scope_f32(jsdr_demod *h, const float *iq_dev, int64_t stream_stride_f32, int64_t nsamples, int16_t *audio_dev,
+                         int64_t audio_stride_i16, int width, int height, int32_t *trace_dev, int32_t *spec_dev, float *dbg_dev,
+                         void *stream)
+{
+    return demod_scope_run<true>("jsdr_demod_scope_f32", h, nullptr, iq_dev, stream_stride_f32, nsamples, 0, 0, audio_dev,
+                                 audio_stride_i16, width, height, trace_dev, spec_dev, dbg_dev, as_stream(stream));
+}
+
+int jsdr_demod_scope_chunk(jsdr_demod *h, int frames_per_pass)
+{
+    JSDR_REQUIRE(h, "jsdr_demod_scope_chunk: null handle");
+    JSDR_REQUIRE(frames_per_pass >= 0, "jsdr_demod_scope_chunk: frames_per_pass=%d is negative", frames_per_pass);
+    h->scope.chunk = frames_per_pass;
+    return JSDR_OK;
+}
+
+const char *jsdr_demod_scope_kernel(jsdr_demod *h) { return h ? h->scope.kernel.c_str() : ""; }
 
 int jsdr_demod_create(jsdr_demod **out, int rate, int nsamples_per_frame, int nstreams, int64_t max_batch_samples)
 {
