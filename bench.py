@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- IQ Msamples/s through FFT + FIR + BPSK demod on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload pipeline|fft|bpsk] [--streams S] [--samples L] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--full] [--workload pipeline|fft|bpsk] [--streams S] [--samples L] [--dump-outputs DIR]
+
+The plain command does what its headline figure needs and nothing else: it sets up, warms up, times the K steps (where the library
+says the CU split may pay, both forms of the pipeline, K steps each: the line is the faster one's), writes the outputs if
+--dump-outputs is given and prints the JSON line.  Its roofline block holds what the timed steps themselves measured (HIP events
+and the library's timing scopes inside them) with the stored traffic table; "validated" is null.  Everything that takes time of
+its own runs with --full only: the counted HBM traffic (child runs under rocprofv3), the five steps of the other pipeline form
+after the timed region where that form did not run it, the validation against the payloads and the oracle, the gather check of
+the distributed path, and the CPU baseline.  With --full the --no-* options below switch those parts off one by one, as before.
 
 One STEP = one pass of the hot path over one HBM-resident batch of synthetic input:
     S streams x L int16 IQ samples (96 kHz FUNcube-style DBPSK carrying valid FEC frames, generated on
@@ -16,11 +24,12 @@ per rank instead ("scaling": "weak").  Every step ends with one all-gather of th
 slots over xGMI.  value = samples processed by all ranks / max-over-ranks time.
 
 The JSON line also carries
-    roofline     : dominant kernel (HIP events recorded on the launch stream inside the timed region); at N = 1 its `traffic`
-                   (HBM bytes per launch) is COUNTED IN THE RUN: before its first GPU call this process runs its own command
-                   line (two steps, no validation) as a child under `rocprofv3 --pmc FETCH_SIZE` and again under `--pmc
-                   WRITE_SIZE` (live_traffic_table; ~6 s; --no-live-traffic, or a failing profiler: the stored table under profiles/)
-    cpu_baseline : the plain-C oracle (oracle/, a restatement of the Java arithmetic: kind "port") on the
+    roofline     : dominant kernel (HIP events recorded on the launch stream inside the timed region); with --full at N = 1 its
+                   `traffic` (HBM bytes per launch) is COUNTED IN THE RUN: before its first GPU call this process runs its own
+                   command line (two steps, no validation) as a child under `rocprofv3 --pmc FETCH_SIZE` and again under `--pmc
+                   WRITE_SIZE` (live_traffic_table; ~6 s; without --full, with --no-live-traffic, or with a failing profiler: the
+                   stored table under profiles/)
+    cpu_baseline : with --full, the plain-C oracle (oracle/, a restatement of the Java arithmetic: kind "port") on the
                    host cores, bounded sample, rank 0 at N=1 only.
 """
 import argparse
@@ -72,6 +81,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, everything that takes time of its own: the HBM traffic counted in child runs under "
+                         "rocprofv3, the other pipeline form after the timed region, the validation against the payloads and the oracle, "
+                         "the gather check of the distributed path and the CPU baseline (each with a --no-* option of its own); "
+                         "without it the run sets up, warms up, times the steps and prints its line")
     ap.add_argument("--workload", default="pipeline", choices=["pipeline", "fft", "bpsk", "demod", "fir"])
     ap.add_argument("--total-streams", type=int, default=8192,
                     help="streams of the whole job, sharded over the GPUs (strong scaling, BASELINE config 5)")
@@ -87,7 +101,7 @@ def parse():
                     help="pipeline workload where the CU split may pay (8192 streams per GPU): run side by side without first timing three "
                          "steps of each form after the warm-up (profile runs: one form only)")
     ap.add_argument("--no-compare-serial", dest="compare_serial", action="store_false",
-                    help="pipeline workload, side by side: skip the five steps of the one-after-the-other form that are otherwise timed on "
+                    help="--full, pipeline workload, side by side: skip the five steps of the one-after-the-other form that are otherwise timed on "
                          "the same box right after the timed region (roofline.one_after_the_other_ms_per_step: boxes differ by more "
                          "than the two forms do, so the pair belongs in one record); profile runs pass it so that per-kernel averages "
                          "are those of ONE form")
@@ -95,7 +109,7 @@ def parse():
                     help="pipeline workload: PSD then demodulator on ONE stream, each kernel with the whole chip (the default until round 4). "
                          "Default now, from 8192 streams per GPU: side by side on two streams with the CU shares set (jsdr_fft_set_cu_share 2, jsdr_bpsk_set_cu_share 1)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="N = 1: do not count the HBM traffic in this run (two child runs of this command under rocprofv3 --pmc, "
+                    help="--full at N = 1: do not count the HBM traffic in this run (two child runs of this command under rocprofv3 --pmc, "
                          "about a minute); roofline.traffic then comes from the stored table under profiles/")
     ap.add_argument("--live-traffic-timeout", type=float, default=240.0, help="seconds one counter pass may take")
     ap.add_argument("--psd-stream", action="store_true",
@@ -103,8 +117,8 @@ def parse():
                          "one after the other on one stream, whose per-kernel times are not inflated by the overlap)")
     ap.add_argument("--samples", type=int, default=1048576, help="IQ samples per stream per step")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-validate", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-validate", action="store_true", help="--full without the validation against the payloads and the oracle")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64, at most "
                          "64 MB in all: a fixed, seeded sample of larger outputs, with the sampled rows in <name>_rows.npy)")
@@ -564,8 +578,8 @@ def live_traffic_table(a, samples_per_launch):
     # re-execs, and a different python3 on PATH may lack this process's packages)
     py = os.path.realpath(sys.executable) if sys.executable else "python3"
     argv = sys.argv[1:]
-    child = [x for i, x in enumerate(argv)  # (the child writes no outputs: --dump-outputs is this run's)
-             if not (x.startswith("--dump-outputs") or (i > 0 and argv[i - 1] == "--dump-outputs"))]
+    child = [x for i, x in enumerate(argv)  # (the child is a plain run and writes no outputs: --full and --dump-outputs are this run's)
+             if not (x == "--full" or x.startswith("--dump-outputs") or (i > 0 and argv[i - 1] == "--dump-outputs"))]
     child += ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-validate", "--no-compare-serial",
                                          "--no-autotune", "--no-live-traffic"]
     tmp = tempfile.mkdtemp(prefix="jsdr_pmc_", dir="/tmp")
@@ -688,7 +702,7 @@ def main():
             raise
     live_tab, live_why = None, None
     under_profiler = any(k.startswith("ROCPROF") or k.startswith("ROCP_") for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if (N == 1 and not D and not a.no_live_traffic and os.environ.get("JSDR_BENCH_CHILD") != "1" and not under_profiler and
+    if (a.full and N == 1 and not D and not a.no_live_traffic and os.environ.get("JSDR_BENCH_CHILD") != "1" and not under_profiler and
             os.environ.get("JSDR_BENCH_LIVE_TRAFFIC", "1") != "0" and os.path.exists("/dev/kfd")):
         # (before this process's first GPU call; not when this run is itself being profiled, not for the A/B tooling's runs)
         S_ = a.streams if a.streams > 0 else a.total_streams
@@ -1069,7 +1083,7 @@ def main():
         # (both forms ran the full timed region: the other form's figure is that run's)
         roofline["side_by_side_ms_per_step" if not form["sbs"] else "one_after_the_other_ms_per_step"] = \
             autotune["side_by_side_ms" if not form["sbs"] else "one_after_the_other_ms"]
-    elif shares != (0, 0) and psd_stream is not None and not a.serial and not a.psd_stream and N == 1 and not D and a.compare_serial:
+    elif shares != (0, 0) and psd_stream is not None and not a.serial and not a.psd_stream and N == 1 and not D and a.full and a.compare_serial:
         # the OTHER form, five steps right after the timed region
         calls_made += 7
         ran = form["sbs"]
@@ -1086,13 +1100,14 @@ def main():
 
     # ---- validation outside the timed region: every sampled stream decodes what it was sent
     validated = None
+    validate = a.full and not a.no_validate
     # (FFT-acquire mode is not validated by payload: the reference's block-wise FFT filter puts a seam into the
     #  signal every frame, and at 2048-sample frames its own demodulator -- the oracle bit for bit, see
     #  tests/test_gpu_bpsk.py -- rarely brings a 5200-bit FEC block through; parity for that mode is the tests')
     cert = None
     vstats = None
     none_streams = []
-    if dem is not None and not a.no_validate and not (a.fft_acquire and (a.bpsk_frame != 9600 or RATE != 96000)):
+    if dem is not None and validate and not (a.fft_acquire and (a.bpsk_frame != 9600 or RATE != 96000)):
         payloads = pay.to_host(np.uint8).reshape(S, nfr, 256)
         info = dem.slot_info()
         vslots = J.DeviceBuffer(S * info["slot_bytes"])
@@ -1123,7 +1138,7 @@ def main():
         if a.fft_acquire and n_good < S // 2:
             # FFT-acquire mode may lose frames by design, but a run in which (almost) nothing decodes has checked nothing
             validated = None if n_good == 0 else False
-    if dem is not None and not a.no_validate:
+    if dem is not None and validate:
         # any frame size: sampled streams against the oracle replaying the same calls (the payload check above only exists
         # for the 9600-sample frame, and passes over streams without a decoded frame: here the oracle must lose those too).
         # Tune mode (the default line): 8 sampled streams, every call of the run, bit for bit -- counters, state doubles,
@@ -1138,14 +1153,14 @@ def main():
             st_o["recovered_streams_among_them"] = rec_ids
         vstats = dict(vstats or {}, **st_o)
         validated = bool(ok_o) if validated is None else bool(validated and ok_o)
-    if fft is not None and not a.no_validate:
+    if fft is not None and validate:
         # the PSD the step wrote (also on the pipeline line: it used to go unread there)
         ok_f, st_f = validate_fft(J, d_iq, d_psd, nframes, RATE)
         vstats = dict(vstats or {}, psd=st_f)
         validated = bool(ok_f) if dem is None else bool(validated and ok_f)
-    if fir_taps is not None and not a.no_validate:
+    if fir_taps is not None and validate:
         validated, vstats = validate_fir(J, d_iq, d_fir, S, L, fir_taps, a.fir_decim, 0.9 * 32768.0)
-    if amfm is not None and not a.no_validate:
+    if amfm is not None and validate:
         J.binding.stream_sync(None)
         validated, vstats = validate_demod(J, d_iq, d_audio, S, L, a.warmup + a.steps, DEMOD_MODES[a.demod_mode], RATE)
     if dem is not None and a.variant == "fast":
@@ -1158,9 +1173,9 @@ def main():
             print(f"[bench] fast variant: {cert['streams_uncertified']} stream(s) ended uncertified -- validated: false",
                   file=sys.stderr)
 
-    # ---- N > 1: the gathered buffer of the LAST timed step against this rank's own results
+    # ---- --full, N > 1: the gathered buffer of the LAST timed step against this rank's own results
     gather_check = None
-    if dem is not None and D:
+    if dem is not None and D and a.full:
         import hashlib
         info = dem.slot_info()
         sb = info["slot_bytes"]
@@ -1234,7 +1249,7 @@ def main():
                 out["rccl_version"] = None
         if cert is not None:
             out["certification"] = cert
-        if N == 1 and not a.no_cpu_baseline:
+        if a.full and N == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.workload if a.workload != "demod" else "demod:" + a.demod_mode, L, a.cpu_seconds)
         sys.stdout.flush()
         if saved_stdout is not None:

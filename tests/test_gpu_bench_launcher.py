@@ -27,7 +27,7 @@ def run_bench(extra, env_extra):
 
 def test_bare_command_two_ranks_gather_is_checked():
     r, lines = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--streams", "48", "--samples", "1048576",
-                          "--no-cpu-baseline"], {"JSDR_BENCH_SAME_DEVICE": "1", "JSDR_BENCH_BACKEND": "gloo"})
+                          "--full", "--no-cpu-baseline"], {"JSDR_BENCH_SAME_DEVICE": "1", "JSDR_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
     out = json.loads(lines[0])
@@ -44,7 +44,7 @@ def test_bare_command_four_ranks_strong_scaling_shape():
     """the shape of the driver's N > 2 lines: --total-streams fixed, S/N per rank, contiguous shards, one gather a step.
     Four ranks, not eight: the GPU box allows six processes on the card at once (this test process is one of them)."""
     r, lines = run_bench(["--gpus", "4", "--steps", "2", "--warmup", "1", "--total-streams", "32", "--samples", "524288",
-                          "--no-cpu-baseline"], {"JSDR_BENCH_SAME_DEVICE": "1", "JSDR_BENCH_BACKEND": "gloo"})
+                          "--full", "--no-cpu-baseline"], {"JSDR_BENCH_SAME_DEVICE": "1", "JSDR_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
     out = json.loads(lines[0])
@@ -85,7 +85,7 @@ def test_distributed_path_with_the_real_backend_and_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dist-single", "--streams", "256", "--steps", "3",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -96,7 +96,7 @@ def test_distributed_path_with_the_real_backend_and_one_rank():
 
 
 def test_roofline_traffic_is_counted_in_the_run_itself():
-    """`python bench.py` at N = 1 counts the HBM bytes it reports: the same command as a child process under rocprofv3 --pmc
+    """`python bench.py --full` at N = 1 counts the HBM bytes it reports: the same command as a child process under rocprofv3 --pmc
     FETCH_SIZE and again under --pmc WRITE_SIZE before the timed run ('roofline.traffic is a stored constant').
     A small pipeline batch: the source says so, the per-kernel table holds the step's kernels, and the PSD kernel's bytes are its
     algorithmic ones (4 B in + 4 B out per sample) within what the counters' granularity allows."""
@@ -106,7 +106,7 @@ def test_roofline_traffic_is_counted_in_the_run_itself():
         env.pop(k, None)
     S, L = 256, 1048576
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--streams", str(S), "--samples", str(L), "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[:2000]
@@ -117,7 +117,7 @@ def test_roofline_traffic_is_counted_in_the_run_itself():
     assert rf["traffic"] and rf["traffic"] > 0
     # the same command with the counting switched off: the stored table, and the line says that instead
     r2 = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--streams", str(S), "--samples", str(L), "--steps", "2",
-                         "--warmup", "1", "--no-cpu-baseline", "--no-live-traffic", "--serial"], env=env, capture_output=True, text=True, timeout=600)
+                         "--warmup", "1", "--full", "--no-cpu-baseline", "--no-live-traffic", "--serial"], env=env, capture_output=True, text=True, timeout=600)
     assert r2.returncode == 0, r2.stderr[-2000:]
     rf2 = json.loads([ln for ln in r2.stdout.splitlines() if ln.strip()][0])["roofline"]
     assert "not counted in this run" in rf2["traffic_source"]
@@ -128,3 +128,36 @@ def test_roofline_traffic_is_counted_in_the_run_itself():
     # ... and the counted table of the first run agrees with it kernel by kernel
     per = rf["traffic_per_kernel"]
     assert 0.9 * S * L * 8.0 < per["k_fft"] < 1.3 * S * L * 8.0 and 0.9 * S * L * 5.6 < per["k_fm"] < 1.3 * S * L * 5.6, per
+
+
+def test_plain_run_is_lean_and_full_brings_the_rest():
+    """the plain command sets up, warms up, times its steps and prints the line: no validation, no CPU baseline, no counted
+    traffic, and at most 30 s of the whole run (start to exit) outside its (steps + warmup) x ms_per_step.  The same command with
+    --full validates and measures the CPU baseline as before.  A small batch (what is checked is which parts run) of streams long
+    enough to hold whole FEC frames of 5200 symbols x 80 samples, so that every stream decodes one and the validation can pass."""
+    import time
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--streams", "64", "--samples", "1048576"]
+    env = {"JSDR_BENCH_LIVE_TRAFFIC": "1"}
+    t0 = time.perf_counter()
+    r, lines = run_bench(args, env)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
+    out = json.loads(lines[0])
+    assert out["metric"].startswith("IQ Msamples/s") and out["unit"] == "Msamples/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f64" and out["value"] > 0 and out["ms_per_step"] > 0 and out["steps"] == 2 and out["warmup"] == 1
+    assert out["validated"] is None and "validation" not in out and "cpu_baseline" not in out, sorted(out)
+    rf = out["roofline"]
+    assert "not counted in this run" in rf["traffic_source"] and "valu_issue" not in rf, rf
+    assert "k_fft" in rf["kernels_ms_per_step"] and "k_fm" in rf["kernels_ms_per_step"]  # (measured inside the timed steps)
+    outside = wall - 3 * out["ms_per_step"] * 1e-3
+    print(f"plain run: {wall:.2f} s in all, {outside:.2f} s outside its steps")
+    assert outside <= 30.0, (wall, out["ms_per_step"])
+    r, lines = run_bench(args + ["--full", "--no-live-traffic", "--cpu-seconds", "1"], env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len(lines) == 1, (r.stdout[-2000:], r.stderr[-2000:])
+    full = json.loads(lines[0])
+    assert full["validated"] is True and full["validation"]["streams_compared_with_the_oracle"] > 0, full
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline"]["unit"] == "Msamples/s"
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert full[k] == out[k], k

@@ -41,6 +41,18 @@ def test_bench_refuses_experiment_knobs_and_reports_missing_gpu():
         assert r.returncode != 0 and "no HIP device" in (r.stderr + r.stdout)
 
 
+def test_bench_full_option_is_off_by_default(monkeypatch):
+    """the plain command is the lean one: --full exists, is off unless given, and leaves the other options as they were"""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and (a.gpus, a.steps, a.warmup, a.dump_outputs) == (1, 4, 2, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-validate"])
+    a = bench.parse()
+    assert a.full is True and a.no_validate is True and not a.no_cpu_baseline and not a.no_live_traffic and a.compare_serial
+
+
 def test_strong_scaling_shards_are_contiguous_and_cover_every_stream():
     from java_sdr_amd import sharding as SH
     for total, n in ((8192, 1), (8192, 2), (8192, 4), (8192, 8), (1000, 8)):

@@ -25,7 +25,7 @@ SQ2="SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_LDS_BAN
 for FR in $FRAMES; do  # a frame size, or size@rate (4410@44100)
   F=${FR%@*}; RATE=96000; case $FR in *@*) RATE=${FR#*@};; esac
   ARGS="--workload bpsk --fft-acquire --bpsk-frame $F --rate $RATE --streams 1024 --no-cpu-baseline"
-  step acq${F} 300 python bench.py $ARGS --steps 5 --warmup 2
+  step acq${F} 300 python bench.py --full $ARGS --steps 5 --warmup 2
   line $O/${T}_acq${F}.log > $O/${T}_acq${F}.json
   PA="$ARGS --steps 2 --warmup 1 --no-validate"
   JSDR_FFT_PHASECLK=1 step clk_$F 300 python bench.py $PA

@@ -20,7 +20,7 @@ SQ4="SQ_INST_LEVEL_VMEM SQ_INST_LEVEL_LDS SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_
 export JSDR_NO_OVERLAP=1
 for V in exact fast; do
   A="--workload bpsk --variant $V --no-cpu-baseline"
-  step bpsk_$V 300 python bench.py $A --steps 5 --warmup 2
+  step bpsk_$V 300 python bench.py --full $A --steps 5 --warmup 2
   grep '^{"metric' $O/${T}_bpsk_$V.log | tail -1 > $O/${T}_b_bpsk_alone_$V.json
   i=1
   for SQ in "$SQ1" "$SQ2" "$SQ3" "$SQ4"; do

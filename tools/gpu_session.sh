@@ -27,27 +27,27 @@ for step in "$@"; do
     smoke)       run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     micro)       run micro_build 120 hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o /tmp/mb_fp64 tools/microbench_fp64.hip
                  run micro 120 /tmp/mb_fp64 ;;
-    bench_small) run bench_small 300 python bench.py --steps 3 --warmup 1 --streams 128 --samples 1048576 --cpu-seconds 3 ;;
-    bench)       JSDR_BENCH_LIVE_TRAFFIC=1 run bench 900 python bench.py ;;
+    bench_small) run bench_small 300 python bench.py --full --steps 3 --warmup 1 --streams 128 --samples 1048576 --cpu-seconds 3 ;;
+    bench)       JSDR_BENCH_LIVE_TRAFFIC=1 run bench 900 python bench.py --full ;;
     tests_demod) run tests_demod 600 python -m pytest tests/test_gpu_demod.py -m gpu -q -x -p no:cacheprovider --timeout 600 ;;
     tests_fft)   run tests_fft 900 python -m pytest tests/test_gpu_fft.py -m gpu -q -x -p no:cacheprovider --timeout 800 ;;
     tests_misc)  run tests_misc 600 python -m pytest tests/test_gpu_fir_phase_fec.py tests/test_gpu_host.py -m gpu -q -x -p no:cacheprovider --timeout 600 ;;
     tests_fmt)   run tests_fmt 600 python -m pytest tests/test_gpu_formats.py -m gpu -q -x -p no:cacheprovider --timeout 600 ;;
     tests_host)  run tests_host 600 python -m pytest tests/test_gpu_host.py -m gpu -q -x -p no:cacheprovider --timeout 600 ;;
     tests_bpsk)  run tests_bpsk 600 python -m pytest tests/test_gpu_bpsk.py -m gpu -q -x -p no:cacheprovider --timeout 600 ;;
-    bench_quick) run bench_quick 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_acq)   run bench_acq 400 python bench.py --workload bpsk --fft-acquire --steps 3 --warmup 1 --no-cpu-baseline ;;
-    bench_acq9600) run bench_acq9600 400 python bench.py --workload bpsk --fft-acquire --bpsk-frame 9600 --steps 3 --warmup 1 --no-cpu-baseline ;;
-    bench_acq_clk) JSDR_FFT_PHASECLK=1 run bench_acq_clk 400 python bench.py --workload bpsk --fft-acquire --steps 2 --warmup 1 --no-cpu-baseline ;;
-    bench_n2)    JSDR_BENCH_SAME_DEVICE=1 JSDR_BENCH_BACKEND=gloo run bench_n2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --streams 256 ;;
-    bench_reg_alone) JSDR_NO_OVERLAP=1 run bench_reg_alone 300 python bench.py --workload bpsk --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_reg) run bench_reg 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_m64) JSDR_FFT_GRID_MULT=64 run bench_m64 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_m256) JSDR_FFT_GRID_MULT=256 run bench_m256 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_m16) JSDR_FFT_GRID_MULT=16 run bench_m16 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_alone_b) JSDR_LIB=$PWD/java-sdr_amd/libjsdr_hip_b.so JSDR_NO_OVERLAP=1 run bench_alone_b 300 python bench.py --workload bpsk --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_alone) JSDR_NO_OVERLAP=1 run bench_alone 300 python bench.py --workload bpsk --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_noov)  JSDR_NO_OVERLAP=1 run bench_noov 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_quick) run bench_quick 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_acq)   run bench_acq 400 python bench.py --full --workload bpsk --fft-acquire --steps 3 --warmup 1 --no-cpu-baseline ;;
+    bench_acq9600) run bench_acq9600 400 python bench.py --full --workload bpsk --fft-acquire --bpsk-frame 9600 --steps 3 --warmup 1 --no-cpu-baseline ;;
+    bench_acq_clk) JSDR_FFT_PHASECLK=1 run bench_acq_clk 400 python bench.py --full --workload bpsk --fft-acquire --steps 2 --warmup 1 --no-cpu-baseline ;;
+    bench_n2)    JSDR_BENCH_SAME_DEVICE=1 JSDR_BENCH_BACKEND=gloo run bench_n2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 3 --warmup 1 --streams 256 ;;
+    bench_reg_alone) JSDR_NO_OVERLAP=1 run bench_reg_alone 300 python bench.py --full --workload bpsk --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_reg) run bench_reg 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_m64) JSDR_FFT_GRID_MULT=64 run bench_m64 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_m256) JSDR_FFT_GRID_MULT=256 run bench_m256 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_m16) JSDR_FFT_GRID_MULT=16 run bench_m16 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_alone_b) JSDR_LIB=$PWD/java-sdr_amd/libjsdr_hip_b.so JSDR_NO_OVERLAP=1 run bench_alone_b 300 python bench.py --full --workload bpsk --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_alone) JSDR_NO_OVERLAP=1 run bench_alone 300 python bench.py --full --workload bpsk --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_noov)  JSDR_NO_OVERLAP=1 run bench_noov 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
     fec_bench)   run fec_bench 300 python tests/tools/fec_bench.py ;;
     hbm)         run hbm_build 120 hipcc --offload-arch=gfx950 -O3 -o /tmp/mb_hbm tools/microbench_hbm.hip
                  run hbm 120 /tmp/mb_hbm ;;
@@ -91,17 +91,17 @@ for step in "$@"; do
     fftm_small)  FM_S=8 FM_NFR=20 run fftm_small 300 python tools/fftm_bench.py ;;
     dbg_demod)   run dbg_demod 300 python tests/tools/dbg_demod.py ;;
     trig)        run trig 300 python tests/tools/trig_stats.py ;;
-    bench_fft)   run bench_fft 300 python bench.py --workload fft --no-cpu-baseline ;;
-    bench_fft_m16) JSDR_FFT_GRID_MULT=16 run bench_fft_m16 300 python bench.py --workload fft --no-cpu-baseline ;;
-    bench_fft_m64) JSDR_FFT_GRID_MULT=64 run bench_fft_m64 300 python bench.py --workload fft --no-cpu-baseline ;;
-    bench_fft_m1k) JSDR_FFT_GRID_MULT=1024 run bench_fft_m1k 300 python bench.py --workload fft --no-cpu-baseline ;;
-    bench_fft_m1) JSDR_FFT_GRID_MULT=1 run bench_fft_m1 300 python bench.py --workload fft --no-cpu-baseline ;;
-    bench_demod) run bench_demod 400 python bench.py --workload demod --steps 5 --warmup 2 --cpu-seconds 4 ;;
-    bench_demod_fm) run bench_demod_fm 400 python bench.py --workload demod --demod-mode nfm --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_fft_wf) run bench_fft_wf 300 python bench.py --workload fft --waterfall-width 1024 --no-cpu-baseline ;;
-    bench_fft_b) JSDR_LIB=$PWD/java-sdr_amd/libjsdr_hip_b.so run bench_fft_b 300 python bench.py --workload fft --no-cpu-baseline ;;
-    bench_quick_b) JSDR_LIB=$PWD/java-sdr_amd/libjsdr_hip_b.so run bench_quick_b 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
-    bench_bpsk)  run bench_bpsk 400 python bench.py --workload bpsk --no-cpu-baseline ;;
+    bench_fft)   run bench_fft 300 python bench.py --full --workload fft --no-cpu-baseline ;;
+    bench_fft_m16) JSDR_FFT_GRID_MULT=16 run bench_fft_m16 300 python bench.py --full --workload fft --no-cpu-baseline ;;
+    bench_fft_m64) JSDR_FFT_GRID_MULT=64 run bench_fft_m64 300 python bench.py --full --workload fft --no-cpu-baseline ;;
+    bench_fft_m1k) JSDR_FFT_GRID_MULT=1024 run bench_fft_m1k 300 python bench.py --full --workload fft --no-cpu-baseline ;;
+    bench_fft_m1) JSDR_FFT_GRID_MULT=1 run bench_fft_m1 300 python bench.py --full --workload fft --no-cpu-baseline ;;
+    bench_demod) run bench_demod 400 python bench.py --full --workload demod --steps 5 --warmup 2 --cpu-seconds 4 ;;
+    bench_demod_fm) run bench_demod_fm 400 python bench.py --full --workload demod --demod-mode nfm --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_fft_wf) run bench_fft_wf 300 python bench.py --full --workload fft --waterfall-width 1024 --no-cpu-baseline ;;
+    bench_fft_b) JSDR_LIB=$PWD/java-sdr_amd/libjsdr_hip_b.so run bench_fft_b 300 python bench.py --full --workload fft --no-cpu-baseline ;;
+    bench_quick_b) JSDR_LIB=$PWD/java-sdr_amd/libjsdr_hip_b.so run bench_quick_b 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline ;;
+    bench_bpsk)  run bench_bpsk 400 python bench.py --full --workload bpsk --no-cpu-baseline ;;
     prof)        rm -rf gpurun_out/prof_$R
                  run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$R -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline ;;
     pmc_rd)      rm -rf gpurun_out/pmc_rd_$R

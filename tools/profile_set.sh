@@ -18,10 +18,10 @@ step() { # name timeout cmd...
   if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "TIMEOUT in $name: stopping" | tee -a $O/session.log; exit 99; fi
   if grep -q "Memory access fault" "$O/${T}_$name.log"; then echo "GPU FAULT in $name: stopping" | tee -a $O/session.log; exit 98; fi
 }
-step bench 500 python bench.py --steps 20 --warmup 5
+step bench 500 python bench.py --full --steps 20 --warmup 5
 line $O/${T}_bench.log > $O/${T}_bench.json
 rm -rf $O/prof_$T $O/pmc_rd_$T $O/pmc_wr_$T
-step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-compare-serial --no-autotune
+step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$T -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-compare-serial --no-autotune
 line $O/${T}_prof.log > $O/${T}_bench_under_rocprof.json
 cp "$(find $O/prof_$T -name '*kernel_stats.csv' | head -1)" $O/${T}_kernel_stats.csv
 step pmc_rd 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_rd_$T -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-validate --no-compare-serial --no-autotune
@@ -41,7 +41,7 @@ for tag, ctr in (("rd", "FETCH_SIZE"), ("wr", "WRITE_SIZE")):
         for k in sorted(acc):
             o.write(f'"{k}",{ctr},{len(acc[k])},{sum(acc[k]) / len(acc[k]):.1f}\n')
 PY
-B="--no-cpu-baseline"
+B="--full --no-cpu-baseline"
 # the pipeline the old way: PSD then demodulator on one stream, each kernel with the whole chip (per-kernel times not stretched by the other)
 step b_serial 300 python bench.py --serial --steps 20 --warmup 5 $B;     line $O/${T}_b_serial.log > $O/${T}_b_serial.json
 step b_bpsk 300 python bench.py --workload bpsk $B;                      line $O/${T}_b_bpsk.log > $O/${T}_b_bpsk.json
