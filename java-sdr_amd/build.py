@@ -44,8 +44,14 @@ SOURCES = {
     "demod_chan.hip": ["-ffp-contract=off"],
     # (the demod scope: demod.hip's tile again, the column schedules' float products and the painters' casts)
     "demod_scope.hip": ["-ffp-contract=off"],
-    # (the handle: host code only, but tuPhaseInc and its sin / cos tables are doubles that must round as Java's do)
+    # (the handle's units, bpsk_handle.h: host code only, but tuPhaseInc and its sin / cos tables are doubles that must round as Java's do)
+    "bpsk_call.hip": ["-ffp-contract=off"],
     "bpsk_handle.hip": ["-ffp-contract=off"],
+    "bpsk_control.hip": ["-ffp-contract=off"],
+    "bpsk_results.hip": ["-ffp-contract=off"],
+    "bpsk_call_chan.hip": ["-ffp-contract=off"],
+    "bpsk_ckpt.hip": ["-ffp-contract=off"],
+    "bpsk_call_pst.hip": ["-ffp-contract=off"],
     # (the host scheduler: host code only, it steps the reference's phase recurrences in doubles that must round as Java's do)
     "bpsk_sched.hip": ["-ffp-contract=off"],
     "bpsk_fft.hip": ["-ffp-contract=off"],

@@ -1,4 +1,4 @@
-// bpsk_chan.h -- the channel handle's tune-mode front end (bpsk_chan.hip), launched from bpsk_handle.hip.
+// bpsk_chan.h -- the channel handle's tune-mode front end (bpsk_chan.hip), launched from bpsk_call_chan.hip.
 #pragma once
 #include "common.h"
 

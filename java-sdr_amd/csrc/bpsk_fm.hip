@@ -622,7 +622,7 @@ __global__ __launch_bounds__(FM_THREADS, JSDR_FM_MINWAVES) void k_fm(FmArgs a)
 }
 
 // =============================================================================================== launchers
-// What bpsk_handle.hip starts (bpsk_kernels.h): the grid, the LDS and the template choice of each kernel.
+// What the handle's call (bpsk_call.hip) starts (bpsk_kernels.h): the grid, the LDS and the template choice of each kernel.
 
 int bpsk_fm_upload_constants(const BpskConst &bc)
 {

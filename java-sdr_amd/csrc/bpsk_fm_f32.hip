@@ -1,6 +1,6 @@
 // bpsk_fm_f32.hip -- tune mode, float input: k_fm_f32, the front end and the matched filter in ONE kernel for the frames of
 // IAudioHandler.receive(float[]) taken as they are (x = (double)f: no DC correction, no scaling), and k_fm_prep_f32, its
-// streams' edge images and the next call's input history.  jsdr_bpsk_batch_f32's hot path (bpsk_handle.hip).
+// streams' edge images and the next call's input history.  jsdr_bpsk_batch_f32's hot path (bpsk_call.hip).
 //
 // k_fm_f32 is k_fm (bpsk_fm.hip) with a float window: the same tile (FM_NB blocks of 65 outputs + 64 of halo in LDS), the
 // same jobs of R outputs a lane, the same walk newest -> oldest and the same matched half, so every floating-point operation

@@ -467,7 +467,7 @@ __global__ void k_hist_convert(int2 *hist, int nstreams, int to_float, int *bad)
 }
 
 // =============================================================================================== launchers
-// What bpsk_handle.hip starts (bpsk_kernels.h): the grid, the LDS and the template choice of each kernel.
+// What the handle's call (bpsk_call.hip) starts (bpsk_kernels.h): the grid, the LDS and the template choice of each kernel.
 
 int bpsk_front_upload_constants(const BpskConst &bc)
 {

@@ -1,5 +1,5 @@
 // bpsk_pst.h -- the front end of a tuned handle (jsdr_bpsk_create_tuned: every stream its own tuning), bpsk_pst.hip, as
-// bpsk_handle.hip starts it.
+// bpsk_call_pst.hip starts it.
 #pragma once
 #include "common.h"
 #include "bpsk_kernels.h"

@@ -1,4 +1,4 @@
-// bpsk_state.h -- the checkpoint kernels (bpsk_state.hip) as the handle (bpsk_handle.hip) starts them: k_state_pack gathers the
+// bpsk_state.h -- the checkpoint kernels (bpsk_state.hip) as the handle (bpsk_ckpt.hip) starts them: k_state_pack gathers the
 // records of a range of streams from the handle's live buffers into one stream-major image (bpsk_blob.h's record layout),
 // k_state_unpack scatters such an image back.  Every buffer choice -- which bit log and where the register starts in it, dm or
 // dmh, which input history and tuner-index buffer -- is resolved by the handle and arrives here as a pointer and a stride.

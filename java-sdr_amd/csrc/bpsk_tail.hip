@@ -31,7 +31,7 @@
 //   k_fec_bpsk  : FECDecode of every triggered window (fec.hip)
 // DESIGN.md has the lane/LDS mapping of each kernel and its roofline.
 //
-// The handle, the host scheduler and the C ABI are in bpsk_handle.hip, which sees the four units through bpsk_kernels.h: the
+// The handle and the C ABI are in the host units of bpsk_handle.h, which see the four units through bpsk_kernels.h: the
 // argument structs and the launch_* functions at the end of each unit.
 #include "bpsk_units.h"
 #include <math.h>
@@ -1170,7 +1170,7 @@ __global__ void k_reset_maxcorr_chan(TailState *st, int nin, int nch, int ch)
 }
 
 // =============================================================================================== launchers
-// What bpsk_handle.hip starts (bpsk_kernels.h): the grid, the LDS and the template choice of each kernel.
+// What the handle's call (bpsk_call.hip) starts (bpsk_kernels.h): the grid, the LDS and the template choice of each kernel.
 namespace jsdr {
 
 // every unit's copy of the tables (bpsk_units.h)

@@ -11,7 +11,7 @@
 // librccl.so is loaded with dlopen when the first group is created (the single-GPU library does not depend on it); a
 // group that is created with JSDR_GROUP_GATHER_COPY gathers with device-to-device copies instead (what a host without
 // RCCL, or a rehearsal with several ranks on ONE device -- RCCL refuses a device twice -- can run).
-#include "common.h"
+#include "bpsk_handle.h"  // (bpsk_live_check: the checks of jsdr_bpsk_set_tuning / _set_mode)
 #include <dlfcn.h>
 #include <atomic>
 #include <condition_variable>
@@ -20,8 +20,6 @@
 #include <thread>
 #include <cmath>
 #include <vector>
-
-int bpsk_live_check(jsdr_bpsk *h, int do_fft, const char *who);  // bpsk_handle.hip: the checks of jsdr_bpsk_set_tuning / _set_mode
 
 namespace jsdr {
 

@@ -2,7 +2,7 @@
 W owns a contiguous block of streams and no data-path collective is needed; the only exchange is ONE all-gather
 per batch of fixed-size per-stream result slots (equal counts on every rank).
 
-Slot layout (must match csrc/bpsk_tail.hip k_pack_slots, sized by csrc/bpsk_handle.hip jsdr_bpsk_slot_info):
+Slot layout (must match csrc/bpsk_tail.hip k_pack_slots, sized by csrc/bpsk_results.hip jsdr_bpsk_slot_info):
     int32 header[16] = {nbits, nfec, cntRaw, cntDS, cntBit, cntFEC, cntDec, dmErrBits, dmCorr, dmMaxCorr, decodeOK, 0..}
     int8  bits[slot_bits]
     nfec_max x { int32 rc; int32 bit_index; uint8 data[256] }
