@@ -1238,7 +1238,7 @@ def waterfall_lines(psd, n, width, peak_rgb=0x00FFFF):
 
 def waterfall_lines_dev(psd_dev, nframes, n, width, pix_dev, peak_rgb=0x00FFFF, stream=None):
     _check(lib().jsdr_waterfall_lines(_addr(psd_dev), C.c_int64(nframes), n, width, C.c_uint32(peak_rgb),
-                                      _addr(pix_dev), stream), "jsdr_waterfall_lines")
+                                      _addr(pix_dev), C.c_void_p(stream)), "jsdr_waterfall_lines")
 
 
 def recording_probe(path, raw_channels=2):

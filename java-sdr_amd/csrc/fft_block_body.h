@@ -2,6 +2,10 @@
 // batch, FPB frames at a time.  In scope: the kernel's argument a (FftArgs / FftPixArgs) and the constants N, T, FPB, IN, OUT,
 // R0 .. R3, TWG.  (A function that both kernels called would state it as well; k_fft then comes out of the compiler with another
 // schedule than it had, and its form was settled by measurement.)
+// Where a frame is whole waves (T a multiple of 64) everything this loop hands to fft_fetch / fft_frame about WHICH frame -- the slot
+// in the workgroup, the frame's number with the surplus part-workgroup's clamp, the next frame's -- is a scalar: the rows are then
+// addressed as scalar base + 32-bit lane offset (wave_row, fft_common.h) and no vector register carries a frame number or an address
+// through the passes (profiles/r10_fft_uniform_lanes.md).  Frames of 8 or 16 threads share a wave and keep per-lane values.
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int FE = lds_frame_elems(N);
     constexpr int TWN = TWG ? 0 : tw_total(R0, R1, R2, R3);
@@ -21,8 +25,10 @@
         __syncthreads();
     }
 
-    const int fib = tid_b / T;
+    int fib = tid_b / T;
     const int tid = tid_b - fib * T;
+    // whole waves a frame: the slot is a scalar, and so are the frame numbers, the clamp and the row bases made from it below
+    if constexpr (frame_is_waves(T)) fib = FPB == 1 ? 0 : __builtin_amdgcn_readfirstlane(fib);
     float2 *buf = bufs + (size_t)fib * FE;
     const long long ngroups = (a.nframes + FPB - 1) / FPB;
     // a surplus part-workgroup (frame count not a multiple of FPB) redoes the last frame: identical values to

@@ -244,6 +244,76 @@ struct Best {
     int k;
 };
 
+// A frame of T threads with T a multiple of 64 is whole waves: its slot in the workgroup, its number, the clamp of a surplus
+// part-workgroup, the next frame and every row base made from them are the same in all 64 lanes.  The compiler cannot see that
+// through threadIdx.x / T; the slot is said to be a scalar (v_readfirstlane) and the rest follows in scalar registers.
+constexpr bool frame_is_waves(int T) { return T % 64 == 0; }
+
+// A row of global memory whose base is the same in every lane of a wave, addressed as scalar base + unsigned 32-bit lane
+// offset + constant: a buffer resource (the base and the row's size in four scalar registers), the lane's byte offset in ONE
+// vector register that never changes, the constant in a scalar register.  No 64-bit address is built per frame or per access.
+// (Stated as `base + zext(offset)` on a plain pointer the compiler hoists the zero-extension and the lane's part of the sum
+// out of the frame loop, and inside the loop builds base + 64-bit vector offset again -- the global saddr form is matched
+// only where the zero-extension stands in the block of the access.)  The resource carries the row's size: an access outside
+// [0, bytes) reads zero or is dropped by the hardware.
+using WaveRow = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ WaveRow wave_row(const void *base, unsigned bytes)
+{
+    // (word 3: 32-bit untyped data, the raw-buffer setting of the gfx9 family; stride 0, so the range check is in bytes)
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
+}
+template <class V>
+__device__ __forceinline__ V wave_row_load(WaveRow row, unsigned lane_bytes, unsigned const_bytes)
+{
+    static_assert(sizeof(V) == 4 || sizeof(V) == 8, "one or two dwords a lane");
+    if constexpr (sizeof(V) == 4) return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b32(row, lane_bytes, const_bytes, 0));
+    else return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b64(row, lane_bytes, const_bytes, 0));
+}
+template <class V>
+__device__ __forceinline__ void wave_row_store(WaveRow row, unsigned lane_bytes, unsigned const_bytes, V v)
+{
+    static_assert(sizeof(V) == 4 || sizeof(V) == 8, "one or two dwords a lane");
+    if constexpr (sizeof(V) == 4)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), row, lane_bytes, const_bytes, 0);
+    else
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(decltype(__builtin_amdgcn_raw_buffer_load_b64(row, 0, 0, 0)), v), row,
+                                              lane_bytes, const_bytes, 0);
+}
+
+// ------------------------------------------------------------------ first maximum over the 64 lanes of a wave, no LDS
+// Inside a row of 16 lanes four DPP steps whose partners are an involution each (the quad's neighbour, the quad's other pair,
+// the mirrored half row, the mirrored row) leave the row's result in all 16 lanes; the four rows are read as scalars
+// (v_readlane) and combined, so the result is the same in every lane.
+template <int CTRL>
+__device__ __forceinline__ int dpp_i32(int x)
+{
+    // (every lane has a partner under these four controls: bound_ctrl and `old` decide nothing, and in this form the move folds
+    //  into the v_max_i32 / v_min_i32 that uses it)
+    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xf, 0xf, true);
+}
+constexpr int DPP_QUAD_1032 = 0xB1, DPP_QUAD_2301 = 0x4E, DPP_ROW_HALF_MIRROR = 0x141, DPP_ROW_MIRROR = 0x140;
+template <bool MAX, int CTRL>
+__device__ __forceinline__ int pick_dpp(int x)
+{
+    const int o = dpp_i32<CTRL>(x);
+    return MAX ? (o > x ? o : x) : (o < x ? o : x);
+}
+template <bool MAX>
+__device__ __forceinline__ int wave_reduce_i32(int x)
+{
+    x = pick_dpp<MAX, DPP_QUAD_1032>(x);
+    x = pick_dpp<MAX, DPP_QUAD_2301>(x);
+    x = pick_dpp<MAX, DPP_ROW_HALF_MIRROR>(x);
+    x = pick_dpp<MAX, DPP_ROW_MIRROR>(x);
+    const int r0 = __builtin_amdgcn_readlane(x, 0), r1 = __builtin_amdgcn_readlane(x, 16);
+    const int r2 = __builtin_amdgcn_readlane(x, 32), r3 = __builtin_amdgcn_readlane(x, 48);
+    const int a = MAX ? (r0 > r1 ? r0 : r1) : (r0 < r1 ? r0 : r1), b = MAX ? (r2 > r3 ? r2 : r3) : (r2 < r3 ? r2 : r3);
+    return MAX ? (a > b ? a : b) : (a < b ? a : b);
+}
+// The bits of a float that is not a NaN as a signed integer that orders as the float does (negative floats run backwards as
+// integers: their magnitude bits are flipped); its own inverse.  +0 and -0, equal as floats, get the keys 0 and -1.
+__device__ __forceinline__ int f32_order_key(int bits) { return bits ^ (int)((unsigned)(bits >> 31) >> 1); }
+
 // mixed-radix path (fft_mixed.hip): n = 4800, 9600 -- java-sdr's default 48 kHz / 96 kHz frames
 struct MixedPlan {
     int n = 0, nrad = 0, radix[6] = {1, 1, 1, 1, 1, 1};

@@ -93,13 +93,16 @@ __device__ __forceinline__ void fft_fetch(const FftArgs &a, FR frame, int tid, t
 #else
         frame_in(frame, N);
 #endif
+    using RAW = typename RawPoint<IN>::type;
+    [[maybe_unused]] const WaveRow row = wave_row(src, N * (unsigned)sizeof(RAW));  // (whole waves a frame: `src` is a scalar)
 #pragma unroll
     for (int r = 0; r < R; r++) {
 #ifdef JSDR_X_FFT_NOLOAD  // timing experiment: no input loads (wrong data)
         if constexpr (IN == IN_I16) w[r] = (tid + r * NB) * 2654435761u + (int)(size_t)src;
         else w[r] = make_float2((float)(tid + r), (float)(size_t)src);
 #else
-        w[r] = src[tid + r * NB];
+        if constexpr (frame_is_waves(T)) w[r] = wave_row_load<RAW>(row, tid * (unsigned)sizeof(RAW), r * NB * (unsigned)sizeof(RAW));
+        else w[r] = src[tid + r * NB];
 #endif
     }
 }
@@ -209,7 +212,12 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, FR frame, bool active
                 if constexpr (OUT == OUT_SPEC) {
                     float2 *dst = reinterpret_cast<float2 *>(a.out) + frame_out(frame, N);
 #pragma unroll
-                    for (int r = 0; r < R; r++) dst[j0 + r * P] = v[gi][cx_bitrev(r, R)];
+                    for (int r = 0; r < R; r++) {
+                        if constexpr (frame_is_waves(T))
+                            wave_row_store(wave_row(dst, N * 8u), j0 * 8u, r * P * 8u, v[gi][cx_bitrev(r, R)]);
+                        else
+                            dst[j0 + r * P] = v[gi][cx_bitrev(r, R)];
+                    }
                 } else {
                     float *dst = a.out + frame_out(frame, N + 2);
                     float db[R];
@@ -220,8 +228,10 @@ __device__ __forceinline__ void fft_pass(const FftArgs &a, FR frame, bool active
                             reinterpret_cast<float *>(buf)[row_pad(j0 + r * P)] = db[r];
                         } else {
 #ifndef JSDR_X_FFT_NOSTORE  // timing experiment: no PSD stores (the argmax keeps the arithmetic alive)
-                            dst[j0 + r * P] = db[r];  // (nontemporal stores: 1.99 -> 2.39 ms, measured r02; 8-byte stores through a DPP
-                                                      //  exchange between neighbouring lanes: 15.5 -> 16.1 ms at 8192 streams, r03)
+                            // (nontemporal stores: 1.99 -> 2.39 ms, measured r02; 8-byte stores through a DPP exchange between
+                            //  neighbouring lanes: 15.5 -> 16.1 ms at 8192 streams, r03)
+                            if constexpr (frame_is_waves(T)) wave_row_store(wave_row(dst, (N + 2) * 4u), j0 * 4u, r * P * 4u, db[r]);
+                            else dst[j0 + r * P] = db[r];
 #endif
                         }
                     }
@@ -286,13 +296,31 @@ __device__ __forceinline__ void fft_frame(const ARGS &a, FR frame, FN next, int 
         float bestv = best.v;
         int bestk = best.k;
         constexpr int W = (T < 64) ? T : 64;
+        if constexpr (frame_is_waves(T)) {
+            // whole waves: two reductions in registers (wave_reduce_i32, fft_common.h) -- the wave's maximum M, then the lowest
+            // bin among the lanes that hold it -- where a butterfly of (value, bin) exchanges took six LDS round trips.
+            // The maximum is taken over integer keys (f32_order_key), which order as the merge's '>' / '==' pair does on every
+            // value that arrives here: a thread's best.v starts at -FLT_MAX and is replaced only by a gm with gm > best.v,
+            // which no NaN and no -inf satisfies, so the lanes hold -FLT_MAX, finite values and +inf -- no NaN, and on floats
+            // that are not NaN the key's order is the float order.  (+0 and -0, equal to '==', have two keys; psd_db's last
+            // operation is an fma with the non-zero addend OFF, whose exact zero rounds to +0: -0 is never a dB value.)  So equal
+            // keys are equal values, M is the bits of the value the merge kept, and a lane that never took a bin holds
+            // k = INT_MAX, which is also what a lane below M contributes to the second reduction.  (v_max_f32 on a value that
+            // came through a DPP move gets a canonicalising v_max in front of it at every step; v_max_i32 does not, and the
+            // four rows combine in scalar registers.)
+            const int key = f32_order_key(__builtin_bit_cast(int, bestv));
+            const int mkey = wave_reduce_i32<true>(key);
+            bestk = wave_reduce_i32<false>(key == mkey ? bestk : 0x7fffffff);
+            bestv = __builtin_bit_cast(float, f32_order_key(mkey));
+        } else {
 #pragma unroll
-        for (int off = W / 2; off >= 1; off >>= 1) {
-            float ov = __shfl_xor(bestv, off, W);
-            int ok = __shfl_xor(bestk, off, W);
-            const bool take = (ov > bestv) | ((ov == bestv) & (ok < bestk));  // branch-free
-            bestv = take ? ov : bestv;
-            bestk = take ? ok : bestk;
+            for (int off = W / 2; off >= 1; off >>= 1) {
+                float ov = __shfl_xor(bestv, off, W);
+                int ok = __shfl_xor(bestk, off, W);
+                const bool take = (ov > bestv) | ((ov == bestv) & (ok < bestk));  // branch-free
+                bestv = take ? ov : bestv;
+                bestk = take ? ok : bestk;
+            }
         }
         if constexpr (T > 64) {
             constexpr int NW = T / 64;
