@@ -639,6 +639,65 @@ int jsdr_bpsk_batch_i16(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stream_str
  * where FFT-acquire needs them, a JSDR_VARIANT_FAST handle (its certification re-reads int16).
  * Not covered: jsdr_group_*, the FAST variant, JNI and the Java classes (they feed floats through receive_f32). */
 int jsdr_bpsk_batch_f32(jsdr_bpsk *h, const float *iq_dev, int64_t stream_stride_f32, int64_t nsamples, void *stream);
+/* The BPSK scope over batches: the five debug rings of FUNcubeBPSKDemod (tuned, downSmpl, demodIQ, demodBits, demodRe,
+ * FUNcubeBPSKDemod.java:118-125) and everything paintComponent's first panel computes from them (:231-268), for every frame of a
+ * batch call.  A scope call IS the batch call plus the painter: it runs jsdr_bpsk_batch_i16 / _f32 with the same arguments --
+ * every getter and the carried state come out bit for bit as the batch call leaves them -- and then, on the caller's stream, the
+ * scope passes over the frames of the call.  The painter's two spectra (:270-327) are not built; the tuned and ds rows are their
+ * inputs.
+ * Geometry: n the handle's frame, D = rate / 9600, L = n * 9600 / rate (Java's int arithmetic, :201: the length of the three
+ * short rings in pairs), frames = nsamples / n, row = s * frames + f for frame f of stream s, rows packed.  The decimated sample
+ * number g (the g-th RxDemodulate call since the origin, from 0) belongs to frame f when G_f <= g < G_{f+1}, G_f =
+ * (n_in + f n) / D - origin, n_in the samples the handle had taken before the call.  origin is 0 at creation;
+ * jsdr_bpsk_reconfigure is the reference's setup, which resets the ring indices (:198-204), and sets origin to the decimated
+ * samples taken so far.  jsdr_bpsk_restore leaves origin as it is, 0 on a fresh handle: the blob does not carry it, and a
+ * handle that adopts a blob counts its slots as if the saved stream had never been reconfigured.
+ * What the painter sees after frame f, all rings in slot order; each output may be NULL:
+ *   tuned_dev[row][n][2]  slot k: the pair RxDownSample received for the frame's sample k (:471-473): (i cosTab[..], q sinTab[..]),
+ *                         or (i, q) where tuPhase <= 0 (:388-396), from the call's own tuner schedule (after jsdr_bpsk_set_tuning too);
+ *   ds_dev[row][L][2]     downSmpl: slot g mod L holds the down-sampler output g after HOWARD_FUDGE_FACTOR (:486, :507-509); of
+ *                         the frame's g that share a slot the largest wins;
+ *   iq_dev[row][L][2]     demodIQ: slot (g + 1) mod L holds (fi, fq) of sample g (the index moves before the write, :529-531);
+ *                         again the largest g of the frame wins;
+ *   bits_dev[row][L]      demodBits: zero (:367-370), then for g ascending through the frame, at every detector instant with
+ *                         energy2 > 100.0, slot (g + 1) mod L takes +1 or -1 (:549-551); a later bit overwrites an earlier one,
+ *                         a later sample that is no bit does not clear it;
+ *   max_dev[row][2]       mi, mq of :232-238: from 0.0 under the strict mi < Math.abs(x); a NaN never wins;
+ *   pts_dev[row][L][4]    per slot, with xs = 100.0 / mi, ys = 100.0 / mq, rs = 50.0 / (mi * mq) (:239, :260): (int)(I * xs), the
+ *                         yellow x and the red trace; (int)(Q * ys), the yellow y; (int)(Q * xs), the blue trace (xs, as written,
+ *                         :256); (int)(demodRe[slot] * rs), the grey trace -- demodRe zeroed and marked like demodBits, holding di.
+ * (int) is Java's cast (truncates, saturates, NaN -> 0); every product and quotient is one IEEE double operation; mi == 0 gives
+ * xs = Infinity and 0 * Infinity = NaN -> 0, as in Java.  The window offsets (101 +, getHeight() - 301 -, xo + n / 2, * 50) are
+ * the caller's arithmetic.  With all six outputs NULL the call is the batch call and launches nothing more.
+ * jsdr_bpsk_scope_layout (host only) states L, origin and G_0 .. G_frames (g_first, cap entries of room, frames + 1 needed) for
+ * a call of nsamples from the handle's present counters; any of the three may be NULL.  It refuses what the scope calls refuse
+ * of the handle and of nsamples.
+ * Passes: "k_bpsk_scope_front" (tuned and ds: the input converted and mixed again with the call's tuner schedule, the 27 taps at
+ * the frame's decimated instants from the input history of before the call), "k_bpsk_scope_walk" (bits and pts: the bit clock of
+ * :533-593 again over the call's (fi, fq), from the clock state of before the call, which is copied on the device ahead of the
+ * call's own tail kernel, ordered by events, no host wait) and "k_bpsk_scope_pts" (iq, max, pts); jsdr_bpsk_scope_kernel joins
+ * what the last scope call launched with '+' ("" before the first and after a call with no output).  The scratch between the
+ * passes (the clock copy, the call's tuner index table) belongs to the handle: allocated at the first scope call that needs it,
+ * counted by jsdr_live_resources, gone with jsdr_bpsk_destroy.  A handle that makes no scope call allocates and launches what it
+ * did before.  Scope calls belong on one stream at a time, the stream of the handle's batch calls.
+ * Serves handles of jsdr_bpsk_create in the tune mode, JSDR_VARIANT_EXACT, any nstreams, int16 and float input, live
+ * jsdr_bpsk_set_tuning between calls, restored handles.
+ * JSDR_ERR before any device work, the handle unchanged, the message naming the reason: a null handle or input; nsamples not
+ * whole frames or outside (0, max_batch_samples]; the stride rules of the batch call; n_in not a multiple of n (the reference
+ * never paints such a state); L < 1; rate < 9600 (a frame does not refill the rings); do_fft set or a mode switch pending (in
+ * FFT-acquire `tuned` is the inverse transform's real part twice); every channel handle and tuned handle; the FAST variant; an
+ * output not aligned to its element size (tuned_dev: 16 bytes).  What only the batch call inside refuses (int16 input behind float
+ * frames whose last 26 samples no int16 holds) is refused after the scope's scratch exists and the clock copy is queued: the
+ * demodulator's state is unchanged, and nothing of the scope is launched. */
+int jsdr_bpsk_scope_i16(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stream_stride_i16, int64_t nsamples, int ic, int qc,
+                        double *tuned_dev, double *ds_dev, double *iq_dev, double *max_dev, int32_t *pts_dev, int8_t *bits_dev,
+                        void *stream);
+int jsdr_bpsk_scope_f32(jsdr_bpsk *h, const float *iq_in_dev, int64_t stream_stride_f32, int64_t nsamples,
+                        double *tuned_dev, double *ds_dev, double *iq_dev, double *max_dev, int32_t *pts_dev, int8_t *bits_dev,
+                        void *stream);
+int jsdr_bpsk_scope_layout(jsdr_bpsk *h, int64_t nsamples, int *ring_len, int64_t *origin, int64_t *g_first /* [frames + 1] */,
+                           int cap);                              /* host only */
+const char *jsdr_bpsk_scope_kernel(jsdr_bpsk *h);                 /* what the last scope call launched, joined with '+' */
 int jsdr_bpsk_set_cu_share(jsdr_bpsk *h, int wgs_per_cu); /* see jsdr_fft_set_cu_share; applies to the tune-mode front-end kernel */
 /* The library's own answer to "should fft.receive and this demodulator, fed the same batch on two streams, share the CUs?":
  * the shares to pass to jsdr_fft_set_cu_share / jsdr_bpsk_set_cu_share (2 and 1 where the split was measured to pay: the

@@ -46,13 +46,13 @@ def lib():
         _lib.jsdr_bpsk_profile_name.restype = C.c_char_p
         _lib.jsdr_demod_profile_name.restype = C.c_char_p
         for fn in ("jsdr_bpsk_front_kernel", "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel",
-                   "jsdr_fft_waterfall_kernel", "jsdr_phase_scope_kernel", "jsdr_demod_scope_kernel"):
+                   "jsdr_fft_waterfall_kernel", "jsdr_phase_scope_kernel", "jsdr_demod_scope_kernel", "jsdr_bpsk_scope_kernel"):
             getattr(_lib, fn).restype = C.c_char_p
             getattr(_lib, fn).argtypes = [C.c_void_p]
         for name in EXPORTED_SYMBOLS:
             if name not in ("jsdr_last_error", "jsdr_bpsk_profile_name", "jsdr_demod_profile_name", "jsdr_bpsk_front_kernel",
                             "jsdr_bpsk_tail_kernel", "jsdr_bpsk_fec_kernel", "jsdr_fft_kernel", "jsdr_fft_waterfall_kernel",
-                            "jsdr_phase_scope_kernel", "jsdr_demod_scope_kernel"):
+                            "jsdr_phase_scope_kernel", "jsdr_demod_scope_kernel", "jsdr_bpsk_scope_kernel"):
                 getattr(_lib, name).restype = C.c_int
     return _lib
 
@@ -575,6 +575,33 @@ class Bpsk:
         as batch_i16"""
         _check(lib().jsdr_bpsk_batch_f32(self.h, _addr(iq_dev), C.c_int64(stride_f32), C.c_int64(nsamples),
                                          C.c_void_p(stream)), "jsdr_bpsk_batch_f32")
+
+    # the scope (jsdr_hip.h "The BPSK scope over batches"): the batch call plus the painter's rings and first panel, a row per frame
+    def scope_i16(self, raw_dev, stride_i16, nsamples, ic=0, qc=0, tuned=None, ds=None, iq=None, max=None, pts=None, bits=None,
+                  stream=None):
+        """batch_i16, then per frame (row = s * frames + f) the outputs given: tuned f64 [rows][n][2], ds / iq f64 [rows][L][2],
+        max f64 [rows][2], pts i32 [rows][L][4], bits i8 [rows][L]; None passes NULL"""
+        _check(lib().jsdr_bpsk_scope_i16(self.h, _addr(raw_dev), C.c_int64(stride_i16), C.c_int64(nsamples), ic, qc, _addr(tuned),
+                                         _addr(ds), _addr(iq), _addr(max), _addr(pts), _addr(bits), C.c_void_p(stream)),
+               "jsdr_bpsk_scope_i16")
+
+    def scope_f32(self, iq_in_dev, stride_f32, nsamples, tuned=None, ds=None, iq=None, max=None, pts=None, bits=None, stream=None):
+        """batch_f32, then the outputs as scope_i16"""
+        _check(lib().jsdr_bpsk_scope_f32(self.h, _addr(iq_in_dev), C.c_int64(stride_f32), C.c_int64(nsamples), _addr(tuned), _addr(ds),
+                                         _addr(iq), _addr(max), _addr(pts), _addr(bits), C.c_void_p(stream)), "jsdr_bpsk_scope_f32")
+
+    def scope_layout(self, nsamples):
+        """(L, origin, G[frames + 1]) of a scope call of nsamples from the handle's present counters (host only)"""
+        frames = max(int(nsamples) // self.samples, 0)
+        ring, origin = C.c_int(), C.c_int64()
+        g = np.zeros(frames + 1, np.int64)
+        _check(lib().jsdr_bpsk_scope_layout(self.h, C.c_int64(nsamples), C.byref(ring), C.byref(origin), _addr(g), frames + 1),
+               "jsdr_bpsk_scope_layout")
+        return ring.value, origin.value, g
+
+    def scope_kernel(self):
+        """what the last scope call launched, joined with '+' ("" after a call with no output)"""
+        return lib().jsdr_bpsk_scope_kernel(self.h).decode()
 
     def is_recovered(self, stream):
         """fast variant: this stream is served by the exact shadow handle (jsdr_bpsk_recover_uncertified replayed it)"""

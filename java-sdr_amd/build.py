@@ -67,6 +67,8 @@ SOURCES = {
     # (checkpoints: the gather / scatter kernels do no arithmetic; the blob codec is host code only -- flagged like their neighbours)
     "bpsk_state.hip": ["-ffp-contract=off"],
     "bpsk_blob.hip": ["-ffp-contract=off"],
+    # (the BPSK scope: the painter's rings and integers, every product, sum and quotient one IEEE double operation; its host side with it)
+    "bpsk_scope.hip": ["-ffp-contract=off"],
     "group.hip": [],
 }
 

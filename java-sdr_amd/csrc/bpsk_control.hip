@@ -228,7 +228,9 @@ int jsdr_bpsk_reconfigure(jsdr_bpsk *h, double tuning_hz, int do_fft, int do_up)
         return chan_apply(h, -1, &tuning_hz, &up, false, "jsdr_bpsk_reconfigure", h->live_chan ? &fft : nullptr);
     }
     if (do_fft && !h->do_fft && fft_mode_alloc(h, fft_front_kind(h->nsf, h->decim, false), true) != JSDR_OK) return JSDR_ERR;
-    return live_apply(h, tuning_hz, do_fft != 0, do_up != 0, false);
+    if (live_apply(h, tuning_hz, do_fft != 0, do_up != 0, false) != JSDR_OK) return JSDR_ERR;
+    h->scope_origin = h->n_ds;  // setup() resets the debug rings' indices (:198-204): the scope counts its slots from here
+    return JSDR_OK;
 }
 
 int jsdr_bpsk_get_control(jsdr_bpsk *h, double *tuning_hz, int *do_fft, int *do_up)

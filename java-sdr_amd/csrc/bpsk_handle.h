@@ -8,6 +8,7 @@
 //   bpsk_results.hip    what a call left: the getters, the snapshot, profiling, the packed slots
 //   bpsk_control.hip    live control between calls: tuning, mode, per-stream tunings and tuning plans
 //   bpsk_ckpt.hip       checkpoints: jsdr_bpsk_save / jsdr_bpsk_restore
+// (bpsk_scope.hip, the painter's scope passes behind a batch call, holds its own kernels beside its host code.)
 // The kernels come in through the launch_* functions of bpsk_kernels.h, bpsk_fft.h, bpsk_chan.h, bpsk_pst.h and bpsk_fec.h.  The
 // handle fills their argument structs and calls the launchers, each stage of a call in ONE function that every kind of handle
 // (ordinary, channel, tuned) calls.
@@ -31,6 +32,7 @@
 #include "bpsk_sched.h"
 #include <atomic>
 #include <memory>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -266,6 +268,15 @@ struct jsdr_bpsk {
     std::vector<unsigned char> trace_void;   // [S] 1: restored since the last call -- the stream's last call is an empty one
     Event ev_state[2];                       // around the last k_state_pack / k_state_unpack launch (created at the first use)
     float state_pack_ms = -1.f, state_unpack_ms = -1.f;  // jsdr_bpsk_state_kernel_ms; -1: none yet
+    // the scope (jsdr_bpsk_scope_*, bpsk_scope.hip).  scope_origin: the decimated samples before the reference's ring indices were
+    // last reset (setup, :198-204: jsdr_bpsk_reconfigure); the rest is the scope passes' scratch, allocated at the first scope call
+    long long scope_origin = 0;
+    DevBuf<TailState> scope_tail0;               // [S] the tail state of before the call (the walk starts from it)
+    DevBuf<unsigned short> scope_k9;             // [26 + max_batch] the call's 9-bit tuner indices (expand_k9)
+    std::vector<unsigned short> scope_h_k9;
+    Event scope_ev_copy, scope_ev_walk;          // side stream -> caller's: the copy is made; caller's -> side: the walk has read it
+    bool scope_walk_pending = false;
+    std::string scope_name;                      // jsdr_bpsk_scope_kernel
 };
 
 namespace jsdr {
