@@ -54,6 +54,13 @@ SOURCES = {
     "bpsk_call_pst.hip": ["-ffp-contract=off"],
     # (the host scheduler: host code only, it steps the reference's phase recurrences in doubles that must round as Java's do)
     "bpsk_sched.hip": ["-ffp-contract=off"],
+    # (the demod handle's units, demod_handle.h: host code only; the weights and the carrier phases are floats that must round as Java's do)
+    # (demod_call.hip holds the carrier walk, a 7-instruction loop that has to retire one float subtraction's latency an iteration:
+    #  kept inside one 32-byte fetch block wherever the unit lands in the library)
+    "demod_call.hip": ["-ffp-contract=off", "-falign-loops=32"],
+    "demod_control.hip": ["-ffp-contract=off"],
+    "demod_scope_host.hip": ["-ffp-contract=off"],
+    "demod_host.hip": ["-ffp-contract=off"],
     "bpsk_fft.hip": ["-ffp-contract=off"],
     # (no atomic optimiser: it turns the one-lane ticket atomicAdd into atomic + s_waitcnt vmcnt(0) + v_readfirstlane on the spot,
     #  i.e. a round trip to memory at the top of a frame for a value that is wanted a pass later)

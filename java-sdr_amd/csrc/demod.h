@@ -1,4 +1,6 @@
-// demod.h -- what demod.hip (the ordinary handle and its kernels) and demod_chan.hip (the channel handle's kernels) share.
+// demod.h -- the demod.java chain's constants and kernel arguments, and the launchers of its three kernel units: demod.hip
+// (the ordinary handle's kernels), demod_chan.hip (the channel handles') and demod_scope.hip (the scope's).  The handle's
+// host units (demod_handle.h) reach the kernels through these.
 #pragma once
 #include "common.h"
 
@@ -27,6 +29,20 @@ __device__ __forceinline__ int demod_f2i(float v)
 
 // (short)(sam * 32767f) to both channels (:478-481): the low half of the int, twice
 __device__ __forceinline__ int demod_lr(float x) { const int sv = demod_f2i(x * 32767.0f); return (int)__builtin_amdgcn_perm((unsigned)sv, (unsigned)sv, 0x01000100u); }
+
+// ---- the ordinary handle's kernels (demod.hip)
+struct DemodArgs;  // demod_dev.h
+// k_demod_fused (fused: every mode but AM, frames of up to 5 tiles -- raw samples to int16 audio at out, the frames' (max, avg)
+// to stats) or k_demod_front (one tile per workgroup to a.d, a.fmax_bits zeroed before)
+int launch_demod_front(const DemodArgs &a, bool f32in, bool fused, int nstreams, int *out, long long out_stride_pairs,
+                       float *stats, hipStream_t st);
+int launch_demod_state(const DemodArgs &a, bool f32in, float2 *hist_new, float2 *lilq_new, int nstreams, hipStream_t st);
+// the unfused form's second pass: a.d, a.fmax_bits and favg (k_demod_mean's, AM) to int16 audio
+int launch_demod_out(const DemodArgs &a, int nstreams, const float *favg, int *out, long long out_stride_pairs, float *stats,
+                     hipStream_t st);
+// both kinds of handle: (cos, sin) of n carrier phases; the AM mean of nframes_total frames of n floats in rows of L
+int launch_demod_nco(const float *car, long long n, float2 *nco, hipStream_t st);
+int launch_demod_mean(const float *d, long long L, int n, int nfr, long long nframes_total, float *favg, hipStream_t st);
 
 // ---- channel handles (jsdr_demod_create_channels): ninputs x K receivers, channel c of input i is stream i * K + c
 enum { DCHAN_MAX = 16 };
@@ -67,7 +83,6 @@ int launch_demod_chan_state(const DemodChanArgs &a, bool f32in, float2 *hist_new
 int launch_demod_chan_out(const DemodChanArgs &a, int drows, const float *favg, hipStream_t st);
 
 // ---- the demod scope (jsdr_demod_scope_*, demod_scope.hip): demod.paintComponent's trace and spectrum (:509-558) per frame
-struct DemodArgs;  // demod_dev.h
 constexpr int DSCOPE_WIDTH_MAX = 32768;
 constexpr size_t DSCOPE_SCRATCH_BYTES = (size_t)64 << 20;  // the handle's rows of one pass: dbg, final floats and PSD together
 

@@ -132,6 +132,32 @@ def test_one_channel_handle_equals_an_ordinary_handle():
         assert lib.jsdr_demod_configure_channel(od.h, 1, 1, 0, 0, 0) != 0
 
 
+def test_an_ordinary_handle_through_the_channel_form_calls():
+    """configure_channel(0) / channel_weights(0) on an ordinary handle are configure / weights: the same audio, byte for byte, the
+    same controls and state through either form of getter; channel 1 is refused and nothing of the handle moves"""
+    rate, n, S, nf = 96000, 64, 2, 2
+    CH = J.DemodChannels  # (its per-channel methods take any demod handle)
+    raws = signals(9, S, 2 * nf * n, rate)
+    a, b = J.Demod(rate, n, S, nf * n), J.Demod(rate, n, S, nf * n)
+    a.configure(3, 1, 1, 0)
+    CH.configure_channel(b, 0, 3, 1, 1, 0)
+    (wa, pa), (wb, pb) = a.weights(3000, 11000), CH.channel_weights(b, 0, 3000, 11000)
+    assert wa.tobytes() == wb.tobytes() and pa == pb and pa != 0
+    for k in range(2):
+        chunk = np.stack([r[2 * k * nf * n:2 * (k + 1) * nf * n] for r in raws])
+        got_a, got_b = a.batch_host_i16(chunk, nf * n), b.batch_host_i16(chunk, nf * n)
+        assert got_a.tobytes() == got_b.tobytes() and got_a.any(), k
+        assert CH.channel_control(b, 0) == CH.channel_control(a, 0) == (3, 1, 1, 0, 3000, 11000)
+        assert CH.channel_state(b, 0) == b.state() == a.state() == CH.channel_state(a, 0), k
+        assert b.state()[0] != 0  # (the carrier has moved: the state compared is not the initial one)
+    before = (CH.channel_control(b, 0), b.state())
+    for refused in (lambda: CH.configure_channel(b, 1, 1, 0, 0, 0), lambda: CH.channel_weights(b, 1, 0, 5000),
+                    lambda: CH.channel_control(b, 1), lambda: CH.channel_state(b, 1), lambda: CH.configure_channel(b, -1, 1, 0, 0, 0)):
+        with pytest.raises(J.JsdrError, match="channel -?1 outside 0..0"):
+            refused()
+    assert (CH.channel_control(b, 0), b.state()) == before and CH.channel_info(b) == (S, 1)
+
+
 def test_live_per_channel_control_between_calls():
     """configure_channel on one channel, filterMove steps applied with channel_weights, the all-pass impulse on one channel,
     then a handle-wide configure / weights; the channels no action touched stay equal to their own oracles"""
