@@ -66,8 +66,13 @@ SOURCES = {
     #  i.e. a round trip to memory at the top of a frame for a value that is wanted a pass later)
     "bpsk_acq.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
     "bpsk_acq_chan.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"],
+    # (the mixed-radix front ends, cut by kernel family over bpsk_fftm_dev.h's passes)
     "bpsk_fftm.hip": ["-ffp-contract=off"],
+    "bpsk_fft2x.hip": ["-ffp-contract=off"],
+    "bpsk_fftm2.hip": ["-ffp-contract=off"],
     "bpsk_acqg.hip": ["-ffp-contract=off"],
+    # (the FFT-acquire plan: host code only; its twiddle tables are long doubles rounded once -- flagged like its neighbours)
+    "bpsk_fftplan.hip": ["-ffp-contract=off"],
     "bpsk_chan.hip": ["-ffp-contract=off"],
     "bpsk_pst.hip": ["-ffp-contract=off"],
     "bpsk_chan_pst.hip": ["-ffp-contract=off"],

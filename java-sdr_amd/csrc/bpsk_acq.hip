@@ -23,7 +23,7 @@
 //     t = w*b (tr = wr*br - wi*bi, ti = wr*bi + wi*br), a' = a + t, b' = a - t
 // only the grouping of the stages into passes differs -- spectra, centre bins and everything downstream are bit-identical
 // to the oracle and to k_front_fft (which keeps serving calls of ONE frame per stream: a live receive()).
-#include "bpsk_fft.h"
+#include "bpsk_fftplan.h"
 #include "bpsk_acq_dev.h"
 #include <math.h>
 
@@ -840,7 +840,7 @@ int g_acq_last_grid[4] = {0, 0, 0, 0};
 
 // The call's frames in launches of at most chunk_frames per stream (the scratch holds S * chunk_frames frames)
 // the default mixed-radix frames: k_acqm_fwd / k_acqm_inv (bpsk_fftm.hip) around the same scan and edges
-static int launch_acq3_m(AcqArgs &a, const FftFrontArgs &fa, const AcqmPlan &plan, int num_cu, hipStream_t st, const AcqProf &prof,
+static int launch_acq3_m(AcqArgs &a, const FftFrontArgs &fa, const FftPlan &plan, int num_cu, hipStream_t st, const AcqProf &prof,
                          int parts = ACQ_PARTS_ALL)
 {
     auto mark = [&](int phase, bool begin) {
@@ -849,7 +849,7 @@ static int launch_acq3_m(AcqArgs &a, const FftFrontArgs &fa, const AcqmPlan &pla
     JSDR_HIP_TRY(hipMemsetAsync(a.tickets, 0, 2 * sizeof(unsigned), st));
     if (parts & ACQ_PART_FWD) {
         mark(0, true);
-        if (launch_acqm(a, fa, plan.np, plan.rad, plan.tw_off, plan.wr_off, num_cu, 0, st) != JSDR_OK) return JSDR_ERR;
+        if (launch_acqm(a, fa, plan, num_cu, 0, st) != JSDR_OK) return JSDR_ERR;
         mark(0, false);
     }
     if (parts & ACQ_PART_SCAN) {
@@ -860,7 +860,7 @@ static int launch_acq3_m(AcqArgs &a, const FftFrontArgs &fa, const AcqmPlan &pla
     }
     if (parts & ACQ_PART_INV) {
         mark(2, true);
-        if (launch_acqm(a, fa, plan.np, plan.rad, plan.tw_off, plan.wr_off, num_cu, 1, st) != JSDR_OK) return JSDR_ERR;
+        if (launch_acqm(a, fa, plan, num_cu, 1, st) != JSDR_OK) return JSDR_ERR;
         mark(2, false);
     }
     if (parts & ACQ_PART_EDGES) {
@@ -873,7 +873,7 @@ static int launch_acq3_m(AcqArgs &a, const FftFrontArgs &fa, const AcqmPlan &pla
 }
 
 // any other frame: the passes of bpsk_acqg.hip around the same scan and edges
-static int launch_acq3_g(AcqArgs &a, const AcqgPlan &gen, double2 *img, hipStream_t st, const AcqProf &prof, int parts = ACQ_PARTS_ALL)
+static int launch_acq3_g(AcqArgs &a, const FftPlan &gen, double2 *img, hipStream_t st, const AcqProf &prof, int parts = ACQ_PARTS_ALL)
 {
     auto mark = [&](int phase, bool begin) {
         if (prof.mark) prof.mark(prof.ctx, phase, begin, st);
@@ -909,10 +909,10 @@ void acq3_row_layout(int n, int do_up, int *nsb, int *na) { acq3_layout(n, do_up
 
 // some of the four phases of ONE launch over the a.S x a.F frames of `a` (the channel handle's front end, bpsk_acq_chan.hip: the
 // forward phase over the inputs, scan / inverse / edges over the streams of one channel), with the kernels of the frame size
-int launch_acq3_parts(AcqArgs &a, const FftFrontArgs &fa, int parts, int num_cu, hipStream_t st, const AcqProf &prof, const AcqmPlan &plan,
-                      const AcqgPlan *gen, double2 *img)
+int launch_acq3_parts(AcqArgs &a, const FftFrontArgs &fa, int parts, int num_cu, hipStream_t st, const AcqProf &prof, const FftPlan &plan,
+                      double2 *img)
 {
-    if (gen != nullptr && gen->on) return launch_acq3_g(a, *gen, img, st, prof, parts);
+    if (plan.kind == FRONT_GEN) return launch_acq3_g(a, plan, img, st, prof, parts);
     if (acqm_supported(fa.n)) return launch_acq3_m(a, fa, plan, num_cu, st, prof, parts);
     JSDR_REQUIRE(acq3_supported(fa.n), "bpsk: the three-phase FFT-acquire front end does not take frames of %d samples", fa.n);
     switch (fa.logn) {
@@ -924,9 +924,9 @@ int launch_acq3_parts(AcqArgs &a, const FftFrontArgs &fa, int parts, int num_cu,
 }
 
 int launch_acq3(const FftFrontArgs &fa, int nstreams, unsigned char *scratch, size_t scratch_bytes, int chunk_frames, int num_cu,
-                hipStream_t st, const AcqProf &prof, const AcqmPlan &plan, const AcqgPlan *gen)
+                hipStream_t st, const AcqProf &prof, const FftPlan &plan)
 {
-    const bool generic = gen != nullptr && gen->on;
+    const bool generic = plan.kind == FRONT_GEN;
     JSDR_REQUIRE(generic || acq3_supported(fa.n), "bpsk: the three-phase FFT-acquire front end takes frames of 1024 .. 8192 samples (2^k) or 9600 / 4800 / 4410, not %d", fa.n);
     int nsb, na;
     acq3_layout(fa.n, fa.do_up, &nsb, &na);
@@ -976,7 +976,7 @@ int launch_acq3(const FftFrontArgs &fa, int nstreams, unsigned char *scratch, si
         a.F = fa.nframes - f0 < chunk_frames ? fa.nframes - f0 : chunk_frames;
         int rc;
         if (generic) {
-            rc = launch_acq3_g(a, *gen, img, st, prof);
+            rc = launch_acq3_g(a, plan, img, st, prof);
             if (rc != JSDR_OK) return rc;
             continue;
         }

@@ -22,6 +22,7 @@
 // 16 points a thread, LDS-only barriers, in-order requests, tickets -- with the last stage formed for bins [0, n/2 + 28) and the
 // boxcar run once per band over the one |X| image.
 #include "bpsk_acq_dev.h"
+#include "bpsk_fftplan.h"
 
 namespace jsdr {
 
@@ -328,9 +329,9 @@ static int launch_acqc_fwd_t(AcqcFwdArgs &ca, int num_cu, hipStream_t st)
 }
 
 int launch_acq3_chan(const FftFrontArgs &fa, AcqChanArgs &ca, unsigned char *scratch, size_t scratch_bytes, int chunk_frames, int num_cu,
-                     hipStream_t st, const AcqProf &prof, const AcqmPlan &plan, const AcqgPlan *gen)
+                     hipStream_t st, const AcqProf &prof, const FftPlan &plan)
 {
-    const bool generic = gen != nullptr && gen->on;
+    const bool generic = plan.kind == FRONT_GEN;
     const int n = fa.n;
     JSDR_REQUIRE(generic || acq3_supported(n), "bpsk channels: no FFT-acquire front end for frames of %d samples", n);
     JSDR_REQUIRE(ca.nfft >= 1 && ca.nfft <= 16 && ca.nin >= 1 && (fa.raw != nullptr) != (fa.rawf != nullptr), "bpsk channels: internal: bad FFT-acquire channel set");
@@ -430,7 +431,7 @@ int launch_acq3_chan(const FftFrontArgs &fa, AcqChanArgs &ca, unsigned char *scr
             for (int u = 0; u < 2; u++) {
                 if (!(mask & (1 << u))) continue;
                 band(u);
-                if (launch_acq3_parts(a, fa, ACQ_PART_FWD, num_cu, st, prof, plan, gen, img) != JSDR_OK) return JSDR_ERR;
+                if (launch_acq3_parts(a, fa, ACQ_PART_FWD, num_cu, st, prof, plan, img) != JSDR_OK) return JSDR_ERR;
                 ca.fwd_frames += (long long)a.S * a.F;
             }
         }
@@ -446,10 +447,10 @@ int launch_acq3_chan(const FftFrontArgs &fa, AcqChanArgs &ca, unsigned char *scr
                 // ... but the SCAN's band is the channel's own
                 AcqArgs sc = a;
                 sc.do_up = 1;
-                if (launch_acq3_parts(sc, fa, ACQ_PART_SCAN, num_cu, st, prof, plan, gen, img) != JSDR_OK) return JSDR_ERR;
-                if (launch_acq3_parts(a, fa, ACQ_PART_INV | ACQ_PART_EDGES, num_cu, st, prof, plan, gen, img) != JSDR_OK) return JSDR_ERR;
+                if (launch_acq3_parts(sc, fa, ACQ_PART_SCAN, num_cu, st, prof, plan, img) != JSDR_OK) return JSDR_ERR;
+                if (launch_acq3_parts(a, fa, ACQ_PART_INV | ACQ_PART_EDGES, num_cu, st, prof, plan, img) != JSDR_OK) return JSDR_ERR;
             } else {
-                if (launch_acq3_parts(a, fa, ACQ_PART_SCAN | ACQ_PART_INV | ACQ_PART_EDGES, num_cu, st, prof, plan, gen, img) != JSDR_OK)
+                if (launch_acq3_parts(a, fa, ACQ_PART_SCAN | ACQ_PART_INV | ACQ_PART_EDGES, num_cu, st, prof, plan, img) != JSDR_OK)
                     return JSDR_ERR;
             }
             ca.inv_frames += (long long)a.S * a.F;

@@ -1,6 +1,6 @@
 // bpsk_acq_rule.h -- the scalar arithmetic of doBufferFFT (FUNcubeBPSKDemod.java:399-456) around its transforms, each stated
 // once for the host and the device: the averaging factors, the searched band, the first-maximum search, the centre-bin rule
-// and the first RxDownSample output of a frame.  Every FFT-acquire kernel (bpsk_fft.hip, bpsk_fftm.hip, bpsk_acq.hip,
+// and the first RxDownSample output of a frame.  Every FFT-acquire kernel (bpsk_fft.hip, bpsk_fftm.hip, bpsk_fft2x.hip, bpsk_acq.hip,
 // bpsk_acq_chan.hip, bpsk_acqg.hip) steps them through these functions; tests/tools/acq_rule_driver.hip runs them on the host.
 //
 // No HIP call.  Every unit that includes this is compiled with -ffp-contract=off: each operation rounds by itself, as Java's do.

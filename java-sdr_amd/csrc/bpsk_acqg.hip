@@ -2,7 +2,7 @@
 //
 // JTransforms takes any n (:194, :422-423) and a frame is a tenth of a second of any audio-rate (JavaAudio.java:49,58-59).  The LDS
 // front ends hold a frame as a double2 image in ONE workgroup's LDS: powers of two 1024 .. 8192 (bpsk_fft.hip / bpsk_acq.hip), any
-// other frame of 416 .. 9600 samples (bpsk_fftm.hip), twice a 16 | m, 2^a 3^b 5^c frame (19200).  Every other frame the oracle
+// other frame of 416 .. 9600 samples (bpsk_fftm.hip), twice a 16 | m, 2^a 3^b 5^c frame (19200, bpsk_fft2x.hip).  Every other frame the oracle
 // defines comes here: powers of two below 1024 and above 8192, 17640 (176.4 kHz: 2 x 8820, 7^2 | 8820), 38400 (384 kHz), any
 // frame above 9600 samples, and the LDS front ends' frames at decimations they do not take (a 2^k frame below 38.4 kHz).
 //
@@ -14,7 +14,7 @@
 // prime radix above 7 as the DFT's definition; inverse = conj o forward o conj) -- so centre bins, traces, bits and FEC bytes are
 // bit-identical to the oracle's.  A pass is a round trip through HBM (32 bytes a point): a correctness path for rare rates, ~10x
 // the LDS kernels' time per sample; the scan (k_acq_scan) and the windows across frame borders (k_acq_edges) are shared.
-#include "bpsk_fft.h"
+#include "bpsk_fftplan.h"
 #include "bpsk_radix.h"
 #include <math.h>
 
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(AG_T) void k_acqg_pass(const double2 *in, double2 *
 // TWO consecutive Stockham passes (radix R1 at stride P, then R2 at stride P R1) in one round trip through memory: group g = m0 P + k1
 // holds the R1 R2 points both passes connect -- the R2 first-pass butterflies b1 = g + j2 n/(R1 R2), whose outputs q1 feed the R1
 // second-pass butterflies (k2 = k1 + q1 P), which write out[(g - k1) R1 R2 + k1 + q1 P + q2 P R1].  The operations of
-// k_acqg_pass<R1> followed by k_acqg_pass<R2> on the same operands in the same order (bpsk_fftm.hip's fm_pass2, out of place).
+// k_acqg_pass<R1> followed by k_acqg_pass<R2> on the same operands in the same order (bpsk_fftm_dev.h's fm_pass2, out of place).
 template <int R1, int R2>
 __global__ __launch_bounds__(AG_T) void k_acqg_pass2(const double2 *in, double2 *out, int n, int P, const double2 *tw1, const double2 *tw2, int bpf)
 {
@@ -277,94 +277,8 @@ __global__ __launch_bounds__(AG_T) void k_acqg_rx(AcqArgs a, const double2 *img,
 }
 
 // ============================================================================================================= host
-// the oracle's jo_fft_mixed_radices (o_fft.c:151-171), frames above 9600 samples starting with one radix-2 pass
-static int acqg_radices(int n, int *rad)
-{
-    int c = 0;
-    if (n < 2) return 0;
-    if (n > 9600 && n % 2 == 0) {
-        rad[c++] = 2;
-        n /= 2;
-    }
-    while (n % 4 == 0 && c < ACQG_MAXPASS) {
-        rad[c++] = 4;
-        n /= 4;
-    }
-    if (n % 2 == 0 && c < ACQG_MAXPASS) {
-        rad[c++] = 2;
-        n /= 2;
-    }
-    for (int p = 3; p <= 7; p += 2)
-        while (n % p == 0 && c < ACQG_MAXPASS) {
-            rad[c++] = p;
-            n /= p;
-        }
-    for (int p = 11; n > 1 && c < ACQG_MAXPASS; p += 2) {
-        if (p * p > n) p = n;
-        while (n % p == 0 && c < ACQG_MAXPASS) {
-            rad[c++] = p;
-            n /= p;
-        }
-    }
-    return n == 1 ? c : 0;
-}
-
-bool acqg_supported(int n)
-{
-    // below 416 samples the 204 gathered bins do not end inside the frame (the reference's own arraycopy would throw); the image
-    // index arithmetic of the kernels is 32-bit within a frame
-    if (n < 416 || n > (1 << 22)) return false;
-    if ((n & (n - 1)) == 0) return true;
-    int rad[ACQG_MAXPASS];
-    const int np = acqg_radices(n, rad);
-    if (np <= 0) return false;
-    // a prime radix r above 7 is a pass of n r complex multiply-adds (one thread per output, r terms each): bounded, so that a frame
-    // with a huge prime factor is refused at create instead of occupying the GPU for minutes per call
-    for (int p = 0; p < np; p++)
-        if (rad[p] > 7 && (long long)n * rad[p] > (1LL << 31)) return false;
-    return true;
-}
-
-// images of a frame in the launch's scratch: a power of two is transformed in place, the Stockham passes go between two
-size_t acqg_image_bytes(int n) { return sizeof(double2) * (size_t)n * (((n & (n - 1)) == 0) ? 1 : 2); }
-
-void acqg_twiddles(std::vector<double2> &w, int n, AcqgPlan *plan)
-{
-    plan->on = true;
-    plan->logn = 0;
-    plan->np = 0;
-    if ((n & (n - 1)) == 0) {
-        while ((1 << plan->logn) < n) plan->logn++;
-        fft_twiddles_f64(w, n);
-        return;
-    }
-    plan->np = acqg_radices(n, plan->rad);
-    w.clear();
-    auto table = [&](int len) {  // jo_fft_mixed_table: long double + one rounding, exact on the axes
-        const size_t o = w.size();
-        w.resize(o + (size_t)len);
-        for (int m = 0; m < len; m++) {
-            const long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)m / (long double)len;
-            w[o + m] = make_double2((double)cosl(ang), (double)(-sinl(ang)));
-        }
-        w[o] = make_double2(1.0, -0.0);
-        if (len % 4 == 0) {
-            w[o + len / 4] = make_double2(0.0, -1.0);
-            w[o + 3 * len / 4] = make_double2(-0.0, 1.0);
-        }
-        if (len % 2 == 0) w[o + len / 2] = make_double2(-1.0, -0.0);
-        return (int)o;
-    };
-    int P = 1;
-    for (int p = 0; p < plan->np; p++) {
-        plan->tw_off[p] = table(P * plan->rad[p]);
-        P *= plan->rad[p];
-    }
-    for (int p = 0; p < plan->np; p++) plan->wr_off[p] = plan->rad[p] > 7 ? table(plan->rad[p]) : 0;
-}
-
 // the transform of every frame of the launch: img0 -> wherever the last pass leaves it (returned)
-static double2 *acqg_transform(const AcqgPlan &pl, const double2 *tw, double2 *img0, double2 *img1, int n, long long nfr, bool inverse,
+static double2 *acqg_transform(const FftPlan &pl, const double2 *tw, double2 *img0, double2 *img1, int n, long long nfr, bool inverse,
                                hipStream_t st, int *rc)
 {
     *rc = JSDR_OK;
@@ -445,7 +359,7 @@ static double2 *acqg_transform(const AcqgPlan &pl, const double2 *tw, double2 *i
 
 // phase A (which == 0) or phase C (which == 1) of one launch of the three-phase front end; img: the launch's images (S F frames of
 // acqg_image_bytes(n))
-int launch_acqg(const AcqArgs &a, const AcqgPlan &pl, double2 *img, int which, hipStream_t st)
+int launch_acqg(const AcqArgs &a, const FftPlan &pl, double2 *img, int which, hipStream_t st)
 {
     const int n = a.n;
     const long long nfr = (long long)a.S * a.F;

@@ -288,10 +288,6 @@ FftFrontArgs jsdr::fft_front_args(jsdr_bpsk *h, const int *raw, const float2 *ra
 
 void jsdr::acq_launch_ctx(jsdr_bpsk *h, AcqLaunchCtx &c)
 {
-    c.plan.np = h->fm_np;
-    c.plan.rad = h->fm_rad;
-    c.plan.tw_off = h->fm_off;
-    c.plan.wr_off = h->fm_off1;
     c.pc.h = h;
     c.prof.ctx = &c.pc;
     c.prof.mark = acq_prof_mark;
@@ -503,10 +499,11 @@ static int fft_front(jsdr_bpsk *h, FftFrontArgs &xa, long long L, hipStream_t st
     // the default mixed-radix frames' are the fused kernel's passes cut in two and cost 10-14 % more per frame at a full grid
     // (9600: 12.6 against 11.5 ms; the spectrum rows' round trip, a ticket a frame) -- they are taken where frames fill the
     // chip better than streams: ceil(S F / W) * 1.15 < ceil(S / W) * F, W = the workgroups the chip holds (one a CU).
-    bool three = !h->fft_2x && acq3_supported(h->nsf) && h->acq_mode != 0 && (xa.nframes >= 2 || h->acq_mode == 1) &&
+    const FftFront kind = h->fft_plan.kind;
+    bool three = kind != FRONT_FFT2X && acq3_supported(h->nsf) && h->acq_mode != 0 && (xa.nframes >= 2 || h->acq_mode == 1) &&
                  L < 0x7fffffffLL && (long long)S * ((xa.nframes + 1) / 2) < 0x7fffffffLL;  // (its kernels' 32-bit frame arithmetic)
-    if (h->gen_plan.on) three = true;  // (no fused kernel exists for these frames)
-    if (three && h->fft_mixed && h->acq_mode < 0) {
+    if (kind == FRONT_GEN) three = true;  // (no fused kernel exists for these frames)
+    if (three && kind == FRONT_FFTM && h->acq_mode < 0) {
         if (!device_cus(h)) return JSDR_ERR;
         const long long W = h->num_cu, F = xa.nframes;
         // (4800 / 4410: the fused kernel takes two frames at once and is 1.38 / 1.27 x the three-phase kernels' pace at a full grid)
@@ -514,17 +511,17 @@ static int fft_front(jsdr_bpsk *h, FftFrontArgs &xa, long long L, hipStream_t st
         three = (double)(((long long)S * F + W - 1) / W) * pace < (double)((((long long)S + W - 1) / W) * F);
     }
     if (three) {
-        const size_t per = acq3_frame_bytes(h->nsf, h->do_up) + 64 + (h->gen_plan.on ? acqg_image_bytes(h->nsf) : 0);
+        const size_t per = acq3_frame_bytes(h->nsf, h->do_up) + 64 + (kind == FRONT_GEN ? acqg_image_bytes(h->nsf) : 0);
         if (acq_scratch_ensure(h, per, (size_t)S, 512) != JSDR_OK) return JSDR_ERR;  // (per stream and frame)
-        h->front_name = h->gen_plan.on ? "k_acqg_pass" : h->fft_mixed ? "k_acqm_fwd" : "k_acq_fwd";
+        h->front_name = kind == FRONT_GEN ? "k_acqg_pass" : kind == FRONT_FFTM ? "k_acqm_fwd" : "k_acq_fwd";
         AcqLaunchCtx lc;
         acq_launch_ctx(h, lc);
-        if (launch_acq3(xa, S, h->acq_scratch.p, h->acq_scratch.n, h->acq_chunk, h->num_cu, st, lc.prof, lc.plan, &h->gen_plan) != JSDR_OK) return JSDR_ERR;
+        if (launch_acq3(xa, S, h->acq_scratch.p, h->acq_scratch.n, h->acq_chunk, h->num_cu, st, lc.prof, h->fft_plan) != JSDR_OK) return JSDR_ERR;
     } else {
         ProfScope ps(h, PK_FRONT, st);
-        h->front_name = h->fft_2x ? "k_front_fft2x" : (h->fft_mixed ? (fftm_pairs(xa.n, xa.nframes) ? "k_front_fftm2" : "k_front_fftm") : "k_front_fft");
-        const int frc = h->fft_2x ? launch_front_fft2x(xa, h->fm_np, h->fm_rad, h->fm_off, h->fm_off1, h->fft2x_ek.p, h->fft2x_r0.p, S, st)
-                                  : (h->fft_mixed ? launch_front_fftm(xa, h->fm_np, h->fm_rad, h->fm_off, h->fm_off1, h->fft2x_ek.p, S, st) : launch_front_fft(xa, S, st));
+        h->front_name = kind == FRONT_FFT2X ? "k_front_fft2x" : (kind == FRONT_FFTM ? (fftm_pairs(xa.n, xa.nframes) ? "k_front_fftm2" : "k_front_fftm") : "k_front_fft");
+        const int frc = kind == FRONT_FFT2X ? launch_front_fft2x(xa, h->fft_plan, h->fft2x_ek.p, h->fft2x_r0.p, S, st)
+                                         : (kind == FRONT_FFTM ? launch_front_fftm(xa, h->fft_plan, h->fft2x_ek.p, S, st) : launch_front_fft(xa, S, st));
         if (frc != JSDR_OK) return JSDR_ERR;
     }
     return JSDR_OK;

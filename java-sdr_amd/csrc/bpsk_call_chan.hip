@@ -61,7 +61,7 @@ static bool chan_cb_foreign(const jsdr_bpsk *h, int c)
 
 static bool chan_fused_ok(const jsdr_bpsk *h)
 {
-    return !h->gen_plan.on && fft_front_kind(h->nsf, h->decim, false, -1) == fft_front_kind(h->nsf, h->decim, true, -1);
+    return h->fft_plan.kind != FRONT_GEN && fft_front_kind(h->nsf, h->decim, false, -1) == fft_front_kind(h->nsf, h->decim, true, -1);
 }
 
 static int chan_fused_front(jsdr_bpsk *h, const FftFrontArgs &xa, int c, bool names_call, bool hist_float, hipStream_t st)
@@ -74,10 +74,10 @@ static int chan_fused_front(jsdr_bpsk *h, const FftFrontArgs &xa, int c, bool na
     x1.dm = h->dm.p + (long long)c * h->dm_stride;
     x1.dm_stride = h->dm_stride * h->nch;
     x1.phase_clk = nullptr;
+    const FftFront kind = h->fft_plan.kind;
     auto front = [&](const FftFrontArgs &x) {
-        return h->fft_2x ? launch_front_fft2x(x, h->fm_np, h->fm_rad, h->fm_off, h->fm_off1, h->fft2x_ek.p, h->fft2x_r0.p, S, st)
-                         : (h->fft_mixed ? launch_front_fftm(x, h->fm_np, h->fm_rad, h->fm_off, h->fm_off1, h->fft2x_ek.p, S, st)
-                                         : launch_front_fft(x, S, st));
+        return kind == FRONT_FFT2X ? launch_front_fft2x(x, h->fft_plan, h->fft2x_ek.p, h->fft2x_r0.p, S, st)
+                                   : (kind == FRONT_FFTM ? launch_front_fftm(x, h->fft_plan, h->fft2x_ek.p, S, st) : launch_front_fft(x, S, st));
     };
     const bool seam = cc.seam == SEAM_TO_FFT;
     if (seam) {
@@ -95,7 +95,7 @@ static int chan_fused_front(jsdr_bpsk *h, const FftFrontArgs &xa, int c, bool na
     }
     {
         ProfScope ps(h, PK_FRONT, st);
-        const char *name = h->fft_2x ? "k_front_fft2x" : (h->fft_mixed ? (fftm_pairs(x1.n, x1.nframes) ? "k_front_fftm2" : "k_front_fftm") : "k_front_fft");
+        const char *name = kind == FRONT_FFT2X ? "k_front_fft2x" : (kind == FRONT_FFTM ? (fftm_pairs(x1.n, x1.nframes) ? "k_front_fftm2" : "k_front_fftm") : "k_front_fft");
         if (names_call) h->front_name = name;  // (no three-phase launch ran in the call)
         if (front(x1) != JSDR_OK) return JSDR_ERR;
         if (seam) {
@@ -149,7 +149,7 @@ int jsdr::chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
         // the one step of the call that can fail for want of memory comes before anything of the handle has moved on
         const int mask = chan_band_mask(h);
         // (per INPUT and frame)
-        if (acq_scratch_ensure(h, acq3c_frame_bytes(h->nsf, mask, h->gen_plan.on), (size_t)h->nin, 4096) != JSDR_OK) return JSDR_ERR;
+        if (acq_scratch_ensure(h, acq3c_frame_bytes(h->nsf, mask, h->fft_plan.kind == FRONT_GEN), (size_t)h->nin, 4096) != JSDR_OK) return JSDR_ERR;
         h->acq_mask = mask;
     }
     // the inputs' 26-sample history in the form of this call's input (only the tune-mode channels read it; a channel on its first
@@ -229,7 +229,7 @@ int jsdr::chan_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, 
         AcqLaunchCtx lc;
         acq_launch_ctx(h, lc);
         if (ca.nfft > 0 &&
-            launch_acq3_chan(xa, ca, h->acq_scratch.p, h->acq_scratch.n, h->acq_chunk, device_cus(h), st, lc.prof, lc.plan, &h->gen_plan) != JSDR_OK)
+            launch_acq3_chan(xa, ca, h->acq_scratch.p, h->acq_scratch.n, h->acq_chunk, device_cus(h), st, lc.prof, h->fft_plan) != JSDR_OK)
             return JSDR_ERR;
         h->acq_fwd_frames = ca.fwd_frames;
         h->acq_inv_frames = ca.inv_frames;

@@ -39,7 +39,7 @@ static int live_apply(jsdr_bpsk *h, double tuning, int do_fft, int do_up, bool z
     if (h->do_fft && (do_up != h->do_up || !do_fft) && h->acq_scratch.p) {
         // the three-phase scratch holds a frame's spectrum band, whose width depends on doUp: re-cut it into frames of the
         // new size, or drop it to be allocated again at the next call that needs it
-        const size_t per = acq3_frame_bytes(h->nsf, do_up) + 64 + (h->gen_plan.on ? acqg_image_bytes(h->nsf) : 0);
+        const size_t per = acq3_frame_bytes(h->nsf, do_up) + 64 + (h->fft_plan.kind == FRONT_GEN ? acqg_image_bytes(h->nsf) : 0);
         const long long chunk = (long long)((h->acq_scratch.n - 512) / (per * (size_t)h->nstreams));
         if (chunk >= 1) {
             h->acq_chunk = (int)(chunk < h->acq_chunk ? chunk : h->acq_chunk);
@@ -94,7 +94,7 @@ static int chan_apply(jsdr_bpsk *h, int ch, const double *tuning, const int *do_
             h->acq_scratch.release();  // (never both: the scratch is the handle's largest buffer)
             h->acq_chunk = 0;
             if (mask != 0) {
-                if (acq_scratch_ensure(h, acq3c_frame_bytes(h->nsf, mask, h->gen_plan.on), (size_t)h->nin, 4096) != JSDR_OK) {
+                if (acq_scratch_ensure(h, acq3c_frame_bytes(h->nsf, mask, h->fft_plan.kind == FRONT_GEN), (size_t)h->nin, 4096) != JSDR_OK) {
                     set_error("%s: the FFT-acquire scratch could not be cut again for the bands in use; the handle is unchanged (its next "
                               "call allocates the scratch anew)", who);
                     return JSDR_ERR;

@@ -1,4 +1,5 @@
-// bpsk_fft.h -- interface of the FFT-acquire front end (bpsk_fft.hip) used by the pipeline host code (bpsk_handle.hip)
+// bpsk_fft.h -- interface of the FFT-acquire front ends (bpsk_fft.hip, bpsk_acq*.hip, bpsk_fftm*.hip, bpsk_fft2x.hip) used by
+// the pipeline host code (bpsk_handle.h's units), and the frame stages their kernels share
 #pragma once
 #include "bpsk_acq_rule.h"
 #include <vector>
@@ -146,7 +147,7 @@ __device__ __forceinline__ void wave_first_max(double &bestv, int &besti)
     besti = mi == 0x7fffffff ? -1 : mi;
 }
 
-// ---- the frame stages every FFT-acquire front end shares (bpsk_fft.hip, bpsk_fftm.hip, bpsk_acq*.hip); the scalar rules they
+// ---- the frame stages every FFT-acquire front end shares (bpsk_fft.hip, bpsk_fftm.hip and its siblings, bpsk_acq*.hip); the scalar rules they
 // step are bpsk_acq_rule.h's
 
 // :416-421 -- a sample of the frame as the transform's input: (double) of JavaAudio's float sample, int16 words with the
@@ -306,44 +307,30 @@ __device__ __forceinline__ int acq_spec_index(int b, int n, int do_up)
     return (b >= lo && b < n / 2 + 28) ? 204 + (b - lo) : -1;
 }
 
+// The frame's plan (bpsk_fftplan.h: the front end that serves it, its passes, its tables' offsets, fixed at create) comes with
+// every launch below that is not the power-of-two kernels' own; which frames each front end takes: fft_front_kind there.
+struct FftPlan;
 // the default mixed-radix frames (9600 / 4800 / 4410) in the same three phases: bpsk_fftm.hip has the two frame-parallel kernels
 // (which 0: k_acqm_fwd, 1: k_acqm_inv), built from k_front_fftm's passes
-bool acqm_supported(int n);
-int launch_acqm(const AcqArgs &a, const FftFrontArgs &fa, int np, const int *rad, const int *tw_off, const int *wr_off, int num_cu,
-                int which, hipStream_t st);
-struct AcqmPlan {  // the handle's mixed-radix plan (fftm_twiddles), for launch_acq3
-    int np = 0;
-    const int *rad = nullptr, *tw_off = nullptr, *wr_off = nullptr;
-};
+int launch_acqm(const AcqArgs &a, const FftFrontArgs &fa, const FftPlan &pl, int num_cu, int which, hipStream_t st);
 // per-phase timing hook (bench.py's per-kernel figures): phase 0..3 = k_acq_fwd, k_acq_scan, k_acq_inv, k_acq_edges
 struct AcqProf {
     void *ctx = nullptr;
     void (*mark)(void *ctx, int phase, bool begin, hipStream_t st) = nullptr;
 };
-// ANY other frame (bpsk_acqg.hip): phases A and C with the frame's image in global memory, one launch per pass of the oracle's
-// transform -- powers of two outside 1024 .. 8192, frames above 9600 samples that are not twice a 16 | m, 2^a 3^b 5^c one
-// (17640, 38400), and the LDS front ends' frames at the decimations they do not take
-constexpr int ACQG_MAXPASS = 32;
-struct AcqgPlan {
-    bool on = false;
-    int logn = 0;                // a power of two: the radix-2 network on fft_twiddles_f64's table; else the Stockham plan below
-    int np = 0;
-    int rad[ACQG_MAXPASS] = {0};
-    int tw_off[ACQG_MAXPASS] = {0};  // pass p's table T[m] = exp(-2 pi i m / (P r))
-    int wr_off[ACQG_MAXPASS] = {0};  // a prime radix above 7: W[m] = exp(-2 pi i m / r)
-};
-bool acqg_supported(int n);
-size_t acqg_image_bytes(int n);  // scratch per (stream, frame) of one launch, on top of acq3_frame_bytes
-void acqg_twiddles(std::vector<double2> &w, int n, AcqgPlan *plan);
-int launch_acqg(const AcqArgs &a, const AcqgPlan &pl, double2 *img, int which, hipStream_t st);
+// ANY other frame (bpsk_acqg.hip, a FRONT_GEN plan): phases A and C with the frame's image in global memory, one launch per pass
+// of the oracle's transform -- powers of two outside 1024 .. 8192, frames above 9600 samples that are not twice a 16 | m,
+// 2^a 3^b 5^c one (17640, 38400), and the LDS front ends' frames at the decimations they do not take; its scratch per (stream,
+// frame) of one launch: acqg_image_bytes on top of acq3_frame_bytes
+int launch_acqg(const AcqArgs &a, const FftPlan &pl, double2 *img, int which, hipStream_t st);
 int launch_acq3(const FftFrontArgs &a, int nstreams, unsigned char *scratch, size_t scratch_bytes, int chunk_frames, int num_cu,
-                hipStream_t st, const AcqProf &prof, const AcqmPlan &plan, const AcqgPlan *gen = nullptr);
+                hipStream_t st, const AcqProf &prof, const FftPlan &plan);
 // the channel handle's form (bpsk_acq_chan.hip): the forward phase once per INPUT and frame, scan / inverse / edges once per FFT
 // channel over that channel's streams (one per input), by the same kernels through strided arguments
 enum { ACQ_PART_FWD = 1, ACQ_PART_SCAN = 2, ACQ_PART_INV = 4, ACQ_PART_EDGES = 8, ACQ_PARTS_ALL = 15 };
 void acq3_row_layout(int n, int do_up, int *nsb, int *na);
-int launch_acq3_parts(AcqArgs &a, const FftFrontArgs &fa, int parts, int num_cu, hipStream_t st, const AcqProf &prof, const AcqmPlan &plan,
-                      const AcqgPlan *gen, double2 *img);
+int launch_acq3_parts(AcqArgs &a, const FftFrontArgs &fa, int parts, int num_cu, hipStream_t st, const AcqProf &prof, const FftPlan &plan,
+                      double2 *img);
 struct AcqChanArgs {
     int nin = 0, nch = 0;      // inputs, channels per input: stream = input * nch + channel
     int nfft = 0;              // FFT-acquire channels ...
@@ -359,23 +346,15 @@ struct AcqChanArgs {
 };
 size_t acq3c_frame_bytes(int n, int band_mask, bool generic);  // scratch per (input, frame) of one launch
 int launch_acq3_chan(const FftFrontArgs &fa, AcqChanArgs &ca, unsigned char *scratch, size_t scratch_bytes, int chunk_frames, int num_cu,
-                     hipStream_t st, const AcqProf &prof, const AcqmPlan &plan, const AcqgPlan *gen);
+                     hipStream_t st, const AcqProf &prof, const FftPlan &plan);
 extern int g_acq_last_grid[4];  // workgroups of the last k_acq_fwd / k_acq_inv launch, and how many of each a CU holds
-// frames that are not a power of two (bpsk_fftm.hip): any n with 416 <= n <= 9600 (2^a 3^b 5^c 7^d through the radix passes, any
-// other prime factor through a pass that is the DFT's definition and needs fftm_scratch(n) elements of scratch per stream)
-bool fftm_supported(int n);
-bool fftm_pairs(int n, int nframes);  // launch_front_fftm takes the call's frames two at a time (k_front_fftm2)
-size_t fftm_scratch(int n);
-void fftm_twiddles(std::vector<double2> &w, int n, int *np_out, int *rad, int *tw_off, int *wr_off);
-int launch_front_fftm(const FftFrontArgs &a, int np, const int *rad, const int *tw_off, const int *wr_off, double2 *gscratch,
-                      int nstreams, hipStream_t st);
-void fft_twiddles_f64(std::vector<double2> &w, int n);
-// frames of 2 m samples, m an LDS-sized mixed-radix frame (n = 19200 at 192 kHz): two m-point halves per transform
-bool fft2x_supported(int n);
-void fft2x_twiddles(std::vector<double2> &w, int n, int *np_out, int *rad, int *tw_off, int *tw1_off);
-size_t fft2x_scratch_ek(int n);
-size_t fft2x_scratch_r0(int n);
-int launch_front_fft2x(const FftFrontArgs &a, int np, const int *rad, const int *tw_off, const int *tw1_off, double2 *ek,
-                       double *r0, int nstreams, hipStream_t st);
+// frames that are not a power of two (bpsk_fftm.hip, a FRONT_FFTM plan): any n with 416 <= n <= 9600 (2^a 3^b 5^c 7^d through the
+// radix passes, any other prime factor through a pass that is the DFT's definition and needs fftm_scratch(n) elements of scratch
+// per stream, gscratch); a call that fftm_pairs takes goes on to launch_front_fftm2 (bpsk_fftm2.hip: two frames at a time)
+int launch_front_fftm(const FftFrontArgs &a, const FftPlan &pl, double2 *gscratch, int nstreams, hipStream_t st);
+int launch_front_fftm2(const FftFrontArgs &a, const FftPlan &pl, int nstreams, hipStream_t st);
+// frames of 2 m samples, m an LDS-sized mixed-radix frame (n = 19200 at 192 kHz; bpsk_fft2x.hip, a FRONT_FFT2X plan): two m-point
+// halves per transform, fft2x_scratch_ek / _r0 elements of scratch per stream
+int launch_front_fft2x(const FftFrontArgs &a, const FftPlan &pl, double2 *ek, double *r0, int nstreams, hipStream_t st);
 
 }  // namespace jsdr

@@ -625,22 +625,4 @@ int launch_front_fft(const FftFrontArgs &a, int nstreams, hipStream_t st)
     }
 }
 
-// per-stage twiddles Ts[half-1+j] = W_n^(j*n/(2*half)), j < half, half = 1,2,..,n/2 (n-1 entries), every value taken
-// from the SAME table as oracle/o_fft.c jo_fft_twiddles_f64 builds (long double + one rounding, exact on the axes)
-void fft_twiddles_f64(std::vector<double2> &w, int n)
-{
-    std::vector<double2> base((size_t)n / 2);
-    for (int k = 0; k < n / 2; k++) {
-        long double ang = 2.0L * 3.14159265358979323846264338327950288L * (long double)k / (long double)n;
-        base[k] = make_double2((double)cosl(ang), (double)(-sinl(ang)));
-    }
-    base[0] = make_double2(1.0, -0.0);
-    if (n >= 4) base[n / 4] = make_double2(0.0, -1.0);
-    w.assign((size_t)n, make_double2(0.0, 0.0));
-    for (int half = 1; half < n; half <<= 1) {
-        const int step = n / (2 * half);
-        for (int j = 0; j < half; j++) w[(size_t)half - 1 + j] = base[(size_t)j * step];
-    }
-}
-
 }  // namespace jsdr

@@ -26,7 +26,7 @@
 #pragma once
 #include "bpsk_kernels.h"
 #include "bpsk_fec.h"
-#include "bpsk_fft.h"
+#include "bpsk_fftplan.h"
 #include "bpsk_chan.h"
 #include "bpsk_pst.h"
 #include "bpsk_sched.h"
@@ -66,9 +66,6 @@ enum { PK_FRONT = 0, PK_HIST, PK_MATCHED, PK_DMHIST, PK_TAIL, PK_SYNC, PK_SYNCFI
        PK_ACQ_FWD, PK_ACQ_SCAN, PK_ACQ_INV, PK_ACQ_EDGES, PK_ACQC_FWD, PK_TWALK, PK_COUNT };
 
 enum { SEAM_NONE = 0, SEAM_TO_FFT = 1, SEAM_TO_TUNE = 2 };
-
-// the FFT-acquire front end that serves a frame size (fft_front_kind)
-enum FftFront { FRONT_POW2, FRONT_FFTM, FRONT_FFT2X, FRONT_GEN, FRONT_NONE };
 
 #pragma GCC visibility pop
 }  // namespace jsdr
@@ -187,11 +184,11 @@ struct jsdr_bpsk {
     std::vector<double2> h_vco_cs;
     DevBuf<long long> phase_clk;  // JSDR_FFT_PHASECLK=1: k_front_fft's per-phase cycle counts, printed at destroy
     int logn = 0;
-    bool fft_mixed = false;  // FFT-acquire frame is not a power of two (bpsk_fftm.hip)
-    bool fft_2x = false;     // ... and is 2 m with m an LDS-sized frame (n = 19200): two m-point halves per transform
-    AcqgPlan gen_plan;       // gen_plan.on: none of the LDS front ends takes the frame (or its decimation): bpsk_acqg.hip, always in three phases
-    int fm_np = 0, fm_rad[12] = {0}, fm_off[12] = {0}, fm_off1[12] = {0};
-    DevBuf<double2> fft2x_ek;  // per-stream scratch of the 2 m front end
+    // the FFT-acquire plan of the handle's frame (bpsk_fftplan.h), fixed when the FFT-acquire buffers are made; its kind: FRONT_FFTM
+    // the frame is not a power of two (bpsk_fftm.hip), FRONT_FFT2X it is 2 m with m such a frame (n = 19200), FRONT_GEN none of the
+    // LDS front ends takes the frame (or its decimation): bpsk_acqg.hip, always in three phases
+    FftPlan fft_plan;
+    DevBuf<double2> fft2x_ek;  // per-stream scratch of the 2 m front end (a mixed-radix frame with a prime radix above 7: of its out-of-place pass)
     DevBuf<double> fft2x_r0;
     // round 6: the three-phase front end (bpsk_acq.hip) for calls of two or more frames per stream -- what its phases hand each
     // other, for nstreams x acq_chunk frames; allocated at the first such call
@@ -361,9 +358,8 @@ struct AcqProfCtx {
     jsdr_bpsk *h;
     Event a[5];  // (phase 4: the channel handle's both-band forward kernel)
 };
-// what launch_acq3 / launch_acq3_chan take beside the arguments: the handle's mixed-radix plan and the per-phase timing hook
+// what launch_acq3 / launch_acq3_chan take beside the arguments and the handle's plan: the per-phase timing hook
 struct AcqLaunchCtx {
-    AcqmPlan plan;
     AcqProfCtx pc;
     AcqProf prof;
 };
@@ -412,9 +408,8 @@ inline HistArgs hist_args(const jsdr_bpsk *h, const int *raw, const float2 *rawf
 }
 
 // ------------------------------------------------------------------------------------------- what crosses a unit boundary
-// bpsk_handle.hip.  fft_front_kind: which front end serves a frame of n samples at a decimation of decim, FRONT_NONE: none;
-// fft_mode_alloc: the FFT-acquire buffers of a handle, all or nothing
-FftFront fft_front_kind(int n, int decim, bool chan_form, int force_gen = -1);
+// bpsk_handle.hip.  fft_mode_alloc: the FFT-acquire buffers of a handle and its plan for the front end `kind` (fft_front_kind,
+// bpsk_fftplan.h), all or nothing
 int fft_mode_alloc(jsdr_bpsk *h, FftFront kind, bool seam);
 
 // bpsk_call.hip: the stages of a call, in the order chan_run, pst_run and bpsk_run put their work onto the caller's stream

@@ -43,21 +43,7 @@ static bool bit_clock_is_regular()
 }
 
 // ------------------------------------------------------------------------------------------- FFT-acquire set-up
-// Which FFT-acquire front end serves a frame of n samples at a decimation of decim.  The power-of-two (1024 .. 8192) and the
-// 2 m front ends size their per-thread output lists for a decimation of at least 4; the mixed-radix one (any other frame up
-// to 9600 samples) loops and takes any.  Whatever those refuse -- and any other frame the oracle defines -- goes through the
-// any-frame passes (bpsk_acqg.hip); FRONT_NONE: no front end takes the frame.
-// chan_form (jsdr_bpsk_create_mode_channels): a channel handle has the three-phase front ends only, so every frame that is
-// not one of theirs (2^k of 1024 .. 8192 at a decimation of 4 and more, 9600 / 4800 / 4410) takes the any-frame passes' plan.
-// force_gen (jsdr_bpsk_create under JSDR_ACQG, tests): 1 the any-frame passes for a frame the LDS kernels take, 0 never them.
-FftFront jsdr::fft_front_kind(int n, int decim, bool chan_form, int force_gen)
-{
-    const bool pow2 = n >= 1024 && n <= 8192 && (n & (n - 1)) == 0;
-    const bool lds = chan_form ? ((pow2 && decim >= 4) || acqm_supported(n)) : (fftm_supported(n) || (decim >= 4 && (pow2 || fft2x_supported(n))));
-    if (force_gen >= 0 ? force_gen != 0 : !lds) return acqg_supported(n) ? FRONT_GEN : FRONT_NONE;
-    return pow2 ? FRONT_POW2 : fft2x_supported(n) ? FRONT_FFT2X : FRONT_FFTM;
-}
-
+// (which front end serves a frame: fft_front_kind, bpsk_fftplan.hip)
 // the frame rule's one text; `what`: "<entry point>: <what needs the frame>"
 static int fft_frame_refused(const char *what, int n)
 {
@@ -82,8 +68,7 @@ int jsdr::fft_mode_alloc(jsdr_bpsk *h, FftFront kind, bool seam)
     DevBuf<double2> tw, vcs, ek, dm2;
     DevBuf<double> r0;
     std::vector<double2> w;
-    AcqgPlan plan;
-    int np = 0, rad[12] = {0}, off[12] = {0}, off1[12] = {0};
+    FftPlan plan;
     bool ok = !want_seam || (st2.alloc(S) == JSDR_OK && dm2.alloc(S * (size_t)stride2) == JSDR_OK && st2.zero() == JSDR_OK && dm2.zero() == JSDR_OK);
     if (ok && !h->fft_ready) {
         ok = st.alloc(S) == JSDR_OK && vcs.alloc((size_t)h->max_ds) == JSDR_OK &&
@@ -92,11 +77,7 @@ int jsdr::fft_mode_alloc(jsdr_bpsk *h, FftFront kind, bool seam)
              // (a mixed-radix frame with a prime factor above 7: the out-of-place pass's scratch, in the 2 m front end's slot)
              (!(kind == FRONT_FFTM && fftm_scratch(n) > 0) || ek.alloc(S * fftm_scratch(n)) == JSDR_OK);
         if (ok) {
-            if (gen) acqg_twiddles(w, n, &plan);
-            else if (pow2) fft_twiddles_f64(w, n);
-            else if (f2x) fft2x_twiddles(w, n, &np, rad, off, off1);
-            else fftm_twiddles(w, n, &np, rad, off, off1);  // (off1: the prime radices' r-point tables)
-            ok = w.size() <= tw.n && hipMemcpy(tw.p, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice) == hipSuccess &&
+            ok = fft_plan_build(plan, w, n, kind) && w.size() <= tw.n && hipMemcpy(tw.p, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice) == hipSuccess &&
                  st.zero() == JSDR_OK;
         }
     }
@@ -118,13 +99,7 @@ int jsdr::fft_mode_alloc(jsdr_bpsk *h, FftFront kind, bool seam)
         std::swap(h->fft_tw, tw);
         std::swap(h->fft2x_ek, ek);
         std::swap(h->fft2x_r0, r0);
-        h->fft_mixed = !pow2 && !gen;
-        h->fft_2x = f2x;
-        h->gen_plan = plan;
-        h->fm_np = np;
-        memcpy(h->fm_rad, rad, sizeof(rad));
-        memcpy(h->fm_off, off, sizeof(off));
-        memcpy(h->fm_off1, off1, sizeof(off1));
+        h->fft_plan = plan;
         h->fft_ready = true;
     }
     return JSDR_OK;
@@ -138,7 +113,7 @@ static void bpsk_phase_clocks_report(const jsdr_bpsk *h)
                                             "gather/zero", "inverse FFT", "scale+RxDownSample"};
     static const char *const names_mx[8] = {"load", "forward FFT", "centre-bin rule", "gather/zero/place", "inverse FFT",
                                             "RxDownSample", "|X|", "boxcar+argmax"};
-    const char *const *names = h->fft_mixed ? names_mx : names_p2;
+    const char *const *names = (h->fft_plan.kind == FRONT_FFTM || h->fft_plan.kind == FRONT_FFT2X) ? names_mx : names_p2;
     long long c[16] = {0};
     if (hipDeviceSynchronize() == hipSuccess &&
         hipMemcpy(c, h->phase_clk.p, sizeof(c), hipMemcpyDeviceToHost) == hipSuccess) {

@@ -1,5 +1,5 @@
 // bpsk_radix.h -- the fixed-order r-point butterflies of the oracle's mixed-radix transform (oracle/o_fft.c dft_r), shared by the
-// LDS front ends (bpsk_fftm.hip) and the any-frame passes through global memory (bpsk_acqg.hip).  Include only from translation
+// LDS front ends (bpsk_fftm_dev.h) and the any-frame passes through global memory (bpsk_acqg.hip).  Include only from translation
 // units compiled with -ffp-contract=off: every product and sum rounds by itself, as Java's do.
 #pragma once
 #include "common.h"
