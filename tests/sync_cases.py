@@ -110,12 +110,12 @@ def symbols_of(case):
 
 
 @functools.lru_cache(maxsize=None)
-def stream_of(case):
-    """int16 IQ [2 N] of a case: DBPSK at 1200 symbols/s on a 13 200 Hz carrier, 96 kHz, a little noise"""
+def stream_of(case, carrier_hz=13200.0):
+    """int16 IQ [2 N] of a case: DBPSK at 1200 symbols/s on a 13 200 Hz carrier (or the one given), 96 kHz, a little noise"""
     sym = symbols_of(case)
     ds = O.synth_diffsign((sym > 0).astype(np.uint8), 1)
     ct, st = O.synth_tables(AMP)
-    iq = O.synth_dbpsk(0, N, ds, SPS, 0, O.phase_inc_u32(13200.0, RATE), ct, st, NOISE_GAIN, O.mix64(0x53594E43 ^ (case[2] * 0x9E3779B1)))
+    iq = O.synth_dbpsk(0, N, ds, SPS, 0, O.phase_inc_u32(carrier_hz, RATE), ct, st, NOISE_GAIN, O.mix64(0x53594E43 ^ (case[2] * 0x9E3779B1)))
     iq.setflags(write=False)
     return iq
 

@@ -24,6 +24,7 @@ def run(raw, S, chunks, shares, two_streams):
         dem.set_cu_share(shares[1])
     s1 = J.Stream()
     s2 = J.Stream() if two_streams else s1
+    dem.call_streams = (s1, s2)  # (dem is read after this returns, and its getters synchronise the stream of its last call)
     out = []
     pos = 0
     for c in chunks:

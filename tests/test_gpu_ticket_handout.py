@@ -90,6 +90,9 @@ def run(raw, chunks, shares, fft_in, f32=False, pair=None, two_streams=True):
     pair = pair or make_pair(S, max(chunks))
     s1 = J.Stream()
     streams = (s1, J.Stream() if two_streams else s1)
+    # (the demodulator is returned and read later, and its getters synchronise the stream of its last call: the streams live as
+    #  long as the handle does, not only until this function returns)
+    pair[1].call_streams = getattr(pair[1], "call_streams", []) + [streams]
     out, launches, pos = [], [], 0
     for k, c in enumerate(chunks):
         sh = shares[k] if shares and isinstance(shares[0], tuple) else shares
