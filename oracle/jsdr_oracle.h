@@ -127,6 +127,7 @@ void jo_bpsk_decision_margins(const jo_bpsk_t *d, double *out /* [8] */);
  * FUNcubeBPSKDemod.java:159-162), and a log of what RxDemodulate decides on -- which 0: per detector instant {di, energy2}
  * (:539-544), which 1: per bit clock {dmEnergy[dmNewPeak] - runner-up, dmNewPeak} (:586-592); returns the count */
 void jo_bpsk_set_sincos(jo_bpsk_t *d, const double sin_tab[256], const double cos_tab[256]);
+void jo_bpsk_clear_dm_history(jo_bpsk_t *d);  /* dmBuf zeroed, dmPos and all else kept */
 void jo_bpsk_declog_enable(jo_bpsk_t *d, int64_t cap);
 int64_t jo_bpsk_declog(const jo_bpsk_t *d, int which, double *out, int64_t cap);
 /* the detector instants with their place: g[n] = the 9600 Hz sample number of decision n, out = {di, energy2} as above */

@@ -591,6 +591,13 @@ void jo_bpsk_set_sincos(jo_bpsk_t *d, const double sin_tab[256], const double co
     memcpy(d->cosTab, cos_tab, sizeof(d->cosTab));
 }
 
+/* instrument of tests/fm_cases.py: the matched filter's ring as a new stream has it (:496 leaves it zero), everything else kept --
+ * what a call computes when the 64 samples kept from the call before are lost */
+void jo_bpsk_clear_dm_history(jo_bpsk_t *d)
+{
+    memset(d->dmBuf, 0, sizeof(d->dmBuf));
+}
+
 void jo_bpsk_declog_enable(jo_bpsk_t *d, int64_t cap)
 {
     free(d->dlog_det);

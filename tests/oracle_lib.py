@@ -75,6 +75,8 @@ def _proto(L):
     L.jo_bpsk_declog_pos.restype = C.c_int64
     L.jo_bpsk_declog_pos.argtypes = [vp, vp, vp, C.c_int64]
     L.jo_bpsk_state.argtypes = [vp, vp]
+    L.jo_bpsk_clear_dm_history.restype = None
+    L.jo_bpsk_clear_dm_history.argtypes = [vp]
     L.jo_bpsk_istate.argtypes = [vp, vp]
     L.jo_bpsk_table.argtypes = [C.c_int, vp, C.c_int]
     L.jo_bpsk_sincos.argtypes = [vp, vp]
@@ -451,6 +453,10 @@ class Bpsk:
     def fft_perturb(self, scale, seed):
         lib().jo_bpsk_fft_perturb.argtypes = [C.c_void_p, C.c_double, C.c_uint64]
         lib().jo_bpsk_fft_perturb(self.h, float(scale), int(seed))
+
+    def clear_dm_history(self):
+        """instrument: zero the matched filter's 65-sample ring (tests/fm_cases.py: does the halo matter in this data?)"""
+        lib().jo_bpsk_clear_dm_history(self.h)
 
     def trace_ds(self):
         n = lib().jo_bpsk_trace_ds(self.h, None, 0)
