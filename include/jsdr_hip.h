@@ -643,8 +643,8 @@ int jsdr_bpsk_batch_f32(jsdr_bpsk *h, const float *iq_dev, int64_t stream_stride
  * FUNcubeBPSKDemod.java:118-125) and everything paintComponent's first panel computes from them (:231-268), for every frame of a
  * batch call.  A scope call IS the batch call plus the painter: it runs jsdr_bpsk_batch_i16 / _f32 with the same arguments --
  * every getter and the carried state come out bit for bit as the batch call leaves them -- and then, on the caller's stream, the
- * scope passes over the frames of the call.  The painter's two spectra (:270-327) are not built; the tuned and ds rows are their
- * inputs.
+ * scope passes over the frames of the call.  The painter's two spectra (:270-327) are jsdr_bpsk_scope_spectra_i16 / _f32 below; the
+ * tuned and ds rows are their inputs.
  * Geometry: n the handle's frame, D = rate / 9600, L = n * 9600 / rate (Java's int arithmetic, :201: the length of the three
  * short rings in pairs), frames = nsamples / n, row = s * frames + f for frame f of stream s, rows packed.  The decimated sample
  * number g (the g-th RxDemodulate call since the origin, from 0) belongs to frame f when G_f <= g < G_{f+1}, G_f =
@@ -698,6 +698,54 @@ int jsdr_bpsk_scope_f32(jsdr_bpsk *h, const float *iq_in_dev, int64_t stream_str
 int jsdr_bpsk_scope_layout(jsdr_bpsk *h, int64_t nsamples, int *ring_len, int64_t *origin, int64_t *g_first /* [frames + 1] */,
                            int cap);                              /* host only */
 const char *jsdr_bpsk_scope_kernel(jsdr_bpsk *h);                 /* what the last scope call launched, joined with '+' */
+/* The BPSK scope's spectra: the second half of the painter's panel (:270-327), the green spectrum of the `tuned` ring and the
+ * cyan one of the `downSmpl` ring, for every frame of a batch call.  A spectra call IS the scope call with the same arguments --
+ * its six outputs come out bit for bit as jsdr_bpsk_scope_* leaves them, and so does everything of the batch call -- plus, for
+ * row = s * frames + f, with X the row tuned_dev[row] (len = n) or ds_dev[row] (len = L) as the scope call defines them, in slot
+ * order, nothing rotated:
+ *   Y = DoubleFFT_1D.complexForward(X): this project's jo_fft_f64 (oracle/o_fft.c), operation for operation -- the bit-reversed
+ *       radix-2 network for len = 2^k, else Stockham passes in jo_fft_mixed_radices order, a prime radix above 7 as its definition;
+ *   psd[k] = sqrt(Yre * Yre + Yim * Yim) for all len bins (:277): two products, one sum, a correctly rounded root;
+ *   max = 0.0, mo = 0, and for k ascending over all len bins under the strict max < psd[k] they take psd[k] and k (:274-282): a NaN
+ *       never wins, ties go to the lowest bin, a row of NaN bins or of silence leaves (0.0, 0);
+ *   with Wp = plot_width (the reference's getWidth() - xo), pi = (double)(len / 2) / (double)Wp, ys = 100.0 / max (:285, :293):
+ *       y[0] = (int)(psd[0] * ys), and for m = 1 .. Wp - 1, i = (int)(pi * (double)m), l = (int)pi, y[m] = (int)(getMax(psd, i, l) * ys)
+ *       -- getMax as written (:348-355): from psd[i], strict m < psd[j] for j < i + l, psd[i] itself when l == 0.  (int) is Java's
+ *       cast; max == 0 gives ys = Infinity and 0 * Infinity = NaN -> 0.  Only the lower half of psd[] reaches the polyline; the
+ *       window arithmetic (getHeight() - 1 - y, xo + m) stays the caller's.
+ * Outputs, rows packed, each may be NULL: tspec_dev[row][Wp] and dspec_dev[row][Wp] the y[] of the green and the cyan spectrum,
+ * tpeak_dev[row][2] and dpeak_dev[row][2] (max, (double)mo), tpsd_dev[row][n] and dpsd_dev[row][L] the whole psd[].  With all six
+ * NULL the call is jsdr_bpsk_scope_* launch for launch; with the scope's six NULL as well it is the batch call.  The painter
+ * transforms its rings in place and every later receive() overwrites them whole, so the spectra change nothing downstream.
+ * Rows: a spectrum reads the caller's tuned_dev / ds_dev rows where they are given.  Where they are not, the rows come from the
+ * handle: k_bpsk_scope_front fills them a pass of frames at a time -- as many frames as 64 MiB of rows hold, one at least;
+ * jsdr_bpsk_scope_chunk(h, frames_per_pass) lowers that (0: the default) -- each pass followed by its spectra kernels.
+ * Kernels, one workgroup a row, the row's image in LDS, the epilogue (magnitudes, first maximum, pooled casts) in the same kernel:
+ *   "k_bpsk_spec_pow2"      len = 2^k, 64 .. 8192;
+ *   "k_bpsk_spec_mixed64"   any other len up to 512 (L = 204 = 4 3 17, 102, 409), one wave a row;
+ *   "k_bpsk_spec_mixed256"  ... up to 2048;   "k_bpsk_spec_mixed768"  ... up to 9600 (4800, 4410).
+ * Served lengths: powers of two 64 .. 8192 and every other length of 2 .. 9600 with at most 12 passes.  Not served, refused with
+ * the length named: powers of two below 64 and above 8192, every other length above 9600 (19200 among them).
+ * jsdr_bpsk_scope_kernel names the spectra kernels behind the scope's passes, the green spectrum's first.  The plans of n and L,
+ * their tables and the handle's rows are allocated at the first spectra call that needs them, counted by jsdr_live_resources and
+ * gone with the handle; a later call with the same outputs and sizes neither allocates nor waits for the device.  A handle that
+ * makes no spectra call allocates and launches what it did before.
+ * JSDR_ERR before any device work, the handle unchanged: whatever jsdr_bpsk_scope_* refuses, with its message; plot_width outside
+ * 1 .. 32768 where tspec_dev or dspec_dev is given; an output not aligned (the int32 rows: 4 bytes, the double rows: 16 bytes); a
+ * row length that no kernel serves, where a spectrum of that row is asked for.
+ * jsdr_bpsk_scope_spec_layout (host only, no device): first[m] = i and count[m] = l of column m in the double arithmetic above,
+ * (0, 0) at m = 0, for a row of len points -- any len >= 2, served by a kernel or not; JSDR_ERR for len < 2, plot_width outside
+ * 1 .. 32768, cap < plot_width, and for a column that would read outside psd[] (none exists: i + l <= len / 2 + 1). */
+int jsdr_bpsk_scope_spectra_i16(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stream_stride_i16, int64_t nsamples, int ic, int qc,
+                                double *tuned_dev, double *ds_dev, double *iq_dev, double *max_dev, int32_t *pts_dev, int8_t *bits_dev,
+                                int plot_width, int32_t *tspec_dev, double *tpeak_dev, double *tpsd_dev, int32_t *dspec_dev,
+                                double *dpeak_dev, double *dpsd_dev, void *stream);
+int jsdr_bpsk_scope_spectra_f32(jsdr_bpsk *h, const float *iq_in_dev, int64_t stream_stride_f32, int64_t nsamples,
+                                double *tuned_dev, double *ds_dev, double *iq_dev, double *max_dev, int32_t *pts_dev, int8_t *bits_dev,
+                                int plot_width, int32_t *tspec_dev, double *tpeak_dev, double *tpsd_dev, int32_t *dspec_dev,
+                                double *dpeak_dev, double *dpsd_dev, void *stream);
+int jsdr_bpsk_scope_spec_layout(int len, int plot_width, int32_t *first /* [plot_width] */, int32_t *count, int cap);  /* host only */
+int jsdr_bpsk_scope_chunk(jsdr_bpsk *h, int frames_per_pass);     /* frames of one pass of handle-owned rows; 0: the default */
 int jsdr_bpsk_set_cu_share(jsdr_bpsk *h, int wgs_per_cu); /* see jsdr_fft_set_cu_share; applies to the tune-mode front-end kernel */
 /* The library's own answer to "should fft.receive and this demodulator, fed the same batch on two streams, share the CUs?":
  * the shares to pass to jsdr_fft_set_cu_share / jsdr_bpsk_set_cu_share (2 and 1 where the split was measured to pay: the

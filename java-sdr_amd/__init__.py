@@ -13,5 +13,5 @@ from .binding import (  # noqa: F401
     JsdrError, lib, library_path, have_gpu, live_resources, DeviceBuffer, Fft, Fir, Bpsk, BpskChannels, BpskTuned, BpskTunedChannels, blob_info, tuner_walk_host, tuner_walk_plan_host, tuner_walk_ramp_host, Group, Timer, Stream, Phase,
     convert_i16, fir_batch_decimate_i16, bpsk_table, phase_maxabs, phase_columns, phase_layout, fec_decode, fec_encode, fec_decode_batch, fec_encode_batch, fec_encode_dev, fec_decode_dev,
     synth_payloads, synth_diffsign, synth_dbpsk, synth_tones, EXPORTED_SYMBOLS,
-    Demod, DemodChannels, demod_scope_layout, waterfall_lines, waterfall_lines_dev, recording_probe, recordings_load, RecordingInfo,
+    Demod, DemodChannels, demod_scope_layout, scope_spec_layout, waterfall_lines, waterfall_lines_dev, recording_probe, recordings_load, RecordingInfo,
 )

@@ -590,6 +590,28 @@ class Bpsk:
         _check(lib().jsdr_bpsk_scope_f32(self.h, _addr(iq_in_dev), C.c_int64(stride_f32), C.c_int64(nsamples), _addr(tuned), _addr(ds),
                                          _addr(iq), _addr(max), _addr(pts), _addr(bits), C.c_void_p(stream)), "jsdr_bpsk_scope_f32")
 
+    # the scope's spectra (jsdr_hip.h "The BPSK scope's spectra"): the scope call plus the painter's green and cyan spectra per frame
+    def scope_spectra_i16(self, raw_dev, stride_i16, nsamples, ic=0, qc=0, tuned=None, ds=None, iq=None, max=None, pts=None, bits=None,
+                          plot_width=0, tspec=None, tpeak=None, tpsd=None, dspec=None, dpeak=None, dpsd=None, stream=None):
+        """scope_i16, then per frame of the `tuned` row (t...) and of the `ds` row (d...): spec i32 [rows][plot_width], peak f64
+        [rows][2] = (max, mo), psd f64 [rows][n] / [rows][L]; None passes NULL"""
+        _check(lib().jsdr_bpsk_scope_spectra_i16(self.h, _addr(raw_dev), C.c_int64(stride_i16), C.c_int64(nsamples), ic, qc, _addr(tuned),
+                                                 _addr(ds), _addr(iq), _addr(max), _addr(pts), _addr(bits), int(plot_width), _addr(tspec),
+                                                 _addr(tpeak), _addr(tpsd), _addr(dspec), _addr(dpeak), _addr(dpsd), C.c_void_p(stream)),
+               "jsdr_bpsk_scope_spectra_i16")
+
+    def scope_spectra_f32(self, iq_in_dev, stride_f32, nsamples, tuned=None, ds=None, iq=None, max=None, pts=None, bits=None,
+                          plot_width=0, tspec=None, tpeak=None, tpsd=None, dspec=None, dpeak=None, dpsd=None, stream=None):
+        """scope_f32, then the spectra as scope_spectra_i16"""
+        _check(lib().jsdr_bpsk_scope_spectra_f32(self.h, _addr(iq_in_dev), C.c_int64(stride_f32), C.c_int64(nsamples), _addr(tuned),
+                                                 _addr(ds), _addr(iq), _addr(max), _addr(pts), _addr(bits), int(plot_width), _addr(tspec),
+                                                 _addr(tpeak), _addr(tpsd), _addr(dspec), _addr(dpeak), _addr(dpsd), C.c_void_p(stream)),
+               "jsdr_bpsk_scope_spectra_f32")
+
+    def scope_chunk(self, frames):
+        """frames of one pass of the handle's own rows in a spectra call (0: the default, what 64 MiB of rows hold)"""
+        _check(lib().jsdr_bpsk_scope_chunk(self.h, int(frames)), "jsdr_bpsk_scope_chunk")
+
     def scope_layout(self, nsamples):
         """(L, origin, G[frames + 1]) of a scope call of nsamples from the handle's present counters (host only)"""
         frames = max(int(nsamples) // self.samples, 0)
@@ -1076,6 +1098,15 @@ def unpack_slot(slot, info):
         fec.append((int(rc), int(bi), np.frombuffer(slot[o + 8:o + 264], np.uint8)))
     names = ["nbits", "nfec"] + COUNTER_NAMES[:9]
     return dict(header=dict(zip(names, (int(v) for v in hdr[:11]))), bits=bits, fec=fec)
+
+
+def scope_spec_layout(len, plot_width):
+    """the BPSK scope's spectra: (first, count) int32 [plot_width], i and l of every column of a spectrum of `len` bins drawn
+    plot_width wide, host only (jsdr_bpsk_scope_spec_layout)"""
+    out = [np.zeros(max(int(plot_width), 0), np.int32) for _ in range(2)]
+    _check(lib().jsdr_bpsk_scope_spec_layout(int(len), int(plot_width), *[_addr(a) if a.size else None for a in out], int(plot_width)),
+           "jsdr_bpsk_scope_spec_layout")
+    return tuple(out)
 
 
 # ------------------------------------------------------------------ demod.java (SURVEY 8f next-3)

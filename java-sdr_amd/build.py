@@ -81,6 +81,8 @@ SOURCES = {
     "bpsk_blob.hip": ["-ffp-contract=off"],
     # (the BPSK scope: the painter's rings and integers, every product, sum and quotient one IEEE double operation; its host side with it)
     "bpsk_scope.hip": ["-ffp-contract=off"],
+    # (the scope's two spectra: the oracle's FP64 transform of a row in LDS, operation for operation, magnitudes and casts behind it)
+    "bpsk_scope_spec.hip": ["-ffp-contract=off"],
     "group.hip": [],
 }
 

@@ -17,7 +17,8 @@ namespace jsdr {
 #pragma GCC visibility push(hidden)
 
 // the FFT-acquire front end that serves a frame size (fft_front_kind)
-enum FftFront { FRONT_POW2, FRONT_FFTM, FRONT_FFT2X, FRONT_GEN, FRONT_NONE };
+// (FRONT_ROW: no front end of FFT-acquire -- the plan of a plain row transform, fft_plan_build_row)
+enum FftFront { FRONT_POW2, FRONT_FFTM, FRONT_FFT2X, FRONT_GEN, FRONT_NONE, FRONT_ROW };
 
 constexpr int FM_NMAX = 9600;      // the largest frame whose double2 image fits a workgroup's LDS
 constexpr int FM_MAXPASS = 12;     // passes of such a frame: the bound of the kernels' argument arrays
@@ -96,6 +97,11 @@ size_t acqg_image_bytes(int n);
 // The plan of a frame of n samples for the front end `kind`, its tables in w: the pass tables back to back, the r-point tables
 // of the prime radices above 7 behind them, FRONT_FFT2X's c = 1 tables behind those.  false: the frame is not `kind`'s.
 bool fft_plan_build(FftPlan &pl, std::vector<double2> &w, int n, FftFront kind);
+// The plan of the oracle's transform of a row of n points outside FFT-acquire (the BPSK scope's spectra, bpsk_scope_spec.hip),
+// kind FRONT_ROW: any n of 2 .. 9600 with at most FM_MAXPASS passes, below fftm_supported's 416 as well -- a power of two
+// gets fft_twiddles_f64's table, every other n the pass tables of fft_plan_build with every table read from L2 (lds_tw = 0).
+// fft_front_kind never chooses it and fftm_supported does not know of it.  false: no such plan.
+bool fft_plan_build_row(FftPlan &pl, std::vector<double2> &w, int n);
 
 // The pass arguments of the LDS kernels from a plan: rad, tw_off, wr_off, pmagic, and lds_tw -- the longest prefix of the pass
 // tables that fits lds_room bytes.  false: the plan has more than FM_MAXPASS passes, or the tables of a default frame (9600 /

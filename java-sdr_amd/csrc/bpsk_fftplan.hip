@@ -154,6 +154,43 @@ FftFront fft_front_kind(int n, int decim, bool chan_form, int force_gen)
 }
 
 // ------------------------------------------------------------------------------------------- the plan
+// the Stockham passes of an m-point transform: radices, the pass tables back to back, the r-point tables of the prime radices
+// above 7 behind every pass table (so the default frames' offsets stay put)
+static bool plan_pass_tables(FftPlan &pl, std::vector<double2> &w, int m)
+{
+    pl.np = fft_radices(m, pl.rad);
+    if (pl.np <= 0) return false;
+    auto table = [&](int len) {
+        const size_t o = w.size();
+        w.resize(o + (size_t)len);
+        fft_table(w.data() + o, len);
+        return (int)o;
+    };
+    int P = 1;
+    for (int p = 0; p < pl.np; p++) {
+        pl.tw_off[p] = table(P * pl.rad[p]);
+        P *= pl.rad[p];
+    }
+    for (int p = 0; p < pl.np; p++) pl.wr_off[p] = pl.rad[p] > 7 ? table(pl.rad[p]) : 0;
+    return true;
+}
+
+bool fft_plan_build_row(FftPlan &pl, std::vector<double2> &w, int n)
+{
+    pl = FftPlan();
+    pl.n = n;
+    pl.kind = FRONT_ROW;
+    w.clear();
+    if (n < 2 || n > FM_NMAX) return false;
+    if ((n & (n - 1)) == 0) {
+        while ((1 << pl.logn) < n) pl.logn++;
+        fft_twiddles_f64(w, n);
+        return true;
+    }
+    if (!plan_pass_tables(pl, w, n)) return false;
+    return fft_pass_args(pl.args, pl, 0);  // (every table from L2; more than FM_MAXPASS passes: no plan)
+}
+
 bool fft_plan_build(FftPlan &pl, std::vector<double2> &w, int n, FftFront kind)
 {
     pl = FftPlan();
@@ -169,26 +206,12 @@ bool fft_plan_build(FftPlan &pl, std::vector<double2> &w, int n, FftFront kind)
         return true;
     }
     const int m = kind == FRONT_FFT2X ? n / 2 : n;  // (the 2 m front end runs the m-point passes on each half)
-    pl.np = fft_radices(m, pl.rad);
-    if (kind == FRONT_POW2 || pl.np <= 0) return false;
-    auto table = [&](int len) {
-        const size_t o = w.size();
-        w.resize(o + (size_t)len);
-        fft_table(w.data() + o, len);
-        return (int)o;
-    };
-    int P = 1;
-    for (int p = 0; p < pl.np; p++) {
-        pl.tw_off[p] = table(P * pl.rad[p]);
-        P *= pl.rad[p];
-    }
-    // the r-point tables of the prime radices above 7, behind every pass table (so the default frames' offsets stay put)
-    for (int p = 0; p < pl.np; p++) pl.wr_off[p] = pl.rad[p] > 7 ? table(pl.rad[p]) : 0;
+    if (kind == FRONT_POW2 || !plan_pass_tables(pl, w, m)) return false;
     if (kind == FRONT_GEN) return true;
     if (kind == FRONT_FFT2X) {
         // the c = 1 tables U_p[(j-1) P' + k'] = T_{2 P' r}[(2 k' + 1) j]
         std::vector<double2> t;
-        P = 1;
+        int P = 1;
         for (int p = 0; p < pl.np; p++) {
             const int r = pl.rad[p];
             t.resize((size_t)2 * P * r);
@@ -238,7 +261,7 @@ bool fft_pass_args(FftmArgs &aa, const FftPlan &pl, size_t lds_room, bool pair)
         if (pl.np != d.np) return false;
         for (int p = 0; p < d.np; p++)
             if (pl.tw_off[p] != d.off[p]) return false;
-        if (pl.kind != FRONT_FFT2X && aa.lds_tw != (pair ? d.lds_tw_pair : d.lds_tw)) return false;
+        if (pl.kind != FRONT_FFT2X && pl.kind != FRONT_ROW && aa.lds_tw != (pair ? d.lds_tw_pair : d.lds_tw)) return false;
     }
     return true;
 }

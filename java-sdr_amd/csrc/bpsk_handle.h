@@ -274,6 +274,15 @@ struct jsdr_bpsk {
     Event scope_ev_copy, scope_ev_walk;          // side stream -> caller's: the copy is made; caller's -> side: the walk has read it
     bool scope_walk_pending = false;
     std::string scope_name;                      // jsdr_bpsk_scope_kernel
+    // the scope's spectra (jsdr_bpsk_scope_spectra_*): the plans of the rows of n and of L points with their tables, built at the
+    // first spectra call; the handle's own `tuned` / `ds` rows of one pass of frames, for a spectrum whose rows the caller did not
+    // ask for, and the 26 inputs in front of a pass that does not start the call; all allocated at the first call that needs them
+    FftPlan scope_spec_plan[2];
+    DevBuf<double2> scope_spec_w[2];
+    DevBuf<double2> scope_spec_tuned;            // [S][c][n]
+    DevBuf<double> scope_spec_ds;                // [S][c][L][2]
+    DevBuf<int2> scope_spec_hist;                // [S][32]
+    int scope_spec_chunk = 0;                    // jsdr_bpsk_scope_chunk: frames of a pass at most (0: what 64 MiB of rows hold)
 };
 
 namespace jsdr {

@@ -19,7 +19,13 @@
 // order puts the copy behind the previous call's tail and in front of this one's), and the caller's stream waits for the
 // copy's event: no host wait.  demodRe's marks are written in place, into the last two ints of the slot's pts entry, which
 // k_bpsk_scope_pts reads before it writes the entry.
+//
+// A spectra call (jsdr_bpsk_scope_spectra_i16 / _f32) IS the scope call plus the painter's two spectra (:270-327): the kernels of
+// bpsk_scope_spec.hip over the caller's `tuned` / `ds` rows where they are given, else over rows of the handle's own that
+// k_bpsk_scope_front fills a pass of frames at a time -- the pass's geometry is the call's with its first frame moved on, and the
+// 26 inputs in front of a pass that does not start the call are gathered by k_hist_in (launch_hist_in) as between two calls.
 #include "bpsk_handle.h"
+#include "bpsk_scope_spec.h"
 #include <stdint.h>
 
 namespace jsdr {
@@ -51,15 +57,6 @@ struct ScopeFrontArgs {
     double2 *tuned;           // [rows][n], or null
     double *ds;               // [rows][L][2], or null
 };
-
-// Java's (int) of a double: truncates, saturates, NaN -> 0
-__device__ __forceinline__ int java_d2i(double v)
-{
-    if (v != v) return 0;
-    if (v >= 2147483647.0) return 2147483647;
-    if (v <= -2147483648.0) return (-2147483647 - 1);
-    return (int)v;
-}
 
 template <bool F32IN>
 __global__ __launch_bounds__(SCOPE_THREADS) void k_bpsk_scope_front(ScopeFrontArgs a, ScopeGeom g)
@@ -345,9 +342,108 @@ int jsdr_bpsk_scope_layout(jsdr_bpsk *h, int64_t nsamples, int *ring_len, int64_
 
 const char *jsdr_bpsk_scope_kernel(jsdr_bpsk *h) { return h ? h->scope_name.c_str() : ""; }
 
+// ---- the spectra of a call (jsdr_bpsk_scope_spectra_*): k = 0 the green one over `tuned` (n points), k = 1 the cyan one over
+// `ds` (L points)
+struct ScopeSpecReq {
+    int width = 0;
+    int32_t *spec[2] = {nullptr, nullptr};
+    double *peak[2] = {nullptr, nullptr};
+    double *psd[2] = {nullptr, nullptr};
+    bool want(int k) const { return spec[k] || peak[k] || psd[k]; }
+};
+constexpr size_t SCOPE_SPEC_ROWS_BYTES = (size_t)64 << 20;  // the handle's own rows of one pass
+
+// i and l of every column, checked against psd[]: what jsdr_bpsk_scope_spec_layout states and a spectra call relies on
+static int spec_layout_check(int len, int width, int32_t *first, int32_t *count, const char *who)
+{
+    JSDR_REQUIRE(len >= 2, "%s: len=%d below 2", who, len);
+    JSDR_REQUIRE(width >= 1 && width <= SPEC_WIDTH_MAX, "%s: plot_width=%d outside 1 .. %d; the handle is unchanged", who, width,
+                 SPEC_WIDTH_MAX);
+    for (int m = 0; m < width; m++) {
+        int i, l;
+        scope_spec_column(len, width, m, i, l);
+        JSDR_REQUIRE(i >= 0 && l >= 0 && (long long)i + (l > 1 ? l : 1) <= len, "%s: column %d of %d reads psd[%d .. %d) of %d bins", who, m,
+                     width, i, i + l, len);
+        if (first) first[m] = i;
+        if (count) count[m] = l;
+    }
+    return JSDR_OK;
+}
+
+int jsdr_bpsk_scope_spec_layout(int len, int plot_width, int32_t *first, int32_t *count, int cap)
+{
+    JSDR_REQUIRE(cap >= plot_width, "jsdr_bpsk_scope_spec_layout: cap=%d below plot_width=%d", cap, plot_width);
+    return spec_layout_check(len, plot_width, first, count, "jsdr_bpsk_scope_spec_layout");
+}
+
+int jsdr_bpsk_scope_chunk(jsdr_bpsk *h, int frames_per_pass)
+{
+    JSDR_REQUIRE(h, "jsdr_bpsk_scope_chunk: null handle");
+    JSDR_REQUIRE(frames_per_pass >= 0, "jsdr_bpsk_scope_chunk: frames_per_pass=%d is negative; the handle is unchanged", frames_per_pass);
+    h->scope_spec_chunk = frames_per_pass;
+    return JSDR_OK;
+}
+
+// what a spectra call refuses on top of the scope call, before any device work
+static int spec_check(const ScopeSpecReq &sq, const ScopeGeom &g, const double *ds_dev, const char *who)
+{
+    static const char *const row[2] = {"tuned", "ds"};
+    for (int k = 0; k < 2; k++) {
+        if (!sq.want(k)) continue;
+        const int len = k ? g.L : g.n;
+        JSDR_REQUIRE(scope_spec_form(len), "%s: no spectrum kernel serves the %s rows of %d points (served: powers of two %d .. %d, every "
+                     "other length up to %d); the handle is unchanged", who, row[k], len, SPEC_POW2_MIN, SPEC_POW2_MAX, FM_NMAX);
+        if (sq.spec[k] && spec_layout_check(len, sq.width, nullptr, nullptr, who) != JSDR_OK) return JSDR_ERR;
+        JSDR_REQUIRE((reinterpret_cast<uintptr_t>(sq.spec[k]) & 3) == 0, "%s: %cspec_dev is not aligned to 4 bytes; the handle is unchanged",
+                     who, row[k][0]);
+        JSDR_REQUIRE((reinterpret_cast<uintptr_t>(sq.peak[k]) & 15) == 0 && (reinterpret_cast<uintptr_t>(sq.psd[k]) & 15) == 0,
+                     "%s: %cpeak_dev or %cpsd_dev is not aligned to 16 bytes; the handle is unchanged", who, row[k][0], row[k][0]);
+    }
+    JSDR_REQUIRE(!sq.want(1) || (reinterpret_cast<uintptr_t>(ds_dev) & 15) == 0, "%s: ds_dev is not aligned to 16 bytes, which the cyan "
+                 "spectrum's 16-byte loads need; the handle is unchanged", who);
+    return JSDR_OK;
+}
+
+// the plan of spectrum k and its tables on the device, built once a handle (again where the row length has changed)
+static int spec_plan_ensure(jsdr_bpsk *h, int k, int len, const char *who)
+{
+    if (h->scope_spec_plan[k].n == len && h->scope_spec_w[k].p) return JSDR_OK;
+    std::vector<double2> w;
+    FftPlan pl;
+    JSDR_REQUIRE(fft_plan_build_row(pl, w, len) && !w.empty(), "%s: internal: no plan for a row of %d points", who, len);
+    DevBuf<double2> d;
+    if (d.alloc(w.size()) != JSDR_OK) return JSDR_ERR;
+    JSDR_HIP_TRY(hipMemcpy(d.p, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice));
+    h->scope_spec_w[k] = std::move(d);
+    h->scope_spec_plan[k] = pl;
+    return JSDR_OK;
+}
+
+static ScopeSpecArgs spec_args(const jsdr_bpsk *h, const ScopeSpecReq &sq, int k, const ScopeGeom &g, const double2 *rows, int c, int f0)
+{
+    ScopeSpecArgs sa = {};
+    sa.rows = rows;
+    sa.len = k ? g.L : g.n;
+    sa.c = c;
+    sa.frames = g.frames;
+    sa.f0 = f0;
+    sa.width = sq.spec[k] ? sq.width : 1;
+    sa.pi = (double)(sa.len / 2) / (double)sa.width;  // :285, :317
+    sa.l = (int)sa.pi;
+    sa.spec = sq.spec[k];
+    sa.peak = sq.peak[k];
+    sa.psd = sq.psd[k];
+    sa.logn = h->scope_spec_plan[k].logn;
+    sa.tw = h->scope_spec_w[k].p;
+    sa.m = h->scope_spec_plan[k].args;
+    sa.m.f.tw = sa.tw;
+    sa.m.f.n = sa.len;
+    return sa;
+}
+
 static int scope_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev, int64_t stride, int64_t L, int ic, int qc,
                      double *tuned_dev, double *ds_dev, double *iq_dev, double *max_dev, int32_t *pts_dev, int8_t *bits_dev, void *stream,
-                     const char *who)
+                     const char *who, const ScopeSpecReq *sq = nullptr)
 {
     ScopeGeom g;
     JSDR_REQUIRE(h, "%s: null handle", who);
@@ -364,7 +460,17 @@ static int scope_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev
     const long long tiles = (g.n + SCOPE_TILE - 1) / SCOPE_TILE;
     JSDR_REQUIRE(rows * tiles < (1LL << 31), "%s: nsamples=%lld: %lld rows of %lld tiles exceed one launch; the handle is unchanged", who,
                  (long long)L, rows, tiles);
+    if (sq && spec_check(*sq, g, ds_dev, who) != JSDR_OK) return JSDR_ERR;
     hipStream_t st = as_stream(stream);
+    // a spectrum whose rows the caller did not ask for reads rows of the handle's own, a pass of own_c frames at a time
+    const bool own_t = sq && sq->want(0) && !tuned_dev, own_d = sq && sq->want(1) && !ds_dev;
+    int own_c = 0;
+    if (own_t || own_d) {
+        const size_t per = (size_t)g.nstreams * sizeof(double2) * ((own_t ? (size_t)g.n : 0) + (own_d ? (size_t)g.L : 0));
+        size_t c = SCOPE_SPEC_ROWS_BYTES / per;
+        if (h->scope_spec_chunk > 0 && c > (size_t)h->scope_spec_chunk) c = (size_t)h->scope_spec_chunk;
+        own_c = (int)(c < 1 ? 1 : c > (size_t)g.frames ? (size_t)g.frames : c);
+    }
     const bool want_front = tuned_dev || ds_dev, want_walk = pts_dev || bits_dev, want_pts = iq_dev || max_dev || pts_dev;
     // the scratch, before anything of the handle moves on: what can fail for want of memory leaves the handle as it was
     if (want_walk && !h->scope_tail0.p) {
@@ -372,7 +478,18 @@ static int scope_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev
             h->scope_ev_walk.create(hipEventDisableTiming) != JSDR_OK)
             return JSDR_ERR;
     }
-    if (want_front) {
+    if (sq) {
+        for (int k = 0; k < 2; k++)
+            if (sq->want(k) && spec_plan_ensure(h, k, k ? g.L : g.n, who) != JSDR_OK) return JSDR_ERR;
+        const size_t own_rows = (size_t)g.nstreams * (size_t)own_c;
+        if (own_t && h->scope_spec_tuned.n < own_rows * (size_t)g.n && h->scope_spec_tuned.alloc(own_rows * (size_t)g.n) != JSDR_OK)
+            return JSDR_ERR;
+        if (own_d && h->scope_spec_ds.n < own_rows * (size_t)g.L * 2 && h->scope_spec_ds.alloc(own_rows * (size_t)g.L * 2) != JSDR_OK)
+            return JSDR_ERR;
+        if (own_c && own_c < g.frames && !h->scope_spec_hist.p && h->scope_spec_hist.alloc((size_t)g.nstreams * 32) != JSDR_OK)
+            return JSDR_ERR;
+    }
+    if (want_front || own_c) {
         if (!h->scope_k9.p && h->scope_k9.alloc((size_t)h->max_batch + SCHED_HIST) != JSDR_OK) return JSDR_ERR;
         if (sincos9_ensure(h) != JSDR_OK) return JSDR_ERR;
     }
@@ -396,12 +513,12 @@ static int scope_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev
         if (!h->scope_name.empty()) h->scope_name += "+";
         h->scope_name += k;
     };
-    if (want_front) {
+    ScopeFrontArgs fa;
+    if (want_front || own_c) {
         // the call's tuner schedule as a 9-bit table: the schedule's index where the sample was mixed, 256 where it passed (:395)
         expand_k9(h->scope_h_k9, h->cur.ktu.data(), 0, (long long)L, first ? nullptr : mh0, h->cur.f0, h->cur.n0);
         JSDR_HIP_TRY(hipMemcpyAsync(h->scope_k9.p, h->scope_h_k9.data(), sizeof(unsigned short) * ((size_t)L + SCHED_HIST),
                                     hipMemcpyHostToDevice, st));
-        ScopeFrontArgs fa;
         fa.raw = reinterpret_cast<const int *>(raw_dev);
         fa.rawf = reinterpret_cast<const float2 *>(rawf_dev);
         fa.stride_pairs = stride / 2;
@@ -415,6 +532,8 @@ static int scope_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev
         memcpy(fa.taps, taps, sizeof(fa.taps));
         fa.tuned = reinterpret_cast<double2 *>(tuned_dev);
         fa.ds = ds_dev;
+    }
+    if (want_front) {
         const dim3 grid((unsigned)(rows * tiles));
         if (rawf_dev)
             hipLaunchKernelGGL(k_bpsk_scope_front<true>, grid, dim3(SCOPE_THREADS), 0, st, fa, g);
@@ -453,6 +572,49 @@ static int scope_run(jsdr_bpsk *h, const int16_t *raw_dev, const float *rawf_dev
         JSDR_LAUNCH_CHECK();
         named("k_bpsk_scope_pts");
     }
+    if (!sq) return JSDR_OK;
+    // the spectra over the caller's rows: one launch each over the whole call
+    const double2 *caller[2] = {reinterpret_cast<const double2 *>(tuned_dev), reinterpret_cast<const double2 *>(ds_dev)};
+    const bool own[2] = {own_t, own_d};
+    const char *form[2] = {scope_spec_form(g.n), scope_spec_form(g.L)};
+    for (int k = 0; k < 2; k++) {
+        if (!sq->want(k) || own[k]) continue;
+        if (launch_scope_spec(spec_args(h, *sq, k, g, caller[k], g.frames, 0), rows, st) != JSDR_OK) return JSDR_ERR;
+    }
+    // ... and over the handle's: a pass of own_c frames of every stream through k_bpsk_scope_front, then its spectra
+    for (int f0 = 0; own_c && f0 < g.frames; f0 += own_c) {
+        const int c = g.frames - f0 < own_c ? g.frames - f0 : own_c;
+        const long long skip = (long long)f0 * g.n;  // samples of the call in front of the pass
+        ScopeFrontArgs pa = fa;
+        ScopeGeom pg = g;
+        pg.n_in = g.n_in + skip;
+        pg.frames = c;
+        if (pa.raw) pa.raw += skip;
+        if (pa.rawf) pa.rawf += skip;
+        pa.k9 += skip;
+        if (f0 > 0) {
+            HistArgs ha = hist_args(h, fa.raw, fa.rawf, fa.stride_pairs, skip, ic, qc, g.nstreams);
+            ha.hist_old = fa.hist;
+            ha.hist_new = h->scope_spec_hist.p;
+            if (launch_hist_in(ha, st) != JSDR_OK) return JSDR_ERR;
+            pa.hist = h->scope_spec_hist.p;
+        }
+        pa.tuned = own_t ? h->scope_spec_tuned.p : nullptr;
+        pa.ds = own_d ? h->scope_spec_ds.p : nullptr;
+        const long long prows = (long long)g.nstreams * c;
+        const dim3 grid((unsigned)(prows * tiles));
+        if (rawf_dev)
+            hipLaunchKernelGGL(k_bpsk_scope_front<true>, grid, dim3(SCOPE_THREADS), 0, st, pa, pg);
+        else
+            hipLaunchKernelGGL(k_bpsk_scope_front<false>, grid, dim3(SCOPE_THREADS), 0, st, pa, pg);
+        JSDR_LAUNCH_CHECK();
+        const double2 *mine[2] = {h->scope_spec_tuned.p, reinterpret_cast<const double2 *>(h->scope_spec_ds.p)};
+        for (int k = 0; k < 2; k++)
+            if (own[k] && launch_scope_spec(spec_args(h, *sq, k, g, mine[k], c, f0), prows, st) != JSDR_OK) return JSDR_ERR;
+    }
+    if (own_c && !want_front) named("k_bpsk_scope_front");
+    for (int k = 0; k < 2; k++)
+        if (sq->want(k)) named(form[k]);
     return JSDR_OK;
 }
 
@@ -471,4 +633,36 @@ int jsdr_bpsk_scope_f32(jsdr_bpsk *h, const float *iq_in_dev, int64_t stream_str
     JSDR_REQUIRE(h && iq_in_dev, "jsdr_bpsk_scope_f32: null %s; the handle is unchanged", h ? "input iq_in_dev" : "handle");
     return scope_run(h, nullptr, iq_in_dev, stream_stride_f32, nsamples, 0, 0, tuned_dev, ds_dev, iq_dev, max_dev, pts_dev, bits_dev, stream,
                      "jsdr_bpsk_scope_f32");
+}
+
+static ScopeSpecReq spec_req(int plot_width, int32_t *tspec_dev, double *tpeak_dev, double *tpsd_dev, int32_t *dspec_dev, double *dpeak_dev,
+                             double *dpsd_dev)
+{
+    ScopeSpecReq sq;
+    sq.width = plot_width;
+    sq.spec[0] = tspec_dev, sq.peak[0] = tpeak_dev, sq.psd[0] = tpsd_dev;
+    sq.spec[1] = dspec_dev, sq.peak[1] = dpeak_dev, sq.psd[1] = dpsd_dev;
+    return sq;
+}
+
+int jsdr_bpsk_scope_spectra_i16(jsdr_bpsk *h, const int16_t *raw_dev, int64_t stream_stride_i16, int64_t nsamples, int ic, int qc,
+                                double *tuned_dev, double *ds_dev, double *iq_dev, double *max_dev, int32_t *pts_dev, int8_t *bits_dev,
+                                int plot_width, int32_t *tspec_dev, double *tpeak_dev, double *tpsd_dev, int32_t *dspec_dev,
+                                double *dpeak_dev, double *dpsd_dev, void *stream)
+{
+    JSDR_REQUIRE(h && raw_dev, "jsdr_bpsk_scope_spectra_i16: null %s; the handle is unchanged", h ? "input raw_dev" : "handle");
+    const ScopeSpecReq sq = spec_req(plot_width, tspec_dev, tpeak_dev, tpsd_dev, dspec_dev, dpeak_dev, dpsd_dev);
+    return scope_run(h, raw_dev, nullptr, stream_stride_i16, nsamples, ic, qc, tuned_dev, ds_dev, iq_dev, max_dev, pts_dev, bits_dev, stream,
+                     "jsdr_bpsk_scope_spectra_i16", (sq.want(0) || sq.want(1)) ? &sq : nullptr);
+}
+
+int jsdr_bpsk_scope_spectra_f32(jsdr_bpsk *h, const float *iq_in_dev, int64_t stream_stride_f32, int64_t nsamples, double *tuned_dev,
+                                double *ds_dev, double *iq_dev, double *max_dev, int32_t *pts_dev, int8_t *bits_dev, int plot_width,
+                                int32_t *tspec_dev, double *tpeak_dev, double *tpsd_dev, int32_t *dspec_dev, double *dpeak_dev,
+                                double *dpsd_dev, void *stream)
+{
+    JSDR_REQUIRE(h && iq_in_dev, "jsdr_bpsk_scope_spectra_f32: null %s; the handle is unchanged", h ? "input iq_in_dev" : "handle");
+    const ScopeSpecReq sq = spec_req(plot_width, tspec_dev, tpeak_dev, tpsd_dev, dspec_dev, dpeak_dev, dpsd_dev);
+    return scope_run(h, nullptr, iq_in_dev, stream_stride_f32, nsamples, 0, 0, tuned_dev, ds_dev, iq_dev, max_dev, pts_dev, bits_dev, stream,
+                     "jsdr_bpsk_scope_spectra_f32", (sq.want(0) || sq.want(1)) ? &sq : nullptr);
 }
